@@ -30,6 +30,12 @@ Prints ONE JSON line on rank 0, under 4 KB: the headline (metric, value, ms_per_
 roofline, cpu_baseline).  Everything else - per-kernel times, the other BASELINE configs, the
 scaling projection, the prose - goes to the side file the line names (`side_file`, under
 gpurun_out/): the driver keeps a few KB of stdout and a 28 KB line lost its front there.
+
+``--dump-outputs DIR``: after the timed steps, what the headline's last timed step computed - the
+arrays its caller receives (a stitch: the mosaic and the valid mask; cfg4: the pyramid, and with
+--detect the keypoints and descriptors) - goes to DIR/<name>.npy, at most 64 MB in all
+(``dump_outputs``).  The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -195,7 +201,15 @@ def parse():
                     help="where the whole record goes (default gpurun_out/bench_full_<workload>_n<N>.json)")
     ap.add_argument("--detect", action="store_true",
                     help="cfg4: time detectAndCompute (keypoints + descriptors) too")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline's last timed step "
+                         "computed - the arrays its caller receives - as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB in all, larger arrays as a fixed seeded "
+                         "sample, see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def workload(name):
@@ -499,32 +513,72 @@ def cpu_baseline(cfg):
 COMM = {}              # what the process group saw (pano360_amd.dist.describe_job), every line carries it
 INSTRUMENTED = {}      # seconds of the instrumented pass of the last timed_steps call
 IN_FLIGHT = {"n": 1}   # stitches in flight of the headline measurement (run_sets)
+DUMP_LIMIT = 64_000_000   # --dump-outputs: bytes of all the .npy files together
 
 
-def timed_steps(eng, step, steps, warmup, fence, finish=None):
+def dump_outputs(directory, outputs):
+    """--dump-outputs: every array of ``outputs`` (name -> device tensor or host array) as
+    ``directory/<name>.npy``, float32, or float64 where float32 would round (float64 and 32- or
+    64-bit integer sources).  The arrays share DUMP_LIMIT, the smallest served first.  One larger
+    than its share is written as a fixed, seeded sample of its flattened elements, their flat
+    positions in ``<name>_index.npy`` (float64): the same positions in every run, so two builds
+    can be compared output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    sizes = {name: int(np.prod(tuple(a.shape))) for name, a in outputs.items()}
+    names = sorted(outputs, key=lambda name: sizes[name])
+    left = DUMP_LIMIT
+    for i, name in enumerate(names):
+        a, n = outputs[name], sizes[name]
+        wide = str(a.dtype).split(".")[-1] in ("float64", "int32", "int64", "uint32", "uint64")
+        kind = np.float64 if wide else np.float32
+        share = left // (len(names) - i) - 512                  # (two .npy headers)
+        files = [os.path.join(directory, name + ".npy")]
+        if n * np.dtype(kind).itemsize <= share:
+            values = (a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(kind)
+        else:
+            index = np.sort(np.random.default_rng(0).choice(
+                n, share // (np.dtype(kind).itemsize + 8), replace=False))
+            flat = a.reshape(-1)
+            if torch.is_tensor(a):
+                values = flat[torch.from_numpy(index).to(a.device)].cpu().numpy()
+            else:
+                values = flat[index]
+            values = values.astype(kind)
+            files.append(os.path.join(directory, name + "_index.npy"))
+            np.save(files[1], index.astype(np.float64))
+        np.save(files[0], values)
+        left -= sum(os.path.getsize(f) for f in files)
+
+
+def timed_steps(eng, step, steps, warmup, fence, finish=None, keep=None):
     """W untimed steps, then exactly K steps between two fences: the headline time, with no
     instrumentation inside.  Then the same K steps once more with HIP events around every
     launch (`pano_timing_enable`): the per-kernel times of the roofline.  (The events cost
     2 % of a config-3 stitch, 7 % of config 2 and 29 % of config 4's seventy launches per
     frame - too much to charge the headline with.)  Returns (headline seconds on this rank,
     last step's result, per-kernel times); ``finish`` completes what the steps left in
-    flight (the exchange of the last stitch) inside each timed region."""
+    flight (the exchange of the last stitch) inside each timed region.  ``keep`` is called
+    with the headline region's last step result and what ``finish`` returned, after its
+    closing fence and before anything else runs (--dump-outputs)."""
     def region(events):
         fence()
         eng.timing(events)
         t0 = time.perf_counter()
         for _ in range(steps):
             result = step()
-        if finish:
-            finish()
+        last = finish() if finish else None
         fence()
-        return time.perf_counter() - t0, result
+        return time.perf_counter() - t0, result, last
     for _ in range(warmup):
         step()
     if finish:
         finish()
-    elapsed, result = region(False)
-    INSTRUMENTED["seconds"], result = region(True)
+    elapsed, result, last = region(False)
+    if keep is not None:
+        keep(result, last)
+    INSTRUMENTED["seconds"], result, _ = region(True)
     times = eng.kernel_times()
     eng.timing(False)
     return elapsed, result, times
@@ -571,8 +625,9 @@ class Watchdog:
             return True
 
 
-def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None):
-    """Config 4: Gaussian / DoG scale space of 3840 x 2160 frames, one frame per step."""
+def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None, keep=None):
+    """Config 4: Gaussian / DoG scale space of 3840 x 2160 frames, one frame per step.  ``keep``:
+    as in timed_steps, called with (pyramid, detection or None) of the last timed frame."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     detect = args.detect if detect is None else detect
@@ -617,8 +672,8 @@ def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None):
                 if job is not None:
                     state["kps"] = job.result()[0]
                     state["n_kp"] = len(state["kps"])
-                return state[key].pyramid, state.get("n_kp")
-            return pipes[lane].pyramid(frame), None
+                return state[key].pyramid, state.get("n_kp"), state[key]
+            return pipes[lane].pyramid(frame), None, None
 
     def fence():
         torch.cuda.synchronize()
@@ -649,7 +704,9 @@ def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None):
                     have = total.get(name, (0.0, 0))
                     total[name] = (have[0] + ms, have[1] + count)
             return total
-    elapsed, (pyr, n_kp), times = timed_steps(AllLanes(), step, steps, warmup, fence)
+    elapsed, (pyr, n_kp, _), times = timed_steps(
+        AllLanes(), step, steps, warmup, fence,
+        keep=None if keep is None else (lambda result, _: keep(result[0], result[2])))
     for lane in range(len(lanes)):           # the last frames' keypoints are still in flight
         job = state.get(("job", lane))
         if job is not None:
@@ -1098,8 +1155,29 @@ def main():
     reduce_device = eng.device if backend == "nccl" else "cpu"
     COMM.update(pdist.describe_job(eng.device, reduce_device))
 
+    def dumper(outputs_of):
+        """The headline's `keep` (timed_steps): --dump-outputs of what `outputs_of` makes of the
+        last timed step, on rank 0."""
+        if args.dump_outputs is None or rank != 0:
+            return None
+        return lambda *result: dump_outputs(args.dump_outputs, outputs_of(*result))
+
     if args.workload == "cfg4":
-        elapsed, pyr, n_kp, times, size = run_cfg4(args, eng, rank, world)
+        def cfg4_outputs(pyr, detection):
+            # the frame's pyramid octave by octave ([layers][h][w] float32); with --detect also its
+            # keypoints (one row each, the KP_DTYPE fields in order) and descriptors
+            import numpy as np
+            gauss, dog = pyr
+            out = {f"gauss_octave{o}": g for o, g in enumerate(gauss)}
+            out.update({f"dog_octave{o}": d for o, d in enumerate(dog)})
+            if detection is not None:
+                kps, desc = detection.result()
+                out["keypoints"] = np.stack([kps[f].astype(np.float64) for f in kps.dtype.names],
+                                            axis=1).reshape(len(kps), len(kps.dtype.names))
+                out["descriptors"] = desc
+            return out
+        elapsed, pyr, n_kp, times, size = run_cfg4(args, eng, rank, world,
+                                                   keep=dumper(cfg4_outputs))
         elapsed = pdist.max_over_ranks(elapsed, reduce_device)
         if rank == 0:
             out = cfg4_line(args, world, elapsed, pyr, n_kp, times, size)
@@ -1163,7 +1241,7 @@ def main():
                     total[name] = (have[0] + ms, have[1] + count)
             return total
 
-    def run_strips(exchange, setting):
+    def run_strips(exchange, setting, keep=None):
         """ONE panorama (image set 0) split into column strips, one per rank; the finished
         strips are composed on rank 0 (strong scaling)."""
         # consecutive stitches go round `lanes` engines, each with a stream and exchange buffers of
@@ -1192,13 +1270,14 @@ def main():
         runner.finish()
         fence()
         elapsed, (plan, _, patches), times = timed_steps(
-            AllLanes(engines, serial), strips_step, args.steps, args.warmup, fence, runner.finish)
+            AllLanes(engines, serial), strips_step, args.steps, args.warmup, fence, runner.finish,
+            keep)
         runner.close()                    # the lanes' communicators (collective: every rank, same order)
         return pdist.max_over_ranks(elapsed, reduce_device), plan, patches, times, runner
 
     ONE = {}                                 # one stitch at a time, of the last run_sets
 
-    def run_sets(setting):
+    def run_sets(setting, keep=None):
         """One image set per rank and step (rank r holds set r): independent panoramas,
         nothing crosses a GPU (replicas; the N = 1 path)."""
         my_set = pdist.assign_sets(world, rank, world)[0]
@@ -1230,18 +1309,19 @@ def main():
             with torch.cuda.stream(stream):
                 plan = (use.cached_plan(shapes, rots, intrs, True, NATIVE) if memo
                         else engine.Plan(shapes, rots, intrs, True, NATIVE))
-                mosaic, _, _, patches = use.stitch(frames, plan, "multiband", n_levels)
+                mosaic, _, valid, patches = use.stitch(frames, plan, "multiband", n_levels)
                 if setting["trusted"]:
                     done.append(torch.cuda.Event())
                     done[-1].record(stream)
             # keep only the window geometry: holding the arenas across steps would make
             # the allocator carve out fresh gigabytes every step
-            return plan, mosaic, list(patches)
+            return plan, (mosaic, valid), list(patches)
         for _ in range(3 * len(lanes)):
             step()
         fence()
         elapsed, (plan, _, patches), times = timed_steps(
-            AllLanes([use for use, _ in lanes], serial), step, args.steps, args.warmup, fence)
+            AllLanes([use for use, _ in lanes], serial), step, args.steps, args.warmup, fence,
+            keep=keep)
         # the same K steps one stitch at a time on one engine and stream, no instrumentation: what a
         # caller who hands in one image set and waits for its mosaic sees (the reference's timer,
         # stitcher.py:441-444, brackets one stitch) - `ms_per_stitch_one_in_flight` of the line
@@ -1418,8 +1498,10 @@ def main():
     def alt_entry(setting, ms, value):
         return dict(setting, ms_per_step=ms, value=value)
 
+    # what a caller of the stitch receives: the uint8 mosaic [H][W][3] and the valid mask [H][W]
+    sets_outputs = dumper(lambda result, _: dict(mosaic=result[1][0], valid=result[1][1]))
     if not strips:
-        elapsed, plan, patches, times = run_sets(headline_setting)
+        elapsed, plan, patches, times = run_sets(headline_setting, sets_outputs)
         out = build_line(False, headline_setting, elapsed, plan, patches, times) if rank == 0 else None
         if world == 1 and not args.no_secondary and args.workload == "cfg3":
             out["secondary"] = secondary_single_gpu(eng, fence, other_setting)
@@ -1495,7 +1577,8 @@ def main():
         COMM["preflight"] = pdist.preflight(eng.device, reduce_device,
                                             log=(lambda m: print(m, file=sys.stderr, flush=True))
                                             if rank == 0 else None)
-        elapsed, plan, patches, times, runner = run_strips(args.exchange, headline_setting)
+        elapsed, plan, patches, times, runner = run_strips(
+            args.exchange, headline_setting, dumper(lambda _, last: dict(mosaic=last)))
     except Exception as err:           # noqa: BLE001 - see above
         if dog.cancel() and rank == 0 and fallback is not None:
             fallback["strips_error"] = repr(err)[:300]
