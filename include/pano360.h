@@ -647,6 +647,66 @@ size_t pano_knn2_work_bytes(int nq, int nt, int d);
 int pano_knn2(pano_ctx *ctx, const float *query, int nq, const float *train, int nt, int d,
               float scale, void *work, int32_t *idx, float *dist, int *rescans);
 
+/* Lowe's ratio test over one pair's pano_knn2 result, packed for pano_hom_ransac
+ *                                                  features.py:232-243
+ * Query q survives iff (double) dist[q][0] < ratio * (double) dist[q][1] (strict; the reference
+ * compares cv2.DMatch distances in Python floats).  The survivors are written in ascending query
+ * order (a stable compaction) to pts (dev float [nq][4]: the query keypoint x, y, then its
+ * nearest train keypoint's x, y) and match (dev int32 [nq][2]: q, idx[q][0]); their number goes
+ * to *count (dev int32).  The capacity of pts / match is nq rows, so the caller sizes a pair's
+ * region on the host with no wait.  idx, dist: dev [nq][2] of pano_knn2; kp_query, kp_train: dev
+ * float [nq][2] / [nt][2] (centred keypoints); a train index outside [0, nt) never survives.
+ * pts 16-byte aligned, dist and the keypoints 8-byte aligned.  One launch, nothing waited for. */
+int pano_match_pack(pano_ctx *ctx, const int32_t *idx, const float *dist, int nq, double ratio,
+                    const float *kp_query, const float *kp_train, int nt, float *pts,
+                    int32_t *match, int32_t *count);
+
+/* RANSAC homographies of a batch of pairs                       features.py:244
+ * (cv2.findHomography(src, dst, cv2.RANSAC), restated; not pinned against OpenCV).
+ *   pts        dev float [m][4]: src x, y, dst x, y, all pairs packed, 16-byte aligned
+ *   offsets    dev int32 [n_pairs]: first row of each pair in pts
+ *   counts     dev int32 [n_pairs]: rows of each pair (< 4: the pair fails)
+ *   work       dev, pano_hom_ransac_work_bytes(n_pairs, max_iters) (may be NULL with hyp_inliers)
+ *   hom        dev double [n_pairs][9], row-major, hom[8] = 1; zeros on failure
+ *   mask       dev uint8 [m]: 1 = inlier of the best hypothesis; zeros on failure
+ *   n_inliers  dev int32 [n_pairs]: inliers of the best hypothesis; 0 on failure
+ *   hyp_inliers  optional dev int32 [n_pairs][max_iters]: every hypothesis's score (-1: invalid)
+ * Kernels on the context's stream and nothing else (no allocation, no wait, no host copy): the
+ * call may be captured into a graph.  Semantics, so that a model can reproduce every score:
+ * - Sampler.  Draw k (0..3) of attempt a (0..63) of hypothesis h (0..max_iters-1) of a pair of
+ *   `count` rows is ((r >> 32) * count) >> 32 with r = splitmix64(seed + G * (h * 256 + a * 4 + k
+ *   + 1)) in uint64 arithmetic, G = 0x9E3779B97F4A7C15 and splitmix64(x): z = x + G;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.
+ *   The key does not involve the pair's index or the batch: a pair's result is the same alone
+ *   and in any batch.
+ * - Degeneracy.  An attempt is rejected unless its four indices are distinct and, for each
+ *   triple (0,1,2), (0,1,3), (0,2,3), (1,2,3), the signed areas of the src and of the dst
+ *   triangle, (xb - xa) * (yc - ya) - (yb - ya) * (xc - xa) in f64, have a product > 0 (collinear
+ *   triples, flipped orientation and NaN all reject).  The first accepted attempt is the sample;
+ *   after 64 rejected attempts the hypothesis is invalid.
+ * - Hypothesis.  The exact 4-point homography in f64, h33 = 1: rows [x, y, 1, 0, 0, 0, -(u x),
+ *   -(u y) | u] and [0, 0, 0, x, y, 1, -(v x), -(v y) | v] per point, Gaussian elimination with
+ *   partial pivoting (column c: the first row r >= c of maximal |a_rc|, a NaN counting as
+ *   maximal; swap; a_rk = a_rk - (a_rc / a_cc) * a_ck for r > c, k > c), back substitution
+ *   (s = b_r; s = s - a_rk * h_k for k = r+1 .. 7; h_r = s / a_rr).  A zero or non-finite pivot
+ *   makes the hypothesis invalid.
+ * - Score.  Hf = the hypothesis rounded to float32; t2 = float32(float64(thresh)^2); in float32,
+ *   one rounding per operation, left to right: ww = 1 / ((Hf6 x + Hf7 y) + 1),
+ *   dx = ((Hf0 x + Hf1 y) + Hf2) * ww - u, dy likewise with Hf3..5 and v, err = dx dx + dy dy;
+ *   an inlier iff err <= t2.  Every hypothesis is scored (no adaptive stop).
+ * - Selection.  The most inliers, the lowest h of a tie.  mask is its inlier set (not re-tested
+ *   after the refit).
+ * - Refit.  Over the best hypothesis's inliers: Hartley normalisation (centroid to the origin,
+ *   mean distance sqrt 2, per image), the DLT's 9 x 9 normal matrix in f64 summed in a fixed
+ *   order, its smallest eigenvector (cyclic Jacobi), denormalised, scaled to h33 = 1.  The same
+ *   input gives the same bits on every run.  No Levenberg-Marquardt polish.
+ * - Failure.  count < 4, no valid hypothesis, fewer than 4 inliers, or a non-finite refit:
+ *   hom, n_inliers and the pair's mask are zero. */
+size_t pano_hom_ransac_work_bytes(int n_pairs, int max_iters);
+int pano_hom_ransac(pano_ctx *ctx, const float *pts, const int32_t *offsets, const int32_t *counts,
+                    int n_pairs, int max_iters, float thresh, uint64_t seed, void *work,
+                    double *hom, uint8_t *mask, int32_t *n_inliers, int32_t *hyp_inliers);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -166,6 +166,10 @@ _SIGNATURES = {
     "pano_sift_sort_unique": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "pano_knn2_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_knn2": (_i, [_vp, _vp, _i, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _vp]),
+    "pano_hom_ransac_work_bytes": (C.c_size_t, [_i, _i]),
+    "pano_hom_ransac": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_uint64, _vp, _vp, _vp, _vp,
+                             _vp]),
+    "pano_match_pack": (_i, [_vp, _vp, _vp, _i, C.c_double, _vp, _vp, _i, _vp, _vp, _vp]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -67,6 +67,9 @@ enum PanoKernelId {
     PK_KNN2,
     PK_BLUR_LEAN,
     PK_BLUR_LEAN5,
+    PK_RANSAC_SCORE,
+    PK_RANSAC_FINISH,
+    PK_MATCH_PACK,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------

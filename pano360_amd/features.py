@@ -18,10 +18,21 @@ restated, parity unpinned.
 * ``flann_matching(des1, des2)``        - features.py:222-232: the 2-nearest-neighbour
   search and Lowe's 0.7 ratio test, exhaustive and exact on the GPU (``pano_knn2``:
   matrix-core cross terms rank the candidates, the winners are re-evaluated in float32)
-  where the reference asks FLANN's randomised kd-trees for an approximate answer;
-  homography estimation (RANSAC) stays outside.
+  where the reference asks FLANN's randomised kd-trees for an approximate answer.
+* ``find_homography(src, dst, RANSAC)``  - features.py:244, ``cv2.findHomography`` with
+  ``cv2.RANSAC``: ``pano_hom_ransac`` scores every hypothesis of every pair of a batch on the
+  GPU and refits the winner (a Hartley-normalised DLT; no adaptive stop, no Levenberg-Marquardt
+  polish - include/pano360.h pins the contract).
+* ``matching(imgs)``, ``_match_hom``, ``_reverse`` - features.py:235-283: detection, 2-NN, the
+  ratio test (``pano_match_pack``) and one RANSAC launch over every pair; ``main`` writes the
+  ``matches_<name>.npz`` the reference's stitcher.py:423-428 loads.
 """
+import argparse
 import ctypes as C
+import logging
+import os
+import time
+from collections import defaultdict
 
 import numpy as np
 
@@ -465,13 +476,14 @@ def sift_detect_device(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
     return sift_detect_async(frame, max_keypoints, pyramid, eng).result()
 
 
-def sift_detector():
+def sift_detector(eng=None):
     """Closure, return a SIFT detecting function (features.py:192-201):
-    ``_detect(img) -> (keypoints, RootSIFT descriptors)``."""
+    ``_detect(img) -> (keypoints, RootSIFT descriptors)``.  ``eng``: the engine to detect on
+    (default: the process-wide one)."""
     def _detect(img):
-        eng = _eng.engine()
-        frame = eng.upload_frames([img])[0]
-        kps, desc = sift_detect_device(frame)
+        eng_ = eng if eng is not None else _eng.engine()
+        frame = eng_.upload_frames([img])[0]
+        kps, desc = sift_detect_device(frame, eng=eng_)
         des = desc.cpu().numpy()
         des = np.sqrt(des / (des.sum(axis=1, keepdims=True) + 1e-7))  # RootSIFT
         kp_ = [KeyPoint(k["x"], k["y"], k["size"], k["angle"], k["response"], k["octave"])
@@ -499,20 +511,35 @@ class DMatch:
         self.queryIdx, self.trainIdx, self.distance = int(query), int(train), float(distance)
 
 
-def knn2_device(des1, des2, eng=None, want_rescans=False):
+def _knn_scale(peak):
+    """A power of two that brings the largest magnitude to ~1024: float16 halves stay normal."""
+    return float(2.0 ** np.floor(np.log2(1024.0 / peak))) if peak > 0 else 1.0
+
+
+def knn2_device(des1, des2, eng=None, want_rescans=False, scale=None):
     """Two nearest rows of ``des2`` (Euclidean) for every row of ``des1``; both device
     float32 [K][D], D <= 128.  Returns (indices int64 [K1][2], distances float32 [K1][2]),
     nearest first.  ``pano_knn2``: the cross terms of |a - b|^2 on the matrix cores (split
     float16) rank the rows, the four best per query are re-evaluated exactly in float32 and
-    an error bound proves the rest cannot beat them (else that query is rescanned exactly)."""
+    an error bound proves the rest cannot beat them (else that query is rescanned exactly).
+    ``scale``: ``_knn_scale`` of the largest magnitude of both sets when the caller knows it
+    (no wait for the device's maximum)."""
+    idx, dist, rescans = _knn2_raw(des1, des2, eng or _eng.engine(), scale)
+    if want_rescans:
+        return idx.long(), dist, int(rescans.item())
+    return idx.long(), dist
+
+
+def _knn2_raw(des1, des2, eng, scale=None):
+    """``pano_knn2`` queued: (idx int32 [K1][2], dist float32 [K1][2], rescans int32 [1]) on the
+    device."""
     import torch
-    eng = eng or _eng.engine()
     nq, d = (int(v) for v in des1.shape)
     nt = int(des2.shape[0])
     des1, des2 = des1.contiguous(), des2.contiguous()
-    # a power of two that brings the largest magnitude to ~1024: float16 halves stay normal
-    peak = float(torch.maximum(des1.abs().amax(), des2.abs().amax()).item()) if nq else 1.0
-    scale = float(2.0 ** np.floor(np.log2(1024.0 / peak))) if peak > 0 else 1.0
+    if scale is None:
+        peak = float(torch.maximum(des1.abs().amax(), des2.abs().amax()).item()) if nq else 1.0
+        scale = _knn_scale(peak)
     work = torch.empty(int(eng.lib.pano_knn2_work_bytes(nq, nt, d)), dtype=torch.uint8,
                        device=eng.device)
     idx = torch.empty((nq, 2), dtype=torch.int32, device=eng.device)
@@ -521,9 +548,7 @@ def knn2_device(des1, des2, eng=None, want_rescans=False):
     _lib.check(eng.lib.pano_knn2(eng.ctx(), _eng._ptr(des1), nq, _eng._ptr(des2), nt, d,
                                  C.c_float(scale), _eng._ptr(work), _eng._ptr(idx),
                                  _eng._ptr(dist), _eng._ptr(rescans)), "pano_knn2")
-    if want_rescans:
-        return idx.long(), dist, int(rescans.item())
-    return idx.long(), dist
+    return idx, dist, rescans
 
 
 def flann_matching(des1, des2, ratio=0.7):
@@ -539,3 +564,211 @@ def flann_matching(des1, des2, ratio=0.7):
     idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
     keep = np.nonzero(dist[:, 0] < ratio * dist[:, 1])[0]
     return [DMatch(q, idx[q, 0], dist[q, 0]) for q in keep]
+
+
+# ------------------------------------------------------------- homographies (RANSAC)
+RANSAC = 8                  # cv2.RANSAC
+N_MIN_MATCH = 8             # features.py:17: minimum number of point matches
+LOWE_RATIO = 0.7            # features.py:232
+
+
+def find_homographies_device(pts, offsets, counts, max_iters=2000, thresh=3.0, seed=0,
+                             want_scores=False, eng=None):
+    """``pano_hom_ransac`` over a batch of pairs, device tensors in and out.
+    pts: float32 [m][4] (src x, y, dst x, y; every pair's rows back to back), offsets / counts:
+    int32 [n_pairs] (a pair with fewer than 4 rows fails).  Returns (hom float64 [n][3][3],
+    h33 = 1, zeros where the pair failed; mask uint8 [m]; n_inliers int32 [n], 0 = failed),
+    plus the scores int32 [n][max_iters] of every hypothesis (-1: invalid) with ``want_scores``.
+    Queued on the current stream, nothing waited for."""
+    import torch
+    eng = eng or _eng.engine()
+    dev = eng.device
+    n = int(offsets.shape[0])
+    pts = pts.reshape(-1, 4).to(device=dev, dtype=torch.float32).contiguous()
+    offsets = offsets.to(device=dev, dtype=torch.int32).contiguous()
+    counts = counts.to(device=dev, dtype=torch.int32).contiguous()
+    max_iters = int(max_iters)
+    if pts.shape[0] == 0:                   # (keeps the data pointer valid and aligned)
+        pts = torch.zeros((1, 4), dtype=torch.float32, device=dev)
+    hom = torch.zeros((n, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.zeros(max(int(pts.shape[0]), 1), dtype=torch.uint8, device=dev)
+    n_inl = torch.zeros(n, dtype=torch.int32, device=dev)
+    scores = torch.empty((n, max_iters), dtype=torch.int32, device=dev) if want_scores else None
+    work = None if want_scores else torch.empty(
+        int(eng.lib.pano_hom_ransac_work_bytes(n, max_iters)), dtype=torch.uint8, device=dev)
+    _lib.check(eng.lib.pano_hom_ransac(eng.ctx(), _eng._ptr(pts), _eng._ptr(offsets),
+                                       _eng._ptr(counts), n, max_iters, C.c_float(thresh),
+                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _eng._ptr(work),
+                                       _eng._ptr(hom), _eng._ptr(mask), _eng._ptr(n_inl),
+                                       _eng._ptr(scores)), "pano_hom_ransac")
+    out = (hom, mask, n_inl)
+    return out + (scores,) if want_scores else out
+
+
+def find_homography(srcPoints, dstPoints, method=RANSAC, ransacReprojThreshold=3.0,
+                    maxIters=2000, confidence=0.995, seed=0):
+    """``cv2.findHomography(src, dst, cv2.RANSAC, ...)`` (features.py:244) on the GPU.
+    Points (N, 2) or (N, 1, 2).  Returns (H float64 (3, 3) with H[2, 2] = 1, mask uint8 (N, 1)),
+    or (None, None) when no homography is found.  Every one of ``maxIters`` hypotheses is scored:
+    ``confidence`` is accepted for compatibility and not used; the refit is a normalised DLT over
+    the inliers without OpenCV's Levenberg-Marquardt polish; ``seed`` picks the samples
+    (include/pano360.h, pano_hom_ransac)."""
+    import torch
+    if method != RANSAC:
+        raise ValueError(f"find_homography: method {method!r} (only RANSAC = {RANSAC})")
+    src = np.asarray(srcPoints, np.float32).reshape(-1, 2)
+    dst = np.asarray(dstPoints, np.float32).reshape(-1, 2)
+    if len(src) != len(dst):
+        raise ValueError(f"find_homography: {len(src)} source and {len(dst)} destination points")
+    m = len(src)
+    if m < 4:
+        return None, None
+    eng = _eng.engine()
+    pts = torch.from_numpy(np.ascontiguousarray(np.concatenate([src, dst], axis=1))).to(eng.device)
+    zero = torch.zeros(1, dtype=torch.int32)
+    hom, mask, n_inl = find_homographies_device(pts, zero, torch.full((1,), m, dtype=torch.int32),
+                                                maxIters, ransacReprojThreshold, seed, eng=eng)
+    if int(n_inl.cpu()[0]) == 0:
+        return None, None
+    return hom[0].cpu().numpy(), mask[:m].cpu().numpy().reshape(m, 1)
+
+
+class _Pairs:
+    """Every pair's correspondences packed back to back on the device: per pair, the ratio test
+    over ``pano_knn2`` (``pano_match_pack``) into a region of as many rows as the query image has
+    keypoints, then ONE ``pano_hom_ransac`` over the pairs with at least N_MIN_MATCH survivors.
+    Nothing is waited for until ``download``."""
+
+    def __init__(self, kpts, descs, pairs, eng, max_iters=2000, thresh=3.0, seed=0):
+        import torch
+        self.pairs, dev = list(pairs), eng.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        kp_dev = [torch.from_numpy(np.ascontiguousarray(k, np.float32).reshape(-1, 2)).to(dev)
+                  for k in kpts]
+        des_dev = [torch.from_numpy(np.ascontiguousarray(d, np.float32)).to(dev) for d in descs]
+        peaks = [float(np.abs(d).max()) if len(d) else 0.0 for d in descs]
+        sizes = [len(kpts[i]) for i, _ in self.pairs]
+        self.offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(self.offsets[-1])
+        self.pts = torch.zeros((max(total, 1), 4), **f32)
+        self.match = torch.zeros((max(total, 1), 2), dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(len(self.pairs), dtype=torch.int32, device=dev)
+        for p, (i, j) in enumerate(self.pairs):
+            nq, nt = len(kpts[i]), len(kpts[j])
+            if nq == 0 or nt < 2:
+                continue
+            idx, dist, _ = _knn2_raw(des_dev[i], des_dev[j], eng,
+                                     _knn_scale(max(peaks[i], peaks[j])))
+            off = int(self.offsets[p])
+            _lib.check(eng.lib.pano_match_pack(
+                eng.ctx(), _eng._ptr(idx), _eng._ptr(dist), nq, C.c_double(LOWE_RATIO),
+                _eng._ptr(kp_dev[i]), _eng._ptr(kp_dev[j]), nt, _eng._ptr(self.pts[off:]),
+                _eng._ptr(self.match[off:]), _eng._ptr(self.counts[p:])), "pano_match_pack")
+        # pairs below N_MIN_MATCH survivors take part with no rows: they fail without a wait
+        eff = torch.where(self.counts >= N_MIN_MATCH, self.counts, torch.zeros_like(self.counts))
+        off_dev = torch.from_numpy(self.offsets[:-1].astype(np.int32)).to(dev)
+        self.hom, self.mask, self.n_inl = find_homographies_device(
+            self.pts, off_dev, eff, max_iters, thresh, seed, eng=eng)
+
+    def download(self):
+        """{(i, j): (match int32 [M][2] of the inliers, hom float64 (3, 3))} of the pairs that
+        registered: one wait."""
+        import torch
+        host = [torch.empty(t.shape, dtype=t.dtype).pin_memory()
+                for t in (self.counts, self.n_inl, self.hom, self.mask, self.match)]
+        for h, t in zip(host, (self.counts, self.n_inl, self.hom, self.mask, self.match)):
+            h.copy_(t, non_blocking=True)
+        torch.cuda.current_stream(self.counts.device).synchronize()
+        counts, n_inl, hom, mask, match = (h.numpy() for h in host)
+        out = {}
+        for p, pair in enumerate(self.pairs):
+            if counts[p] < N_MIN_MATCH or n_inl[p] == 0:
+                continue
+            o, c = int(self.offsets[p]), int(counts[p])
+            out[pair] = (match[o:o + c][mask[o:o + c] != 0].copy(), hom[p].copy())
+        return out
+
+
+def _match_hom(pt1, pt2, des1, des2):
+    """Match points, estimate homography and return inlier matches (features.py:235-247):
+    (match int32 [M][2] of the inliers, hom float64 (3, 3)), or (None, None) below N_MIN_MATCH
+    ratio-test survivors or when RANSAC finds nothing."""
+    got = _Pairs([pt1, pt2], [des1, des2], [(0, 1)], _eng.engine()).download()
+    return got.get((0, 1), (None, None))
+
+
+def _reverse(match, hom):
+    """Find the matches and homography for the image is reverse order (features.py:250-252)."""
+    return np.fliplr(match), np.linalg.inv(hom)
+
+
+def _centred_keypoints(kp_, img):
+    cent = np.array([img.shape[1], img.shape[0]]) / 2
+    pts = np.array([kp.pt for kp in kp_], np.float64).reshape(-1, 2)
+    return np.float32(pts - cent)
+
+
+def matching(imgs, detect=sift_detector()):
+    """Find correspondences between images in a list (features.py:255-283).
+    Returns (kpts, matches): kpts a 1-D object array of N float32 [K_i][2] keypoint arrays,
+    centred on the image; matches a 0-d object array holding a ``defaultdict(dict)`` with
+    ``[i][j] = (int32 [M][2] inlier (query, train) indices, float64 (3, 3) homography i -> j)``
+    and ``[j][i] = _reverse(...)``, inserted in the reference's loop order.  Every pair is
+    matched on the device and all pairs share one RANSAC launch; a pair with fewer than
+    N_MIN_MATCH ratio-test survivors, or whose RANSAC fails, gets no entry (the reference would
+    stop on a failed findHomography)."""
+    kpts, descs = [], []
+    start = time.time()
+    for i, img in enumerate(imgs):
+        logging.debug(f"Processing image #{i+1}")
+        kp_, des = detect(img)         # (host results: nothing of the detector's ring is held)
+        kpts.append(_centred_keypoints(kp_, img))
+        descs.append(np.asarray(des, np.float32).reshape(len(kp_), -1))
+    logging.info(f"Extracted keypoints, time: {time.time() - start}")
+
+    n_imgs = len(imgs)
+    start = time.time()
+    pairs = [(src, dst) for src in range(n_imgs) for dst in range(src + 1, n_imgs)]
+    found = _Pairs(kpts, descs, pairs, _eng.engine()).download() if pairs else {}
+    logging.info(f"Matched features, time: {time.time() - start}")
+    return _assemble(kpts, found)
+
+
+def _assemble(kpts, found):
+    """matching's return value from the keypoints and {(src, dst): (match, hom)} of the pairs
+    that registered: keys in the reference's loop order (src ascending, dst ascending, the
+    reverse entry straight after), which is the order ``traverse`` walks them in."""
+    matches, n_imgs = defaultdict(dict), len(kpts)
+    for src in range(n_imgs):
+        for dst in range(src + 1, n_imgs):
+            if (src, dst) not in found:
+                continue
+            match, hom = found[(src, dst)]
+            matches[src][dst] = (match, hom)
+            matches[dst][src] = _reverse(match, hom)
+    kpt_arr = np.empty(len(kpts), dtype=object)     # 1-D even when every K_i is the same
+    for i, k in enumerate(kpts):
+        kpt_arr[i] = k
+    match_arr = np.empty((), dtype=object)
+    match_arr[()] = matches
+    return kpt_arr, match_arr
+
+
+def main(argv=None):
+    """Script entry point (features.py:300-320): the images of ``--path``, shrunk by half,
+    matched; writes ``matches_<name>.npz``.  Read with Pillow, resized on the device."""
+    from .stitcher import ingest
+    parser = argparse.ArgumentParser(description="Extract features.")
+    parser.add_argument("--path", type=str, default="../data/ppwwyyxx/CMU2",
+                        help="directory with the images to process.")
+    args = parser.parse_args(argv)
+    name = os.path.basename(args.path)
+    imgs = ingest(args.path, 2)
+    kpts, matches = matching(imgs)
+    np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
+    return kpts, matches
+
+
+if __name__ == "__main__":
+    logging.basicConfig(level=logging.DEBUG)
+    main()

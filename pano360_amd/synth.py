@@ -71,3 +71,34 @@ def make_scene(n, width, height, sweep_deg=None, step_deg=None, jitter=0.0,
                                jitter, seed)
     imgs = [make_frame(seed + i, width, height, kind) for i in range(n)]
     return imgs, rots, intrs
+
+
+def render_rig(pano, rots, intrs, width, height, device):
+    """Frames of a rig looking at one equirectangular panorama (uint8 [H][W][3], host): pixel
+    (u, v) of camera i looks along R_i^T K_i^-1 (u - w/2, v - h/2, 1) (the reference's
+    conventions, bundle_adj.py:28-29) and takes the panorama's bilinear sample at that ray's
+    longitude / latitude (longitude wraps).  Returns uint8 [height][width][3] tensors on
+    ``device`` (torch, float64 geometry)."""
+    import torch
+    ph, pw = pano.shape[:2]
+    src = torch.from_numpy(np.ascontiguousarray(pano)).to(device).double()
+    vv, uu = torch.meshgrid(torch.arange(height, dtype=torch.float64, device=device),
+                            torch.arange(width, dtype=torch.float64, device=device), indexing="ij")
+    pix = torch.stack([uu - width / 2, vv - height / 2, torch.ones_like(uu)]).reshape(3, -1)
+    frames = []
+    for rot, intr in zip(rots, intrs):
+        ray = torch.from_numpy(rot.T @ np.linalg.inv(intr)).to(device) @ pix
+        theta = torch.atan2(ray[0], ray[2])
+        phi = torch.atan2(ray[1], torch.sqrt(ray[0] ** 2 + ray[2] ** 2))
+        x = (theta + np.pi) / (2 * np.pi) * pw - 0.5
+        y = ((phi + np.pi / 2) / np.pi * ph - 0.5).clamp(0, ph - 1)
+        x0, y0 = torch.floor(x), torch.floor(y).clamp(max=ph - 2)
+        fx, fy = (x - x0)[:, None], (y - y0)[:, None]
+        xi0, yi0 = x0.long() % pw, y0.long()
+        xi1 = (xi0 + 1) % pw
+        top = src[yi0, xi0] * (1 - fx) + src[yi0, xi1] * fx
+        bot = src[yi0 + 1, xi0] * (1 - fx) + src[yi0 + 1, xi1] * fx
+        img = top * (1 - fy) + bot * fy
+        frames.append(torch.round(img).clamp(0, 255).to(torch.uint8).reshape(height, width, 3)
+                      .contiguous())
+    return frames
