@@ -148,12 +148,14 @@ struct pano_ctx {
     // pano_sift_extrema: the list of scale-space extrema between its two kernels (+ its counter)
     uint32_t *sift_raw;
     size_t sift_raw_cap;
+    bool sift_capturing;            // pano_sift_detect is capturing a launch sequence (detect.hip)
     // pano_sift_detect: the captured launch sequences, one per set of buffers (detect.hip)
     std::vector<PanoSiftGraph> sift_graphs;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);
 void pano_sift_graphs_free(pano_ctx *ctx);   // detect.hip
+int pano_sift_raw_reserve(pano_ctx *ctx, int rows, int cols);   // sift.hip: the extrema list's size
 int pano_zero_i32(hipStream_t s, int *p, int n);   // detect.hip: p[0 .. n) = 0, as a kernel
 int pano_ctx_side_stream(pano_ctx *ctx);     // makes ctx->side and the fork / join events
 // Device copy of a host tap table set (and, with `tables`, its matrix-core operand tables'

@@ -33,8 +33,9 @@ static uint64_t fnv(uint64_t h, const void *p, size_t bytes) {
     return h;
 }
 
-// Everything the launch sequence depends on: sizes, switches, every buffer address, the taps' values.
-static uint64_t detect_key(const pano_sift_args *a, const uint8_t *frame) {
+// Everything the launch sequence depends on: sizes, switches, every buffer address (the context's
+// extrema list and its capacity among them), the taps' values.
+static uint64_t detect_key(const pano_ctx *ctx, const pano_sift_args *a, const uint8_t *frame) {
     uint64_t h = 1469598103934665603ull;
     const int ints[8] = {a->h, a->w, a->n_octaves, a->n_layers, a->first_octave, a->max_keypoints,
                          a->detect, 0};
@@ -42,8 +43,10 @@ static uint64_t detect_key(const pano_sift_args *a, const uint8_t *frame) {
     const float fl[3] = {a->contrast_thr, a->edge_thr, a->sigma};
     h = fnv(h, fl, sizeof(fl));
     const void *ptrs[10] = {frame, a->work, a->gauss_dev, a->dims_dev, a->cands, a->kpts, a->counts,
-                            a->sort_work, a->desc, nullptr};
+                            a->sort_work, a->desc, a->detect ? ctx->sift_raw : nullptr};
     h = fnv(h, ptrs, sizeof(ptrs));
+    const size_t raw_cap = a->detect ? ctx->sift_raw_cap : 0;
+    h = fnv(h, &raw_cap, sizeof(raw_cap));
     h = fnv(h, a->gauss, (size_t)a->n_octaves * sizeof(float *));
     h = fnv(h, a->dog, (size_t)a->n_octaves * sizeof(float *));
     size_t floats = 0;
@@ -117,7 +120,15 @@ extern "C" int pano_sift_detect(pano_ctx *ctx, const pano_sift_args *a) {
     // replay needs a frame buffer of its own (a graph holds addresses): `frame_copy`, optional
     const bool graphs = ctx->opt[PANO_OPT_SIFT_GRAPH] != 0 && !ctx->timing_on && a->frame_copy;
     if (!graphs) return queue_frame(ctx, a, a->frame);
-    const uint64_t key = detect_key(a, a->frame_copy);
+    // The extrema list is the context's, not the workspace's: a graph holds its address and capacity.
+    // Sized for this frame HERE (octave 0 is the largest; the condition and the size are
+    // pano_sift_extrema's), before the key that hashes it: a growth - which waits for every stream
+    // and frees the old list - changes the key of every detecting sequence, so no graph captured
+    // before it is replayed again (they leave through the LRU below), and the capture further down
+    // finds the list large enough (pano_sift_raw_reserve refuses to grow it inside a capture).
+    if (a->detect && 2 * a->h < 16384 && 2 * a->w < 16384)
+        if (int rc = pano_sift_raw_reserve(ctx, 2 * a->h, 2 * a->w)) return rc;
+    const uint64_t key = detect_key(ctx, a, a->frame_copy);
     PanoSiftGraph *slot = nullptr;
     for (PanoSiftGraph &g : ctx->sift_graphs)
         if (g.key == key) slot = &g;
@@ -150,7 +161,9 @@ extern "C" int pano_sift_detect(pano_ctx *ctx, const pano_sift_args *a) {
             hipError_t e = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
                 ctx->stream = cap;
+                ctx->sift_capturing = true;
                 const int rc = queue_front(ctx, a, a->frame_copy);
+                ctx->sift_capturing = false;
                 ctx->stream = s;
                 e = hipStreamEndCapture(cap, &graph);                // (always: leaves capture mode)
                 if (rc != PANO_OK || e != hipSuccess || !graph) {

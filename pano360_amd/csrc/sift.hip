@@ -646,6 +646,28 @@ __global__ __launch_bounds__(64 * SIFT_WAVES) void sift_describe_kernel(
     }
 }
 
+// The context's list of scale-space extrema, grown (never shrunk) to hold an octave of rows x cols:
+// a quarter of its samples, at least 1 << 20 entries.  A captured launch sequence of
+// pano_sift_detect holds the list's address and capacity as kernel arguments: the list never grows
+// inside a capture (pano_sift_detect sizes it for the frame before capturing, and hashes it into
+// the graph's key, so a graph made before a growth never matches again).
+int pano_sift_raw_reserve(pano_ctx *ctx, int rows, int cols) {
+    const size_t need = (size_t)rows * cols / 4 > (1u << 20) ? (size_t)rows * cols / 4 : (1u << 20);
+    if (need <= ctx->sift_raw_cap) return PANO_OK;
+    PANO_REQUIRE(!ctx->sift_capturing,
+                 "pano_sift_raw_reserve: the extrema list would grow inside a capture");
+    if (ctx->sift_raw) {
+        // kernels on ANY stream this context has targeted - a replay included - may still use it
+        PANO_HIP(hipDeviceSynchronize());
+        PANO_HIP(hipFree(ctx->sift_raw));
+        ctx->sift_raw = nullptr;
+        ctx->sift_raw_cap = 0;
+    }
+    PANO_HIP(hipMalloc((void **)&ctx->sift_raw, (need + 1) * sizeof(uint32_t)));
+    ctx->sift_raw_cap = need;
+    return PANO_OK;
+}
+
 extern "C" int pano_sift_extrema(pano_ctx *ctx, const float *dog, int rows, int cols, int octave,
                                  int n_layers, float contrast_thr, float edge_thr, float sigma,
                                  pano_sift_keypoint *cands, int *count, int max_cands) {
@@ -658,16 +680,7 @@ extern "C" int pano_sift_extrema(pano_ctx *ctx, const float *dog, int rows, int 
     if (n_layers == 3 && rows < 16384 && cols < 16384) {
         // the streaming search + the refinement of the listed extrema
         const hipStream_t s = (hipStream_t)stream;
-        const size_t cap = (size_t)rows * cols / 4 > (1u << 20) ? (size_t)rows * cols / 4 : (1u << 20);
-        if (cap > ctx->sift_raw_cap) {
-            if (ctx->sift_raw) {
-                PANO_HIP(hipStreamSynchronize(s));       // a queued kernel may still read it
-                PANO_HIP(hipFree(ctx->sift_raw));
-                ctx->sift_raw = nullptr;
-            }
-            PANO_HIP(hipMalloc((void **)&ctx->sift_raw, (cap + 1) * sizeof(uint32_t)));
-            ctx->sift_raw_cap = cap;
-        }
+        if (int rc = pano_sift_raw_reserve(ctx, rows, cols)) return rc;
         int *raw_count = (int *)(ctx->sift_raw + ctx->sift_raw_cap);
         if (int rc = pano_zero_i32(s, raw_count, 1)) return rc;   // (a kernel: graph-safe, detect.hip)
         int seg_rows = 96;

@@ -236,16 +236,18 @@ class _SiftHost:
         self.pinned = None
         self.counts = torch.empty((self.SLOTS, 3), dtype=torch.int32).pin_memory()
         self.slot_events = [None] * self.SLOTS
+        self.slot_gens = [0] * self.SLOTS        # hand-outs of each slot: whose counts it holds
         self.next = 0
 
     def counter_slot(self):
-        """A pinned int32[3] that no queued copy still writes."""
+        """(slot, its generation, a pinned int32[3] that no queued copy still writes)."""
         with self.lock:
             k = self.next
             self.next = (k + 1) % self.SLOTS
             if self.slot_events[k] is not None:
                 self.slot_events[k].synchronize()
-            return k, self.counts[k]
+            self.slot_gens[k] += 1
+            return k, self.slot_gens[k], self.counts[k]
 
     def staging(self, nbytes):
         import torch
@@ -264,28 +266,45 @@ def _sift_host(eng):
 class SiftDetection:
     """A ``detectAndCompute`` queued on the device: nothing has been waited for yet.
     ``result()`` waits, checks the counters and returns (keypoints as a KP_DTYPE array in
-    OpenCV's order, descriptors float32 [K][128] on the device, values 0..255)."""
+    OpenCV's order, descriptors float32 [K][128] on the device, values 0..255).
 
-    def __init__(self, counts, kpts, desc, max_keypoints, keep, eng):
+    ``ring`` = (workspace, its generation when this frame was queued) for a frame in a workspace of
+    a ``SiftPipeline``: ``result()`` raises ``PanoError`` if a later frame has taken the workspace
+    before it.  ``owned``: the descriptors returned are a copy of the caller's own, not a view into
+    the workspace."""
+
+    def __init__(self, counts, kpts, desc, max_keypoints, keep, eng, ring=None, owned=False):
         import torch
         self.counts, self.kpts, self.desc, self.max_keypoints = counts, kpts, desc, max_keypoints
         self.keep = keep                    # buffers the queued kernels still read
+        self.ring, self.owned = ring, owned
         self._out = None
         self.host = _sift_host(eng)
         # the counters travel to pinned memory (a slot of the engine's ring) behind this frame's
         # kernels; `done` marks that point, so result() waits for THIS frame only, not for
         # whatever was queued after it
-        slot, self.host_counts = self.host.counter_slot()
+        self.slot, self.slot_gen, self.host_counts = self.host.counter_slot()
         self.host_counts.copy_(counts, non_blocking=True)
+        self.stream = torch.cuda.current_stream(counts.device)
         self.done = torch.cuda.Event()
-        self.done.record(torch.cuda.current_stream(counts.device))
-        self.host.slot_events[slot] = self.done
+        self.done.record(self.stream)
+        self.host.slot_events[self.slot] = self.done
 
     def result(self):
         import torch
         if self._out is None:
+            if self.ring is not None and self.ring[0]["gen"] != self.ring[1]:
+                raise _lib.PanoError("sift: the detection's workspace went to a later frame before "
+                                     "its result() was taken (a SiftPipeline keeps `depth` frames)")
             self.done.synchronize()
-            n_cand, n_kp, n_out = (int(v) for v in self.host_counts.numpy())
+            with self.host.lock:
+                recycled = self.host.slot_gens[self.slot] != self.slot_gen
+                counts = None if recycled else self.host_counts.numpy().copy()
+            if recycled:
+                # the pinned slot holds a later frame's counters now; the device's are still this
+                # frame's (its workspace has not been taken, checked above)
+                counts = self.counts.cpu().numpy()
+            n_cand, n_kp, n_out = (int(v) for v in counts)
             if max(n_cand, n_kp) > self.max_keypoints:
                 raise _lib.PanoError(f"sift: {max(n_cand, n_kp)} keypoints exceed max_keypoints")
             # the keypoints on a stream of their own: a copy on the compute stream would queue
@@ -297,7 +316,15 @@ class SiftDetection:
                     pinned[:n_out * 32].copy_(self.kpts[:n_out * 32], non_blocking=True)
                 self.host.side.synchronize()
                 kps = pinned[:n_out * 32].numpy().view(KP_DTYPE).copy()
-            self._out = (kps, self.desc[:n_out])
+            desc = self.desc[:n_out]
+            if self.owned:
+                desc = desc.clone()
+                # a later frame queued on the detection's stream must not take the workspace
+                # before the copy has read it
+                cur = torch.cuda.current_stream(desc.device)
+                if cur != self.stream:
+                    self.stream.wait_stream(cur)
+            self._out = (kps, desc)
             self.keep = None
         return self._out
 
@@ -309,12 +336,16 @@ class SiftPipeline:
     ONE HIP graph).  A graph holds addresses, so every buffer of a frame - the pyramid, the
     keypoint lists, the descriptors - lives in one of ``depth`` workspaces used in turn: what
     ``pyramid()`` / ``detect()`` hand back stays valid until ``depth`` more frames have been queued
-    on this pipeline (take a detection's ``result()`` before that)."""
+    on this pipeline.  A detection's ``result()`` taken later raises ``PanoError``; the
+    descriptors it returned earlier are a view into the workspace and are overwritten then (the
+    keypoints are a host copy and stay).  ``owned``: ``result()`` returns a copy of the
+    descriptors, the caller's to keep (the engine's own pipelines behind ``sift_detect_async``)."""
 
     def __init__(self, eng, h, w, depth=3, max_keypoints=1 << 18, n_octaves=None,
-                 sigma=SIFT_SIGMA, layers=SIFT_LAYERS):
+                 sigma=SIFT_SIGMA, layers=SIFT_LAYERS, owned=False):
         import torch
         self.eng, self.h, self.w, self.depth = eng, int(h), int(w), max(int(depth), 1)
+        self.owned = bool(owned)
         self.max_keypoints, self.layers, self.sigma = int(max_keypoints), layers, sigma
         if n_octaves is None:
             n_octaves = sift_octaves(self.h, self.w)
@@ -376,6 +407,7 @@ class SiftPipeline:
         a.counts, a.sort_work, a.desc = (ws["counts"].data_ptr(), ws["sort"].data_ptr(),
                                          ws["desc"].data_ptr())
         ws["args"] = a
+        ws["gen"] = 0                       # frames queued in this workspace
         self.slots.append(ws)
         return ws
 
@@ -383,6 +415,7 @@ class SiftPipeline:
         if tuple(frame.shape) != (self.h, self.w, 3) or not frame.is_contiguous():
             raise ValueError(f"SiftPipeline of {self.h} x {self.w} frames got {tuple(frame.shape)}")
         ws = self._slot()
+        ws["gen"] += 1                      # what a detection from this workspace held is gone
         a = ws["args"]
         a.frame, a.detect = frame.data_ptr(), 1 if detect else 0
         _lib.check(self.eng.lib.pano_sift_detect(self.eng.ctx(), C.byref(a)), "pano_sift_detect")
@@ -402,7 +435,8 @@ class SiftPipeline:
     def detect(self, frame):
         """A queued ``detectAndCompute``: ``SiftDetection`` (``result()`` waits)."""
         ws = self._queue(frame, True)
-        det = SiftDetection(ws["counts"], ws["cands"], ws["desc"], self.max_keypoints, (ws,), self.eng)
+        det = SiftDetection(ws["counts"], ws["cands"], ws["desc"], self.max_keypoints, (ws,), self.eng,
+                            ring=(ws, ws["gen"]), owned=self.owned)
         det.pyramid = (ws["gauss"], ws["dog"])
         return det
 
@@ -416,7 +450,7 @@ def _pipeline_for(eng, h, w, max_keypoints):
     if key not in kept:
         if len(kept) >= 2:
             kept.pop(next(iter(kept)))
-        kept[key] = SiftPipeline(eng, h, w, depth=3, max_keypoints=max_keypoints)
+        kept[key] = SiftPipeline(eng, h, w, depth=3, max_keypoints=max_keypoints, owned=True)
     return kept[key]
 
 
@@ -430,8 +464,10 @@ def sift_detect_async(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
     eng = eng or _eng.engine()
     lib = eng.lib
     if pyramid is None:
-        # the whole frame in one native call (a HIP graph from the second frame of a workspace on);
-        # the result lives in the engine's pipeline of this frame size: valid for three frames
+        # the whole frame in one native call (a HIP graph from the second frame of a workspace on)
+        # on the engine's pipeline of this frame size: take the result() before three more frames of
+        # this size are queued on the engine (it raises after); the descriptors it returns are a
+        # copy, the caller's to keep
         h, w = (int(v) for v in frame.shape[:2])
         return _pipeline_for(eng, h, w, max_keypoints).detect(frame.contiguous())
     gauss, dog = pyramid

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import SCENES, load_golden, n_patches, scene_inputs
+from sift_reference import assert_same_detection
 
 pytestmark = pytest.mark.gpu
 
@@ -1287,13 +1288,7 @@ def test_sift_pipeline_graph_replay_equals_launch_by_launch(eng):
         gauss, dog = det.pyramid
         assert all(torch.equal(a, b) for a, b in zip(gauss, g_ref))
         assert all(torch.equal(a, b) for a, b in zip(dog, d_ref))
-        assert len(kps) == len(kps_ref)
-        for key in ("x", "y", "size", "response", "octave", "r", "c"):
-            assert np.array_equal(kps[key], kps_ref[key]), key
-        dang = np.abs(kps["angle"] - kps_ref["angle"])
-        assert np.minimum(dang, 360 - dang).max() <= 0.01
-        diff = np.abs(desc.cpu().numpy() - desc_ref)
-        assert diff.max() <= 2 and (diff > 0).mean() < 0.02
+        assert_same_detection(kps, desc, kps_ref, desc_ref)
 
     use = engine.Engine(eng.device)
     stream = torch.cuda.Stream(eng.device)
