@@ -707,6 +707,68 @@ int pano_hom_ransac(pano_ctx *ctx, const float *pts, const int32_t *offsets, con
                     int n_pairs, int max_iters, float thresh, uint64_t seed, void *work,
                     double *hom, uint8_t *mask, int32_t *n_inliers, int32_t *hyp_inliers);
 
+/* Bundle adjustment: the per-match work of the Levenberg-Marquardt loop  bundle_adj.py:311-345
+ * All arithmetic is f64; the host derives every 3 x 3 table (in NumPy, in the reference's
+ * operation order) and uploads it once per iteration, the device forms only sums of products.
+ *   rows    dev double [m][4]: (x_b, y_b, x_a, y_a) per match, the homogeneous 1s implicit; the
+ *           columns 0..1 and 3..4 of the reference's match rows (stitcher.py:372-386)
+ *   pairs   dev int32 [n_pairs][4]: (a, b, first, count), the reference's match tuple
+ *           (a, b, rows) of IncrementalBundleAdjuster.matches (:306) in its order; the pair's
+ *           rows are rows[first .. first + count).  Camera b is the reference's `i` / "from",
+ *           camera a its `j` / "to" in _jacobian_symbolic (:199-205).
+ *   hom     dev double [n_pairs][9], row-major: H = K_b R_b R_a^T K_a^-1 (_hom_to_from, :36-38)
+ * A matrix times p = (x_a, y_a, 1) is (m0 x_a + m1 y_a) + m2 per row, a matrix times a vector
+ * v is (m0 v0 + m1 v1) + m2 v2, with one rounding per operation (no contraction).
+ *
+ * pano_ba_residuals: ssq[p] (dev double [n_pairs]) = the pair's sum over its matches of
+ *   rx^2 + ry^2, rx = x_b - X / Z, ry = y_b - Y / Z, (X, Y, Z) = H p - get_diff (:145-149)
+ *   summed per pair.  loss (:158-160) and the gate of `add` (:304) follow on the host.
+ *   Summation: lane t of a block of 256 takes the pair's matches t, t + 256, ... in order; the
+ *   64 lanes of a wave by an xor butterfly (offsets 32, 16, .. 1), the four waves in order.
+ *
+ * pano_ba_normal: the damped system (J^T J + lambda I) delta = J^T r of one iteration
+ *   (:322-327) over the active cameras.  slot: dev int32 [n_cameras], the parameter block of
+ *   each camera (-1: inactive; every camera of a pair is active); the parameters are the active
+ *   cameras in ascending index, 6 each in camera_to_params's order (:138-142): f, ppx, ppy,
+ *   then the three exponential-map angles.  J is _jacobian_symbolic as written (:186-258), NOT
+ *   the derivative of the residual.  jtab: dev double [n_pairs][90], ten row-major 3 x 3
+ *   matrices per pair, all at the state J is taken at:
+ *     [0]     H                                   (:203)
+ *     [1]     S_b = (R_b R_a^T) K_a^-1            (:219)
+ *     [2]     S_r = R_a^T K_a^-1                  (:227)
+ *     [3]     K_a^-1                              (:233)
+ *     [4..6]  N_k = K_b dR_b[k]                   (:228-230, dR = dr_dvi, :163-177)
+ *     [7..9]  Q_k = (K_b R_b) dR_a[k]^T           (:240-243)
+ *   Per match: (X, Y, Z) = H p, iz = 1 / Z, d = (X iz iz, Y iz iz, -iz) (:208-210) and a column
+ *   of J from w = (w0, w1, w2) is (w0 d2 + w2 d0, w1 d2 + w2 d1) (:212-215).  Columns 0..5 are
+ *   camera b's: s = S_b p gives w = (s0, s1, 0), (s2, 0, 0), (0, s2, 0) for f, ppx, ppy (the dK
+ *   products of :222-224 written out), N_k (S_r p) for the angles; columns 6..11 camera a's:
+ *   n = -(K_a^-1 p) gives w_r = (H_r0 n0 + H_r1 n1) + 0 n2, (0 n0 + 0 n1) + H_r0 n2 and
+ *   (0 n0 + 0 n1) + H_r1 n2 (H dK, :236-238), Q_k (K_a^-1 p) for the angles.
+ *   TWO STATES.  r is the residual at hom_r (dev double [n_pairs][9], H at the state r is
+ *   taken at), J at the state of jtab.  The reference takes J at its accepted cameras but r is
+ *   `errs`, the residual of the last CANDIDATE (:314, :335): after a rejected step J^T r pairs J
+ *   at the accepted state with r at the rejected one, and the caller reproduces that by passing
+ *   the rejected candidate's H here.
+ *   Summation.  ba_pair_kernel, one block per pair: per chunk of 256 matches the 90 products
+ *   of each lane are summed over the wave (the butterfly above) and lane 0 adds each sum to its
+ *   wave's running total, chunk by chunk; the four waves' totals are added in order into
+ *   work[p][90]: [0..20] J_b^T J_b and [21..41] J_a^T J_a (upper triangles, row-major),
+ *   [42..77] J_b^T J_a (6 x 6, row-major), [78..89] J^T r (camera b's 6, then camera a's 6).
+ *   ba_assemble_kernel, one block per 6 x 6 block of the system: starting from 0, the pairs are
+ *   added in pair order (the cross block of a pair at (b, a), its transpose at (a, b), :249-256),
+ *   then lambda on the diagonal (:324).  jtj: dev double [6 n_active][6 n_active] row-major,
+ *   every entry written; jtr: dev double [6 n_active].  work: dev, pano_ba_work_bytes(n_pairs).
+ * Both calls queue kernels on the context's stream and nothing else (no allocation, no wait, no
+ * host copy).  No atomics: the same input gives the same bits on every run.  The caller keeps
+ * first + count within rows and every camera index within slot. */
+size_t pano_ba_work_bytes(int n_pairs);
+int pano_ba_residuals(pano_ctx *ctx, const double *rows, const int32_t *pairs, int n_pairs,
+                      const double *hom, double *ssq);
+int pano_ba_normal(pano_ctx *ctx, const double *rows, const int32_t *pairs, int n_pairs,
+                   const int32_t *slot, int n_active, const double *jtab, const double *hom_r,
+                   double lambda, void *work, double *jtj, double *jtr);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

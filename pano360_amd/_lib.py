@@ -170,6 +170,9 @@ _SIGNATURES = {
     "pano_hom_ransac": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_float, C.c_uint64, _vp, _vp, _vp, _vp,
                              _vp]),
     "pano_match_pack": (_i, [_vp, _vp, _vp, _i, C.c_double, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pano_ba_work_bytes": (C.c_size_t, [_i]),
+    "pano_ba_residuals": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "pano_ba_normal": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -264,7 +264,8 @@ static const char *const g_kernel_names[PK_COUNT] = {
     "block_owner_kernel", "tile_flags_kernel", "overlap_stats_kernel",
     "blur_mfma_kernel", "sift_extrema_kernel", "sift_orient_kernel", "sift_describe_kernel",
     "compose_interior_kernel", "scale_step_kernel", "knn2_kernel", "blur_lean_kernel", "blur_lean5_kernel",
-    "ransac_score_kernel", "ransac_finish_kernel", "match_pack_kernel"};
+    "ransac_score_kernel", "ransac_finish_kernel", "match_pack_kernel",
+    "ba_residual_kernel", "ba_pair_kernel", "ba_assemble_kernel"};
 
 void pano_timing_edge(pano_ctx *ctx, int kid, hipStream_t stream, bool begin) {
     hipEvent_t ev;

@@ -70,6 +70,9 @@ enum PanoKernelId {
     PK_RANSAC_SCORE,
     PK_RANSAC_FINISH,
     PK_MATCH_PACK,
+    PK_BA_RESIDUAL,
+    PK_BA_PAIRS,
+    PK_BA_ASSEMBLE,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------

@@ -10,9 +10,11 @@ reference: ``stitch``, ``no_blend`` / ``linear_blend`` /
 Per-pixel work goes to hand-written HIP kernels through ``_lib`` (ctypes over
 ``libpano360_hip.so``); there is no CPU fallback for it.
 
-Out of scope here: feature matching and bundle adjustment - the
-CLI therefore needs the ``ba_<name>.pkl`` camera cache the reference CLI writes
-(stitcher.py:430-439).
+With ``--register`` and no ``ba_<name>.pkl`` the CLI runs the whole chain as the reference's
+does (stitcher.py:423-439): feature matching (``features.matching``, cached in
+``matches_<name>.npz``), bundle adjustment (``bundle_adj.traverse`` over ``idx_to_keypoints``,
+cached in ``ba_<name>.pkl``), then the stitch.  Without the flag a missing camera cache still
+ends the run before any image is read.
 """
 import argparse
 import logging
@@ -291,6 +293,45 @@ def ingest(path, shrink):
     return _blend.shrink_images([read(f) for f in files], shrink)
 
 
+def idx_to_keypoints(matches, kpts):
+    """The match file's keypoint indices replaced by homogeneous coordinates
+    (stitcher.py:372-386): ``matches`` the 0-d object array of ``matches_<name>.npz`` ([i][j] =
+    (int [M][2] (index in i, index in j), homography i -> j)), ``kpts`` the keypoint arrays.
+    Returns {i: {j: (float64 [M][6] (x_i, y_i, 1, x_j, y_j, 1), homography, M)}}, what
+    ``bundle_adj.traverse`` takes."""
+    hom_kpts = [np.concatenate([kp, np.ones((kp.shape[0], 1))], axis=1) for kp in kpts]
+    table = matches.item() if isinstance(matches, np.ndarray) else matches
+    return {i: {j: (np.concatenate([hom_kpts[i][m[:, 0]], hom_kpts[j][m[:, 1]]], axis=1), h,
+                    len(m))
+                for j, (m, h) in row.items()}
+            for i, row in table.items()}
+
+
+def _register(path, name, frames, badjust):
+    """Cameras for the frames of ``path`` (stitcher.py:423-439): the match file is read if
+    present, else ``features.matching`` runs on the device frames and writes it; then
+    ``traverse``, whose cameras are pickled with host uint8 BGR images so that the reference
+    CLI reads the cache too.  Returns the cameras with the device frames attached."""
+    from . import features
+    try:
+        arr = np.load(f"matches_{name}.npz", allow_pickle=True)
+        kpts, matches = arr["kpts"], arr["matches"]
+    except IOError:
+        kpts, matches = features.matching(frames)
+        np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
+    start = time.time()
+    regions = _ba.traverse(list(frames), idx_to_keypoints(matches, kpts), badjust=badjust)
+    logging.info(f"Image registration, time: {time.time() - start}")
+    device = [reg.img for reg in regions]
+    for reg, frame in zip(regions, device):
+        reg.img = frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)
+    with open(f"ba_{name}.pkl", "wb") as fid:
+        pickle.dump(regions, fid, protocol=pickle.HIGHEST_PROTOCOL)
+    for reg, frame in zip(regions, device):
+        reg.img = frame
+    return regions
+
+
 def main(argv=None):
     """Same command line as the reference (stitcher.py:390-451)."""
     parser = argparse.ArgumentParser(description="Stitch images.")
@@ -305,6 +346,9 @@ def main(argv=None):
     parser.add_argument("--blend", "-b", default="multiband", choices=list(BLENDERS.keys()),
                         help="blending algorithm.")
     parser.add_argument("-o", "--out", type=str, help="save result to this file")
+    parser.add_argument("--register", action="store_true",
+                        help="without a camera cache, match the images and run bundle "
+                             "adjustment (writes matches_<name>.npz and ba_<name>.pkl)")
     args = parser.parse_args(argv)
 
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
@@ -318,15 +362,19 @@ def main(argv=None):
     # read, shrink.  The reference does this before it looks at its caches and, with a
     # ``ba_*.pkl`` present, never uses the result (the pickle carries the shrunk images); here
     # the images are read only when something consumes them: a cache without pixels
-    # (``img=None`` records: cameras only, a few hundred bytes per frame) or no cache at all.
+    # (``img=None`` records: cameras only, a few hundred bytes per frame) or, with --register,
+    # no cache at all: then the frames are matched and registered and go to the stitch as
+    # they are.
     # Decoding is Pillow's, on the host; the resize runs on the device (``pano_resize_u8``)
     # and the shrunk frames stay there for ``stitch``.
-    if regions is None:
+    if regions is None and not args.register:
         # (before anything is decoded or uploaded)
         raise SystemExit(
-            f"{cache} not found: feature matching and bundle adjustment are outside this "
-            "build's scope; produce the camera cache with the reference (it is the pickle "
-            "written at stitcher.py:438-439) and re-run")
+            f"{cache} not found: run with --register to match the images and adjust the "
+            "cameras here (the reference CLI's registration), or produce the camera cache with "
+            "the reference (the pickle written at stitcher.py:438-439) and re-run")
+    if regions is None:
+        regions = _register(args.path, name, ingest(args.path, args.shrink), args.ba)
     if any(reg.img is None for reg in regions):
         frames = ingest(args.path, args.shrink) if os.path.isdir(args.path) else []
         if len(frames) != len(regions):
