@@ -769,6 +769,87 @@ int pano_ba_normal(pano_ctx *ctx, const double *rows, const int32_t *pairs, int 
                    const int32_t *slot, int n_active, const double *jtab, const double *hom_r,
                    double lambda, void *work, double *jtj, double *jtr);
 
+/* Baseline JPEG decode of a batch                               stitcher.py:415-421 (cv2.imread)
+ * Frames equal to libjpeg-turbo's default decompression as Pillow runs it, bit for bit, after
+ * ImageOps.exif_transpose and convert("RGB"), written as uint8 BGR [h][w][3].  Scope: SOF0 /
+ * SOF1, 8-bit, Huffman, one interleaved scan, 1 component or 3 in YCbCr with the luma sampled
+ * 1x1, 2x1 or 2x2 and both chroma 1x1 (4:4:4, 4:2:2, 4:2:0), restart markers or none, any size,
+ * EXIF orientation 1..8, quantisers <= 255.  The IDCT runs in int32: bit-exact while the
+ * dequantised coefficients stay within 16 bits, which every encoder's output from 8-bit samples
+ * does (libjpeg-turbo's own C and SIMD IDCTs disagree beyond that).  Limits: entropy data of an
+ * image < 2^28 bytes, packed_bytes < 2^31 (pano360_amd/jpeg.py splits larger sets).  The host (pano360_amd/jpeg.py) parses the markers and lays the batch
+ * out; this call does everything after that.
+ *   desc     host int64 [n + 1][PANO_JPEG_FIELDS]: n image rows (PANO_JD_*), then the batch row
+ *            (PANO_JB_*).  The same table is the head of `packed` (the device reads it there).
+ *   packed   dev uint8 [packed_bytes]: desc, then per image its tables at PANO_JD_TAB_OFF (4 DC
+ *            and 4 AC Huffman lookups of PANO_JPEG_HUFF_BYTES: fast[512] uint16 = length << 8 |
+ *            symbol of every 9-bit prefix holding a code of <= 9 bits, else 0; maxcode[18] int32
+ *            (-1: no code of that length); valoff[18] int32 = index of the length's first symbol
+ *            minus its first code; vals[256] uint8; then 4 quantisation tables uint16 [64] in
+ *            natural order) and its entropy-coded bytes (between SOS and EOI) at PANO_JD_DATA_OFF
+ *   work     dev scratch of desc's PANO_JB_WORK_BYTES, laid out by desc (destuffed bytes,
+ *            planes, and the PANO_JB_W_* arrays); out: dev uint8, frame i at PANO_JD_OUT_OFF.
+ * Stages, each a kernel on the context's stream:
+ *   1. destuff: per chunk of PANO_JPEG_CHUNK raw bytes the bytes kept and RSTn markers met
+ *      (FF 00 -> FF; FF Dn and fill FFs dropped), an exclusive scan over all chunks, then the
+ *      kept bytes written and every restart interval's first byte recorded.
+ *   2. Huffman, self-synchronising (Weissenberger & Schmidt, ICPP 2018): each interval is cut in
+ *      subsequences of PANO_JPEG_SUBSEQ bits.  The first of an interval starts in the known state
+ *      (bit 0, block 0 of the MCU, coefficient 0); the others start at their first bit in that
+ *      state as a guess.  Each decodes to the first codeword boundary at or past its end and
+ *      records the state there (bit, block in MCU, coefficient, blocks completed).  Then, one
+ *      launch per round, every subsequence whose predecessor's exit changed decodes again from
+ *      that exit; the host reads one flag per round and stops when no exit changed (round r
+ *      makes the first r + 1 subsequences of every interval exact, so it ends).  A scan of the
+ *      completed-block counts places each subsequence's blocks; a last pass writes the
+ *      coefficients (int16 [64], natural order, the DC as a difference).  Reads beyond an
+ *      interval's end see zero bits; blocks past an interval's MCU count are dropped.
+ *   3. DC prediction: per interval and component, a prefix sum of the differences in MCU order.
+ *   4. Dequantise and ISLOW IDCT (CONST_BITS 13, PASS1_BITS 2), 8 lanes per block; the output
+ *      through libjpeg's range-limit table: clamp(wrap10(v) + 128, 0, 255) with wrap10 the
+ *      10-bit two's-complement wrap of the descaled value.
+ *   5. Pixels: per output pixel, the EXIF orientation folded into the indexing; fancy
+ *      upsampling of the chroma (the triangle filter, replicated edges; a plane of <= 2 samples
+ *      across is replicated instead) and YCbCr -> RGB in libjpeg's 16-bit fixed point.
+ * Every result has one writer and the scans run in a fixed order: the same input gives the same
+ * bits on every run.  The call waits on the stream once per synchronisation round (it is not
+ * capturable).  The host row fields are checked against the buffer sizes before anything is
+ * queued; a malformed entropy stream gives wrong pixels, never a read or write outside them. */
+#define PANO_JPEG_FIELDS 32
+#define PANO_JPEG_CHUNK 1024
+#define PANO_JPEG_SUBSEQ 1024
+#define PANO_JPEG_HUFF_BYTES 1424
+enum {  /* image row */
+    PANO_JD_W, PANO_JD_H, PANO_JD_NC, PANO_JD_HMAX, PANO_JD_VMAX, PANO_JD_MCUX, PANO_JD_MCUY,
+    PANO_JD_RI,        /* MCUs per restart interval, 0: none */
+    PANO_JD_NINT,      /* restart intervals */
+    PANO_JD_BPM,       /* blocks per MCU */
+    PANO_JD_ORIENT, PANO_JD_DATA_OFF, PANO_JD_DATA_LEN, PANO_JD_TAB_OFF,
+    PANO_JD_CHUNK0,    /* first chunk, interval, block, pixel of the image */
+    PANO_JD_INT0,
+    PANO_JD_SUB0,      /* running sum of the images' subsequence-slot capacities (entropy bits /
+                          PANO_JPEG_SUBSEQ + intervals + 1): checked, it sizes PANO_JB_SUBS; the
+                          slots themselves are assigned by the scan of the intervals' counts */
+    PANO_JD_BLK0, PANO_JD_PIX0,
+    PANO_JD_DST_OFF,   /* work: destuffed bytes */
+    PANO_JD_PLANE0, PANO_JD_PLANE1, PANO_JD_PLANE2,   /* work: sample planes, whole blocks */
+    PANO_JD_PITCH0, PANO_JD_PITCH1, PANO_JD_PITCH2,
+    PANO_JD_OUT_OFF,
+    PANO_JD_COMP_U,    /* 2 bits per block of the MCU: its component */
+    PANO_JD_SAMP,      /* byte per component: h | v << 4 */
+    PANO_JD_TABSEL     /* byte per component: DC table | AC table << 2 | quant table << 4 */
+};
+enum {  /* batch row */
+    PANO_JB_N, PANO_JB_CHUNKS, PANO_JB_INTS, PANO_JB_SUBS, PANO_JB_BLOCKS, PANO_JB_PIXELS,
+    PANO_JB_OUT_BYTES, PANO_JB_W_KEPT, PANO_JB_W_RST, PANO_JB_W_KEPTX, PANO_JB_W_RSTX,
+    PANO_JB_W_DSTLEN, PANO_JB_W_ISTART, PANO_JB_W_IEND, PANO_JB_W_INSUB, PANO_JB_W_ISUBX,
+    PANO_JB_W_STATE0, PANO_JB_W_STATE1, PANO_JB_W_CNTX, PANO_JB_W_FLAG, PANO_JB_W_COEF,
+    PANO_JB_WORK_BYTES, PANO_JB_PACKED_BYTES
+};
+int pano_jpeg_decode(pano_ctx *ctx, const int64_t *desc, int n, const uint8_t *packed,
+                     int64_t packed_bytes, void *work, int64_t work_bytes, uint8_t *out,
+                     int64_t out_bytes);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -265,7 +265,9 @@ static const char *const g_kernel_names[PK_COUNT] = {
     "blur_mfma_kernel", "sift_extrema_kernel", "sift_orient_kernel", "sift_describe_kernel",
     "compose_interior_kernel", "scale_step_kernel", "knn2_kernel", "blur_lean_kernel", "blur_lean5_kernel",
     "ransac_score_kernel", "ransac_finish_kernel", "match_pack_kernel",
-    "ba_residual_kernel", "ba_pair_kernel", "ba_assemble_kernel"};
+    "ba_residual_kernel", "ba_pair_kernel", "ba_assemble_kernel",
+    "jpeg_destuff_kernel", "jpeg_scan_kernel", "jpeg_intervals_kernel", "jpeg_huff_sync_kernel",
+    "jpeg_huff_write_kernel", "jpeg_dc_kernel", "jpeg_idct_kernel", "jpeg_pixels_kernel"};
 
 void pano_timing_edge(pano_ctx *ctx, int kid, hipStream_t stream, bool begin) {
     hipEvent_t ev;

@@ -73,6 +73,14 @@ enum PanoKernelId {
     PK_BA_RESIDUAL,
     PK_BA_PAIRS,
     PK_BA_ASSEMBLE,
+    PK_JPEG_DESTUFF,
+    PK_JPEG_SCAN,
+    PK_JPEG_INTERVALS,
+    PK_JPEG_HUFF_SYNC,
+    PK_JPEG_HUFF_WRITE,
+    PK_JPEG_DC,
+    PK_JPEG_IDCT,
+    PK_JPEG_PIXELS,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------

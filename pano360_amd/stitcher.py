@@ -272,25 +272,29 @@ def stitch(regions, blender=no_blend, equalize=False, crop=False):
 IMAGE_EXTENSIONS = (".jpg", ".png", ".bmp", ".JPG", ".PNG", ".BMP")     # stitcher.py:411-412
 
 
-def ingest(path, shrink):
+def ingest(path, shrink, decode="device"):
     """The head of the reference's ``main`` (stitcher.py:415-421): every image of the
     directory, in ``os.listdir`` order, as ``cv2.imread`` would return it (uint8 BGR), shrunk by
     ``cv2.resize(im, None, fx=1/shrink, fy=1/shrink)`` when shrink > 1 - on the device.
-    Returns uint8 [h][w][3] device tensors."""
-    from PIL import Image as PilImage
-    from PIL import ImageOps
+    decode="device": baseline JPEGs are decoded on the device in one batch
+    (``jpeg.read_images``), everything else by Pillow; "host": every file by Pillow.  The frames
+    are the same either way.  Returns uint8 [h][w][3] device tensors."""
     from . import blend as _blend
+    from . import jpeg as _jpeg
+    if decode not in ("device", "host"):
+        raise ValueError(f"decode={decode!r}: 'device' or 'host'")
     files = [f for f in os.listdir(path) if any(f.endswith(ext) for ext in IMAGE_EXTENSIONS)]
-
-    def read(name):
+    paths = [os.path.join(path, f) for f in files]
+    if decode == "host":
         # cv2.imread's defaults: the EXIF orientation applied (a phone's rotated JPEG arrives
         # upright, with its shape swapped), 8 bits, three channels: 16-bit images are scaled
         # down to 8 bits and an alpha channel is dropped, as IMREAD_COLOR does
-        im = ImageOps.exif_transpose(PilImage.open(os.path.join(path, name)))
-        if im.mode in ("I;16", "I;16B", "I;16L", "I"):
-            im = PilImage.fromarray((np.asarray(im).astype(np.uint32) >> 8).astype(np.uint8))
-        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[..., ::-1])
-    return _blend.shrink_images([read(f) for f in files], shrink)
+        return _blend.shrink_images([_jpeg._pillow_read(p) for p in paths], shrink)
+    frames, _ = _jpeg.read_images(paths)
+    if shrink > 1:
+        eng = _eng.engine()
+        frames = [_blend.shrink_device(f, shrink, eng) for f in frames]
+    return frames
 
 
 def idx_to_keypoints(matches, kpts):
@@ -365,8 +369,8 @@ def main(argv=None):
     # (``img=None`` records: cameras only, a few hundred bytes per frame) or, with --register,
     # no cache at all: then the frames are matched and registered and go to the stitch as
     # they are.
-    # Decoding is Pillow's, on the host; the resize runs on the device (``pano_resize_u8``)
-    # and the shrunk frames stay there for ``stitch``.
+    # Baseline JPEGs are decoded on the device (``jpeg.read_images``), other files by Pillow;
+    # the resize runs on the device (``pano_resize_u8``) and the frames stay there for ``stitch``.
     if regions is None and not args.register:
         # (before anything is decoded or uploaded)
         raise SystemExit(
