@@ -850,6 +850,52 @@ int pano_jpeg_decode(pano_ctx *ctx, const int64_t *desc, int n, const uint8_t *p
                      int64_t packed_bytes, void *work, int64_t work_bytes, uint8_t *out,
                      int64_t out_bytes);
 
+/* Baseline JPEG encode of one image                              stitcher.py:446-447 (cv2.imwrite)
+ * The entropy-coded segment libjpeg-turbo 3.x writes with its defaults as Pillow runs them
+ * (Image.save(f, "JPEG", quality=, subsampling=)), bit for bit: 8-bit, 3 components YCbCr from
+ * RGB, one interleaved scan, no restart markers, the Annex K Huffman tables.  The host
+ * (pano360_amd/jpeg.py) makes the quantisation tables and the markers around the segment.
+ *   img          dev uint8, pixel (x, y) at img[y * pitch + 3 x], channels R, G, B (flags 0) or
+ *                B, G, R (PANO_JPEG_BGR); pitch >= 3 w, any other value (a cropped view needs no
+ *                copy).  The caller guarantees (h - 1) * pitch + 3 w readable bytes.
+ *   h, w         1 .. PANO_JPEG_MAX_SIDE (libjpeg's JPEG_MAX_DIMENSION)
+ *   subsampling  luma sampling, the chroma 1x1: 0 = 1x1 (4:4:4), 1 = 2x1 (4:2:2), 2 = 2x2 (4:2:0)
+ *   qt           host uint8 [2][64]: luma then chroma quantisers, natural order, 1 .. 255
+ *   work         dev scratch of pano_jpeg_encode_work_bytes(h, w, subsampling) bytes (0: bad
+ *                size).  It starts with the quantised blocks: int16 [blocks][64], zigzag order,
+ *                the DC not differenced, in scan order (MCU by MCU; in an MCU the luma blocks
+ *                row by row, then Cb, then Cr).
+ *   *stream, *stream_bytes   out: the entropy-coded segment (stuffed, padded), in pinned host
+ *                memory the context owns, valid until its next pano_jpeg_encode or its
+ *                destruction.
+ * Stages, each a kernel on the context's stream:
+ *   1. blocks, 8 lanes per block: jccolor.c's 16-bit fixed-point RGB -> YCbCr; the last column
+ *      and row replicated; chroma downsampled h2v1 ((a + b + bias) >> 1, bias 0, 1, ...) or h2v2
+ *      ((a + b + c + d + bias) >> 2, bias 1, 2, ...) over those samples, and below the last
+ *      downsampled h2v2 row that row again; the ISLOW FDCT (CONST_BITS 13, PASS1_BITS 2);
+ *      rounded division by 8 q, the sign applied after.  A block of an MCU beyond its
+ *      component's blocks across or down is jccoefct.c's dummy: AC zero, the DC of the block
+ *      before it.
+ *   2. bit counts, one wave per block: a ballot of the nonzero coefficients gives every lane
+ *      its run; DC difference per component in scan order, run/size codes, ZRL, EOB.
+ *   3. an exclusive scan of the counts into int64 bit offsets (a stream may pass 2^31 bits).
+ *      The call waits for the total.
+ *   4. emission, one wave per block: the block's bits assembled in LDS, MSB first; the words
+ *      wholly inside the block stored, its two boundary words atomicOr'ed into the zeroed
+ *      stream (integer, disjoint bits: order-free); the last byte padded with 1-bits.
+ *   5. stuffing: 0xFF bytes counted per 64-byte chunk, the counts scanned (the call waits for
+ *      the total), every byte written at its shifted place with a 0x00 after each 0xFF.
+ * Then the stuffed bytes are copied to the host and the call waits for that.  Not capturable.
+ * The raw stream and the stuffed stream grow inside the context.  The same input gives the same
+ * bytes on every run.  Sizes, pitch, flags and quantisers are checked before anything is
+ * queued. */
+#define PANO_JPEG_MAX_SIDE 65500
+#define PANO_JPEG_BGR 1
+size_t pano_jpeg_encode_work_bytes(int h, int w, int subsampling);
+int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch, int flags,
+                     int subsampling, const uint8_t *qt, void *work, int64_t work_bytes,
+                     const uint8_t **stream, int64_t *stream_bytes);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -174,6 +174,9 @@ _SIGNATURES = {
     "pano_ba_residuals": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "pano_ba_normal": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "pano_jpeg_decode": (_i, [_vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
+    "pano_jpeg_encode_work_bytes": (C.c_size_t, [_i, _i, _i]),
+    "pano_jpeg_encode": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _vp, _vp, C.c_int64,
+                             C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

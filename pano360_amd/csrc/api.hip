@@ -101,6 +101,9 @@ extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     if (ctx->item_buf) (void)hipFree(ctx->item_buf);
     if (ctx->item_counter) (void)hipFree(ctx->item_counter);
     if (ctx->sift_raw) (void)hipFree(ctx->sift_raw);
+    if (ctx->enc_dev) (void)hipFree(ctx->enc_dev);
+    if (ctx->enc_out) (void)hipFree(ctx->enc_out);
+    if (ctx->enc_host) (void)hipHostFree(ctx->enc_host);
     pano_sift_graphs_free(ctx);
     if (ctx->lay_sum_host) (void)hipHostFree(ctx->lay_sum_host);
     if (ctx->lay_rects_dev) (void)hipFree(ctx->lay_rects_dev);
@@ -267,7 +270,9 @@ static const char *const g_kernel_names[PK_COUNT] = {
     "ransac_score_kernel", "ransac_finish_kernel", "match_pack_kernel",
     "ba_residual_kernel", "ba_pair_kernel", "ba_assemble_kernel",
     "jpeg_destuff_kernel", "jpeg_scan_kernel", "jpeg_intervals_kernel", "jpeg_huff_sync_kernel",
-    "jpeg_huff_write_kernel", "jpeg_dc_kernel", "jpeg_idct_kernel", "jpeg_pixels_kernel"};
+    "jpeg_huff_write_kernel", "jpeg_dc_kernel", "jpeg_idct_kernel", "jpeg_pixels_kernel",
+    "jpeg_enc_blocks_kernel", "jpeg_enc_count_kernel", "jpeg_enc_scan_kernel", "jpeg_enc_emit_kernel",
+    "jpeg_enc_stuff_kernel"};
 
 void pano_timing_edge(pano_ctx *ctx, int kid, hipStream_t stream, bool begin) {
     hipEvent_t ev;

@@ -81,6 +81,11 @@ enum PanoKernelId {
     PK_JPEG_DC,
     PK_JPEG_IDCT,
     PK_JPEG_PIXELS,
+    PK_JPEG_ENC_BLOCKS,
+    PK_JPEG_ENC_COUNT,
+    PK_JPEG_ENC_SCAN,
+    PK_JPEG_ENC_EMIT,
+    PK_JPEG_ENC_STUFF,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------
@@ -162,6 +167,10 @@ struct pano_ctx {
     bool sift_capturing;            // pano_sift_detect is capturing a launch sequence (detect.hip)
     // pano_sift_detect: the captured launch sequences, one per set of buffers (detect.hip)
     std::vector<PanoSiftGraph> sift_graphs;
+    // pano_jpeg_encode (jpeg_enc.hip): the raw stream and its stuffing scan, the stuffed stream,
+    // and its pinned host copy (what the call returns)
+    uint8_t *enc_dev, *enc_out, *enc_host;
+    size_t enc_dev_cap, enc_out_cap, enc_host_cap;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);

@@ -514,3 +514,160 @@ def read_images(paths, eng=None, max_packed=BATCH_PACKED, max_work=BATCH_WORK,
         if r == "pillow":
             frames[i] = torch.from_numpy(_pillow_read(paths[i])).to(eng.device)
     return frames, route
+
+
+# ---- encode (``pano_jpeg_encode``, csrc/jpeg_enc.hip) -----------------------------------------
+# Baseline, 8-bit, YCbCr from RGB, one interleaved scan, no restart markers, the Annex K tables:
+# what Pillow's ``Image.save(f, "JPEG")`` writes (libjpeg-turbo's defaults), byte for byte.
+
+# ITU-T T.81 Annex K.1: the example quantisation tables, natural order
+STD_LUMA_QT = np.array([
+    16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55,
+    14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+    49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99], dtype=np.int32)
+STD_CHROMA_QT = np.full(64, 99, np.int32)
+STD_CHROMA_QT.reshape(8, 8)[:4, :4] = [[17, 18, 24, 47], [18, 21, 26, 66], [24, 26, 56, 99],
+                                       [47, 66, 99, 99]]
+
+# ITU-T T.81 Annex K.3: the example Huffman tables, (BITS, HUFFVAL)
+STD_DC_LUMA = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0], bytes(range(12)))
+STD_DC_CHROMA = ([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0], bytes(range(12)))
+STD_AC_LUMA = ([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D], bytes([
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61,
+    0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1, 0xC1, 0x15, 0x52,
+    0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25,
+    0x26, 0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45,
+    0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64,
+    0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83,
+    0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6,
+    0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3,
+    0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8,
+    0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA]))
+STD_AC_CHROMA = ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77], bytes([
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61,
+    0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1, 0x09, 0x23, 0x33,
+    0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18,
+    0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3A, 0x43, 0x44,
+    0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63,
+    0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A,
+    0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4,
+    0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA,
+    0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7,
+    0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA]))
+# libjpeg's JPEG_MAX_DIMENSION: a larger side goes to Pillow (which then refuses it, as today)
+MAX_ENCODE_SIDE = 65500
+# Pillow's ``subsampling`` values -> luma (h, v) sampling; the chroma is 1x1
+SUBSAMPLING = {-1: (2, 2), 2: (2, 2), 1: (2, 1), 0: (1, 1)}
+# the extensions Pillow saves as JPEG (``Image.registered_extensions()``; ".jif" is not one)
+JPEG_EXTENSIONS = (".jpg", ".jpeg", ".jpe", ".jfif")
+
+
+def quant_tables(quality=75):
+    """libjpeg's ``jpeg_set_quality(quality, force_baseline=TRUE)``: the Annex K tables scaled
+    by ``jpeg_quality_scaling`` and clamped to 1..255; int32 [2][64], natural order."""
+    q = min(max(int(quality), 1), 100)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    out = []
+    for base in (STD_LUMA_QT, STD_CHROMA_QT):
+        out.append(np.clip((base * scale + 50) // 100, 1, 255))
+    return np.stack(out).astype(np.int32)
+
+
+def _segment(marker, body):
+    return bytes([0xFF, marker]) + (len(body) + 2).to_bytes(2, "big") + body
+
+
+def encode_header(width, height, quality=75, subsampling=-1):
+    """Everything before the entropy-coded data, with Pillow's marker sequence of a default
+    save: SOI, APP0 JFIF 1.01 (no units, 1:1), DQT luma, DQT chroma, SOF0, DHT DC0 / AC0 /
+    DC1 / AC1, SOS."""
+    qt = quant_tables(quality)
+    h, v = SUBSAMPLING[subsampling]
+    out = [b"\xff\xd8", _segment(0xE0, b"JFIF\0\x01\x01\x00\x00\x01\x00\x01\x00\x00")]
+    for t in (0, 1):
+        out.append(_segment(0xDB, bytes([t]) + qt[t][ZIGZAG].astype(np.uint8).tobytes()))
+    out.append(_segment(0xC0, bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big")
+                        + bytes([3, 1, h << 4 | v, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    for tc_th, (bits, vals) in ((0x00, STD_DC_LUMA), (0x10, STD_AC_LUMA),
+                                (0x01, STD_DC_CHROMA), (0x11, STD_AC_CHROMA)):
+        out.append(_segment(0xC4, bytes([tc_th] + bits) + vals))
+    out.append(_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return b"".join(out)
+
+
+def encodable(img, quality=75, subsampling=-1):
+    """Whether ``encode_device`` covers the image and the settings (else Pillow does)."""
+    shape = tuple(img.shape)
+    return (str(img.dtype) in ("uint8", "torch.uint8") and len(shape) == 3 and shape[2] == 3
+            and 1 <= shape[0] <= MAX_ENCODE_SIDE and 1 <= shape[1] <= MAX_ENCODE_SIDE
+            and isinstance(quality, (int, np.integer)) and 1 <= quality <= 100
+            and subsampling in SUBSAMPLING)
+
+
+def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_coefs=False):
+    """The JPEG file of a uint8 [h][w][3] image (a device tensor, or a host array that is
+    uploaded), byte for byte what ``Image.fromarray(rgb).save(f, "JPEG", quality=quality,
+    subsampling=subsampling)`` writes.  ``order`` is the channel order of ``img``, "bgr" or
+    "rgb".  Any row pitch works as long as the pixels of a row are contiguous (a crop view of a
+    mosaic needs no copy).  The quantised blocks are coded by ``pano_jpeg_encode`` in one call
+    that waits on the stream twice and downloads the stream; not capturable.  With
+    ``want_coefs`` also returns the quantised blocks (int16 [blocks][64] device tensor, natural
+    order, DC not differenced, MCU order).  Raises ValueError for what ``encodable`` rejects."""
+    import torch
+    from . import _lib
+    from . import engine as _eng
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
+    if not encodable(img, quality, subsampling):
+        raise ValueError(f"{tuple(img.shape)} {img.dtype} at quality {quality}, subsampling "
+                         f"{subsampling}: not a case the device encodes")
+    eng = eng or _eng.engine()
+    dev = torch.device(eng.device)
+    if not isinstance(img, torch.Tensor):
+        img = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+    elif img.device != dev:
+        img = img.to(dev)
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * w:
+        img = img.contiguous()
+    sub = 2 if subsampling == -1 else subsampling
+    lib = eng.lib
+    work_bytes = int(lib.pano_jpeg_encode_work_bytes(h, w, sub))
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+    qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
+    stream, nbytes = C.c_void_p(), C.c_int64()
+    _lib.check(lib.pano_jpeg_encode(
+        eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)),
+        1 if order == "bgr" else 0, sub, qt.ctypes.data_as(C.c_void_p), _eng._ptr(work),
+        C.c_int64(work_bytes), C.byref(stream), C.byref(nbytes)), "pano_jpeg_encode")
+    data = encode_header(w, h, quality, subsampling) + C.string_at(stream.value, nbytes.value) \
+        + b"\xff\xd9"
+    if not want_coefs:
+        return data
+    hm, vm = SUBSAMPLING[subsampling]
+    nblocks = -(-w // (8 * hm)) * -(-h // (8 * vm)) * (hm * vm + 2)
+    zz = work[:128 * nblocks].view(torch.int16).view(nblocks, 64)
+    coefs = torch.empty_like(zz)
+    coefs[:, torch.from_numpy(ZIGZAG.astype(np.int64)).to(dev)] = zz
+    return data, coefs
+
+
+def write(path, img, quality=75, subsampling=-1, order="bgr", eng=None):
+    """Save a uint8 [h][w][3] image (device tensor or host array, ``order`` "bgr" or "rgb") as
+    the JPEG Pillow would write: on the device when ``encodable``, else through Pillow as
+    before.  Returns "device" or "pillow"."""
+    if encodable(img, quality, subsampling):
+        data = encode_device(img, quality, subsampling, order, eng)
+        with open(path, "wb") as fid:
+            fid.write(data)
+        return "device"
+    from PIL import Image as PilImage
+    a = img.cpu().numpy() if hasattr(img, "cpu") else np.asarray(img)
+    if order == "bgr" and a.ndim == 3:
+        a = a[..., ::-1]
+    PilImage.fromarray(np.ascontiguousarray(a)).save(path, "JPEG", quality=quality,
+                                                     subsampling=subsampling)
+    return "pillow"

@@ -224,6 +224,13 @@ def stitch(regions, blender=no_blend, equalize=False, crop=False):
     the reference's bit for bit; multiband is within one uint8 level and 1e-4 relative L2
     (see ``EXACT`` above for the two modes).
     """
+    return _download_cropped(*_stitch_device(regions, blender, equalize, crop))
+
+
+def _stitch_device(regions, blender, equalize, crop):
+    """``stitch`` up to the download: (mosaic, crop rectangle).  The mosaic is the uint8 BGR
+    device tensor of the fused blenders (a host array for any other blender); the rectangle is
+    (y0, x0, h, w) with ``crop``, else None."""
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
     padded = blender == multiband_blend                     # stitcher.py:295
@@ -253,8 +260,7 @@ def stitch(regions, blender=no_blend, equalize=False, crop=False):
         patches, _ = eng.warp_all(frames, plan, luts=luts)
         valid = None
         mosaic = blender(_download_patches(patches), plan.shape)
-    if hasattr(mosaic, "cpu"):
-        mosaic = mosaic.cpu().numpy()
+    rect = None
     if crop:
         logging.debug("Cropping...")
         if valid is None:
@@ -263,6 +269,14 @@ def stitch(regions, blender=no_blend, equalize=False, crop=False):
         rect = eng.crop_rect(valid)
         if rect is None:
             raise UnboundLocalError("local variable 'last' referenced before assignment")
+    return mosaic, rect
+
+
+def _download_cropped(mosaic, rect):
+    """``stitch``'s result: the host mosaic, a view of its crop rectangle when there is one."""
+    if hasattr(mosaic, "cpu"):
+        mosaic = mosaic.cpu().numpy()
+    if rect is not None:
         y0, x0, h, w = rect
         mosaic = mosaic[y0:y0 + h, x0:x0 + w, :]
     return mosaic
@@ -389,13 +403,31 @@ def main(argv=None):
                 reg.img = frame
 
     start = time.time()
-    mosaic = stitch(regions, blender=BLENDERS[args.blend], equalize=args.equalize,
-                    crop=args.crop)
+    dev_mosaic, rect = _stitch_device(regions, BLENDERS[args.blend], args.equalize, args.crop)
+    mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
-        from PIL import Image as PilImage
-        PilImage.fromarray(np.ascontiguousarray(mosaic[..., ::-1])).save(args.out)
+        _save(args.out, dev_mosaic, rect, mosaic)
     return mosaic
+
+
+def _save(path, dev_mosaic, rect, mosaic):
+    """Write the mosaic as Pillow's ``save(path)`` would.  A JPEG of a device mosaic is
+    encoded on the device at Pillow's defaults (``jpeg.encode_device``: the same bytes); every
+    other format, and the host mosaic of a custom blender, goes through Pillow."""
+    from . import jpeg as _jpeg
+    if path.lower().endswith(_jpeg.JPEG_EXTENSIONS) and hasattr(dev_mosaic, "cpu"):
+        view = dev_mosaic
+        if rect is not None:
+            y0, x0, h, w = rect
+            view = dev_mosaic[y0:y0 + h, x0:x0 + w, :]
+        if _jpeg.encodable(view):
+            data = _jpeg.encode_device(view, order="bgr")
+            with open(path, "wb") as fid:
+                fid.write(data)
+            return
+    from PIL import Image as PilImage
+    PilImage.fromarray(np.ascontiguousarray(mosaic[..., ::-1])).save(path)
 
 
 if __name__ == "__main__":
