@@ -14,10 +14,15 @@
 // is built to match).
 //
 // float32 accuracy out of float16 operands: every operand is split into
-// hi = f16(v), lo = f16(v - hi) (22-23 significant bits; inputs and taps are
-// pre-scaled by powers of two so that lo stays a normal number) and a product is
-// three MFMAs, hi*hi + hi*lo + lo*hi, accumulated in float32; the dropped lo*lo
-// term is 2^-22 relative.  Measured against the float32 oracle the blurred
+// hi = f16(v), lo = f16(v - hi) (22-23 significant bits where lo is a normal number)
+// and a product is three MFMAs, hi*hi + hi*lo + lo*hi, accumulated in float32; the
+// dropped lo*lo term is 2^-22 relative.  The power-of-two pre-scales keep lo normal
+// for most inputs but not for every tap: with MB_TAP_SCALE = 256 the lo part of
+// about 40 % of the taps is a float16 subnormal, so a tap is held to 2^-25 / 256
+// absolute (the tail taps to ~2^-17 relative), at most ~2.7e-8 absolute over the
+// two passes of a 117-tap level - under the float32 accumulation's own rounding
+// (tests/multiband_f64.py derives the floor; tests/test_gpu_float64_truth.py measures
+// the blurred planes against a float64 truth).  Measured against the float32 oracle the blurred
 // planes agree to 6.6e-7 absolute (the tests' bound is 1e-6; the float32-product vector-ALU
 // kernels of blur.hip reach 7.7e-7).
 //
