@@ -215,8 +215,7 @@ typedef struct pano_ctx pano_ctx;
 #define PANO_OPT_BLUR_SEG_LEN 6
 #define PANO_OPT_SIFT_GRAPH 7
 #define PANO_OPT_LEVEL_CLASSES 8
-#define PANO_OPT_COMPOSE_COMPACT 9
-#define PANO_OPT_COUNT 10
+#define PANO_OPT_COUNT 9
 #define PANO_BLUR_MFMA 0
 #define PANO_BLUR_VALU 1
 int pano_ctx_create(int device, void *stream, pano_ctx **out);

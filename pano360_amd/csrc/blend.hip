@@ -214,9 +214,7 @@ __device__ __forceinline__ AlphaBound alpha_bound_of(const pano_camera *cam, con
     return out;
 }
 
-#ifndef OWN_ROWS
 #define OWN_ROWS 16
-#endif
 // A workgroup takes OWN_SUB sub-tiles of 64 x OWN_ROWS pixels, one above the other: the camera
 // list is built once for all of them and wave w bounds the listed cameras on sub-tile w, a
 // camera per lane, without a barrier of its own (the set-up of a 64 x 16 tile - list, ranges,
@@ -476,55 +474,10 @@ __global__ __launch_bounds__(256) void ownership_cameras_l1_kernel(
 #define OW_Q 16
 #define OW_CAMS 32          // camera records staged in LDS
 #define OW_QLIST 8          // survivors of a sub-tile that are bounded again per quarter
-#ifndef OW_ILP
 #define OW_ILP 4            // independent pixels per lane in the evaluation
-#endif
 #define OW_EVAL (-3)        // qfill: evaluate the quarter's pixels
 #define OW_NOBODY (-1)      // qfill / tile: no candidate: owner -1, valid 0
 #define OW_UNOWNED (-2)     // tile: a candidate is unmasked but its alpha is 0: owner -1, valid 1
-
-#ifdef OW_STAMP
-// phase timers (timing experiments only, tools/probe_own_stamps.py): thread 0 of every
-// OW_STAMP_STRIDE-th workgroup writes the cycles between consecutive stamps into a row of its own
-// (plain stores: atomics on shared counters, one per stamp and workgroup, made the kernel 4.5 x
-// slower and timed mostly themselves); [14] = 1, [15] = evaluated quarters
-#define OW_STAMP_ROWS 2048
-#define OW_STAMP_STRIDE 4
-__device__ unsigned long long g_ow_stamps[OW_STAMP_ROWS][16];
-#define OW_STAMP_ROW()                                                                       \
-    (((blockIdx.y * gridDim.x + blockIdx.x) % OW_STAMP_STRIDE == 0 &&                        \
-      (blockIdx.y * gridDim.x + blockIdx.x) / OW_STAMP_STRIDE < OW_STAMP_ROWS &&             \
-      threadIdx.x == 0 && threadIdx.y == 0)                                                  \
-         ? (int)((blockIdx.y * gridDim.x + blockIdx.x) / OW_STAMP_STRIDE)                    \
-         : -1)
-#define OW_STAMP_AT(k)                                                      \
-    do {                                                                    \
-        const int row_ = OW_STAMP_ROW();                                    \
-        if (row_ >= 0) {                                                    \
-            const unsigned long long now_ = __builtin_readcyclecounter();   \
-            g_ow_stamps[row_][k] = now_ - ow_last;                          \
-            ow_last = __builtin_readcyclecounter();                         \
-        }                                                                   \
-    } while (0)
-extern "C" int pano_debug_own_stamps(unsigned long long *out, int reset) {
-    // out[16]: the sampled workgroups' rows added up ([14] = how many)
-    if (out) {
-        static unsigned long long host[OW_STAMP_ROWS][16];
-        PANO_HIP(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_ow_stamps), sizeof(host)));
-        for (int k = 0; k < 16; ++k) out[k] = 0;
-        for (int r = 0; r < OW_STAMP_ROWS; ++r)
-            if (host[r][14])
-                for (int k = 0; k < 16; ++k) out[k] += host[r][k];
-    }
-    if (reset) {
-        static unsigned long long zero[OW_STAMP_ROWS][16];
-        PANO_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_ow_stamps), zero, sizeof(zero)));
-    }
-    return PANO_OK;
-}
-#else
-#define OW_STAMP_AT(k) do { } while (0)
-#endif
 
 // The tile is 64 x 128 (eight sub-tiles: one camera list, one staging, one pair of bound passes per
 // workgroup - 9 % faster than 64 x 64 on config 3's 4 000 workgroups, 64 x 256 loses 16 %).  The

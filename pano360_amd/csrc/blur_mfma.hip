@@ -70,9 +70,6 @@ typedef GLOBAL_AS float *gf32;
 typedef const GLOBAL_AS int16_t *gci16;
 typedef const GLOBAL_AS float4u *gcf32x4;
 
-#ifndef MB_SCHED
-#define MB_SCHED 1
-#endif
 #define MB_XT 64                    // output columns per workgroup: two 32-column tiles
 // halfs per band row: 64 + 2 * 48 + 8.  336 B = 84 dwords, and 84 = 4 * 21 with 21 odd: the 16
 // lanes of a ds_read_b128 group (one band row each) start on 16 different multiples of 4
@@ -95,22 +92,6 @@ typedef const GLOBAL_AS float4u *gcf32x4;
 #define MB_NEED_MAX 256             // 32-row tiles of the tallest patch (rows <= 8192)
 #define MB_NEED_LEN (MB_NEED_MAX + 2 * MB_NEED_PAD)
 #define MB_WLEN (PANO_MAX_TAPS + 3)
-
-#ifdef MB_STAMP
-// phase timers (timing experiments only): [wave 0 | wave 4][phase] summed cycles, and counts
-__device__ unsigned long long g_mb_stamps[4][12];
-__device__ unsigned long long g_mb_setup[8];   // blur_lean_kernel: cycles of the set-up phases, and workgroups
-#define STAMP(k)                                                                         \
-    do {                                                                                 \
-        if (stamped) {                                                                   \
-            const unsigned long long now_ = __builtin_readcyclecounter();               \
-            if (lane == 0) atomicAdd(&g_mb_stamps[(wv >> 2) & 1][k], now_ - tlast);      \
-            tlast = __builtin_readcyclecounter();                                        \
-        }                                                                                \
-    } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
 
 struct MbLevels {                       // entries in WORK order: a group = GROUP consecutive entries
     const float *w[PANO_MAX_LEVELS];    // first tap of each level
@@ -245,7 +226,7 @@ __device__ __forceinline__ void mb_colpass(f32x16 (&acc)[2 * ((C + 1) / 2) + 1],
             acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t_hi, m_hi[s], acc[k], 0, 0, 0);
             acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t_lo, m_hi[s], acc[k], 0, 0, 0);
             acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_f16(t_hi, m_lo[s], acc[k], 0, 0, 0);
-            if (MB_SCHED) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 }
@@ -485,24 +466,14 @@ __device__ __forceinline__ void mb_body(const pano_patch &p, const int ch, const
     if (t <= sh.t_hi) fetch(std::integral_constant<int, 0>{}, t);
     if (t1 <= sh.t_hi) fetch(std::integral_constant<int, 1>{}, t1);
     unsigned inf = t <= sh.t_hi ? info_at(t) : 0u;       // flags of band t
-#ifdef MB_STAMP
-    const bool stamped = (wv & 3) == 0 && ch == 0 && (blockIdx.x >> 2) % 7 == 3;
-    unsigned long long tlast = __builtin_readcyclecounter();
-#endif
     auto step = [&](auto slot_c) {
-        STAMP(0);                                        // loop skeleton since the last stamp
         const unsigned inf1 = t1 <= sh.t_hi ? info_at(t1) : 0u;    // one flag word per step
         lds_barrier();                                   // everybody finished reading the band
-        STAMP(1);
         commit(slot_c);
-        STAMP(2);
         lds_barrier();
-        STAMP(3);
         if (live) flush();
-        STAMP(4);
         const int t2 = (inf1 >> 9) & 1u ? t1 + 1 : next_wanted(t1);
         if (t2 <= sh.t_hi) fetch(slot_c, t2);
-        STAMP(5);
         if (t >= my_lo && t <= my_hi && (inf & (DMAX == 1 ? 0x0eu : 0x1fu))) {
             f32x16 mid;
 #pragma unroll
@@ -528,22 +499,15 @@ __device__ __forceinline__ void mb_body(const pano_patch &p, const int ch, const
                 mid = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi[cur], b_lo[cur], mid, 0, 0, 0);
                 if (!alpha)                              // the sharp mask is exact in float16
                     mid = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo[cur], b_hi[cur], mid, 0, 0, 0);
-#if MB_SCHED
                 // next k-step's reads (DS read, mask 0x100) first, then this one's products
                 // (MFMA, mask 0x008)
                 __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-#endif
             }
-            STAMP(6);                                    // row pass
             int u = t % NB;
             if (u < 0) u += NB;
             mb_colpass<C>(acc, mid, s_ty, inf, lane, u, r);
-            STAMP(7);                                    // column pass
         }
-#ifdef MB_STAMP
-        if (stamped && lane == 0) atomicAdd(&g_mb_stamps[(wv >> 2) & 1][11], 1ull);
-#endif
         // bands up to the next wanted one only complete tiles
         const int upto = t1 < my_hi + 1 ? t1 : my_hi + 1;
         if (upto > done_end) done_end = upto;
@@ -757,15 +721,9 @@ __global__ __launch_bounds__(MB_THREADS_OF(GROUP), 4 / GROUP) void blur_mfma_ker
 //    a cleared accumulator (unwanted tiles are skipped by wave-uniform tests, as above);
 //  * exactly one tile per step can finish, and it is stored at the start of the next step
 //    (behind that step's barriers, in front of its fetch): no bookkeeping of finished ranges.
-#ifndef MB_LEAN
-#define MB_LEAN 1
-#endif
-// 1: the lean path keeps TWO band buffers in LDS and one barrier per step: while a wave
+// The lean path keeps TWO band buffers in LDS and one barrier per step: while a wave
 // multiplies band t it stages its share of band t + 1 into the other buffer and fetches band
-// t + 2, in the shadow of its own (and its SIMD partner's) matrix products
-#ifndef ML_OVERLAP
-#define ML_OVERLAP 1
-#endif
+// t + 2, in the shadow of its own (and its SIMD partner's) matrix products.
 
 // Tile o of this wave's column (accumulator `a`) to its plane.
 // ALWAYS sixteen store instructions: with `wanted` false every one of them gets an offset
@@ -827,8 +785,8 @@ __device__ __forceinline__ void ml_store(const f32x16 &a, const int o, const int
 //     top or bottom row takes the masked path, in the prologue;
 //   * the column pass computes every tile within reach, wanted or not (85 % are; an unwanted
 //     tile's accumulator is never stored); a wave that wants nothing of a band runs both
-//     passes all the same (skipping them, -DMS_SKIP_IDLE, put a branch in front of the block
-//     and measured slower; the switch is kept for A/B only);
+//     passes all the same (skipping them put a branch in front of the block, which measured
+//     slower);
 //   * f32 -> (hi, lo) float16 is two instructions per value (v_fma_mixlo/hi_f16: hi =
 //     f16(v s), lo = f16(fma(v, s, -hi)), the same bits as ml_body's (v s) - hi: the
 //     difference is exact in float32), written into packed halves directly;
@@ -921,7 +879,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
     const int X0 = g.gx0 + 32 * tx0, px0 = X0 + 32 * tile;
     const int P = sh.P, CM = sh.CM;
     const int BW = MB_XT + 32 * CM, CPR = BW >> 2, NCH = 32 * CPR;
-    const int my_lo = g.O0 - DMAX, my_hi = g.O1 + DMAX;
 
     f32x16 acc[NB], acc_b[CB ? NB : 1];
     const __amdgpu_buffer_rsrc_t dst = __builtin_amdgcn_make_buffer_rsrc(
@@ -998,16 +955,7 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
     // The loads are inline assembly (the compiler's wait insertion must not see them: with the
     // previous tile's stores pending on the same counter it would wait for vmcnt(0)), issued and
     // consumed inside one step (see ml_body).
-    auto issue = [&](Band &pf, const unsigned (&voff_)[NV]) {
-#ifdef MS_ABL_NOLOAD                                      // timing experiment: no band traffic
-        unsigned none[NV];
-#pragma unroll
-        for (int e = 0; e < NV; ++e) none[e] = SHARP ? 0u : OOB;
-        const unsigned (&voff)[NV] = none;
-        (void)voff_;
-#else
-        const unsigned (&voff)[NV] = voff_;
-#endif
+    auto issue = [&](Band &pf, const unsigned (&voff)[NV]) {
         // (s_nop 4: a scalar operand may have come back from a spill lane by v_readlane just
         // before, and a vector-memory instruction may read a scalar register a vector instruction
         // wrote only five wait states later - the compiler does not look into the statement.
@@ -1188,24 +1136,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
             okv[e] = ok ? p.index : -2;
         }
     };
-#ifdef MB_STAMP
-    // phase timers (timing experiments only): waves 0, 2, 4, 6 of a sample of colour workgroups
-#ifndef MB_STAMP_CH
-#define MB_STAMP_CH 0
-#endif
-    const bool stamped = (wv & 1) == 0 && ch == MB_STAMP_CH && (blockIdx.x >> 2) % 7 == 3;
-    unsigned long long tlast = __builtin_readcyclecounter();
-#define MS_STAMP(k)                                                                      \
-    do {                                                                                 \
-        if (stamped) {                                                                   \
-            const unsigned long long now_ = __builtin_readcyclecounter();               \
-            if (lane == 0) atomicAdd(&g_mb_stamps[wv >> 1][k], now_ - tlast);            \
-            tlast = __builtin_readcyclecounter();                                        \
-        }                                                                                \
-    } while (0)
-#else
-#define MS_STAMP(k) do { } while (0)
-#endif
     int off_cur = __builtin_amdgcn_readfirstlane(0), off_nxt = bstride;
     // What a step finds prepared (by the step before it, in the shadow of its products; by the
     // lines below for the first step): the offsets of the chunks it will fetch - band i + 1's -
@@ -1239,12 +1169,7 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
         off_cur = __builtin_amdgcn_readfirstlane(off_cur);
         off_nxt = __builtin_amdgcn_readfirstlane(off_nxt);
         asm volatile("" : "+s"(off_cur), "+s"(off_nxt));
-        MS_STAMP(0);                // the step's scalar head
-#ifdef MS_ABL_HALF_BARRIERS         // timing experiment (results wrong): a barrier every second step
-        if (!(i & 1))
-#endif
         lds_barrier();              // band i is whole; nobody reads the other buffer any more
-        MS_STAMP(1);                // waiting at the barrier
         // ---- the rare cases the previous step left to this one
         Band pf;
         unsigned nn = 0;                                 // the list word after next (prepare_next)
@@ -1254,7 +1179,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
             if constexpr (CB != 0) ml_store(acc_b[CB ? KP : 0], prev_o, lane, p, dst_b, px0, true);
         }
         // (its sixteen stores stand in front of the block's, whose base is beyond the plane then)
-        const bool work = t >= my_lo && t <= my_hi && inf != 0;                        // uniform
         // ---- the block.  Its order is written out by hand and pinned: the scheduler may not
         // move anything across a sched_barrier(0), so every product is followed by the few
         // vector / memory instructions that are to issue in its shadow (a 32x32x16 product
@@ -1262,14 +1186,7 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
 #define MS_PIN() __builtin_amdgcn_sched_barrier(0)
 // cache policy of the tile stores: 2 = nt (the blurred copies are written once and read by the
 // collapse a kernel later, long after they have left the L2: blur 0.697 -> 0.680 ms)
-#ifndef MS_STORE_AUX
 #define MS_STORE_AUX 2
-#endif
-#ifdef MS_ABL_NOSTORE                                    // timing experiment: every store dropped
-#define MS_STORE_AT OOB
-#else
-#define MS_STORE_AT s_at
-#endif
         auto block = [&](auto work_c) {
             constexpr bool WORK = decltype(work_c)::value;
             constexpr int PR = SHARP ? 2 : 3;            // products per k-step of the row pass
@@ -1281,7 +1198,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
             constexpr int NSTORE = CB ? 32 : 16;         // values of the finished tile(s) per lane
             constexpr int PER_R = (NSTORE + GR_A - 1) / GR_A;   // scaled values per gap of the first row pass
             constexpr int G_COMMIT = GR_A + BLK_A * 3;   // first gap of the first column pass's second half
-            MS_STAMP(2);            // prologue
             issue(pf, voff);
             // the list word after next (wanted at the block's end: its latency is covered)
             const bool more2 = i + 2 < nlist;
@@ -1324,7 +1240,7 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
                 for (int q = 0; q < NSTORE; ++q)
                     if (store_gap(q) == g)
                         __builtin_amdgcn_raw_buffer_store_b32(
-                            __float_as_uint(sc[q]), q < 16 ? dst : dst_b, MS_STORE_AT,
+                            __float_as_uint(sc[q]), q < 16 ? dst : dst_b, s_at,
                             (((q & 15) & 3) + 8 * ((q & 15) >> 2)) * rowstep, MS_STORE_AUX);
             };
             // how many of the tile's stores fill() has issued in the gaps in front of the commit:
@@ -1364,9 +1280,7 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
                     for (int q = 0; q < 16; ++q) mid[q] = 0.0f;
                     // (MS_AHEAD k-steps of operands in flight: 1 = the next k-step's reads in
                     // front of this one's products)
-#ifndef MS_AHEAD
-#define MS_AHEAD 1
-#endif
+                    constexpr int MS_AHEAD = 1;
                     constexpr int NBUF = MS_AHEAD + 1;
                     half8 a_hi[NBUF], a_lo[NBUF], b_hi[NBUF], b_lo[NBUF];
                     auto operands = [&](const int s, const int b) {
@@ -1391,7 +1305,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
                             MS_PIN();
                         }
                     }
-                    if (G0 == 0) MS_STAMP(3);            // (first) row pass
                     // column pass, k-half-major.  Block b = (half, d): two operand reads and three
                     // products; the operands of block b + 1 are read in front of block b's
                     // products; the second half of Mid is split under the first half's products.
@@ -1468,23 +1381,10 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
                 if constexpr (CB != 0)
                     level(std::integral_constant<int, CB>{}, std::integral_constant<int, GR_A + GC_A>{},
                           std::false_type{}, std::true_type{}, acc_b, s_tx_b, s_ty_b);
-                MS_STAMP(4);        // split + column pass (+ the next band's conversion)
             }
             MS_PIN();
-            MS_STAMP(5);
-#ifdef MB_STAMP
-            if (stamped && lane == 0) atomicAdd(&g_mb_stamps[wv >> 1][11], 1ull);
-#endif
         };
-#ifdef MS_SKIP_IDLE
-        if (work)
-            block(std::true_type{});
-        else
-            block(std::false_type{});
-#else
-        (void)work;
         block(std::true_type{});
-#endif
         prev_store = (inf >> (DMAX + 2)) & 1u;           // tile t - DMAX is wanted: complete now
         prev_o = t - DMAX;
         prev_u = U;
@@ -1499,11 +1399,6 @@ __device__ __forceinline__ void ms_body(const pano_patch &p, const int ch, const
         ++i;
         return run_on;
     };
-#ifdef MS_PRIO
-    // (experiment: the second-dispatched half of the workgroup loses every arbitration against
-    // its SIMD partners, MI355X_MICROARCH.md "Two waves per SIMD" item 4)
-    if (wv >= 4) __builtin_amdgcn_s_setprio(MS_PRIO);
-#endif
     while (i < nlist) {                                  // one run per trip
 #pragma unroll
         for (int k = 0; k < NB; ++k)
@@ -1539,17 +1434,6 @@ __device__ __forceinline__ void lean_kernel_body(
     const int2 *__restrict__ items, unsigned char *smem) {
     constexpr int GROUP = 4;
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-#ifdef MB_STAMP
-    unsigned long long ts_last = __builtin_readcyclecounter();
-#define MS_SETUP_STAMP(k)                                                               \
-    do {                                                                                \
-        const unsigned long long now_ = __builtin_readcyclecounter();                   \
-        if (tid == 0) atomicAdd(&g_mb_setup[k], now_ - ts_last);                        \
-        ts_last = now_;                                                                 \
-    } while (0)
-#else
-#define MS_SETUP_STAMP(k) do { } while (0)
-#endif
     // (five levels: ONE group of four wave pairs, the two lightest levels on one pair)
     constexpr bool five = FIVE;
     const int ngroups = five ? 1 : (L.n + GROUP - 1) / GROUP;
@@ -1616,7 +1500,6 @@ __device__ __forceinline__ void lean_kernel_body(
     const int dmaxm = (sh.CM + 1) / 2;
     sh.t_lo = g.O0 - dmaxm;
     sh.t_hi = g.O1 + dmaxm;
-    MS_SETUP_STAMP(0);                                   // item, record, geometry
     for (int which = 0; which < (lv_b >= 0 ? 2 : 1); ++which)
     if (live) {
         const uint4 *from = (const uint4 *)(tables + L.tab_off[which ? level_b : level]);
@@ -1636,7 +1519,6 @@ __device__ __forceinline__ void lean_kernel_body(
             for (int j = 0; j < DEPTH; ++j) to[min(i0 + 128 * j, n16 - 1)] = v[j];
         }
     }
-    MS_SETUP_STAMP(1);                                   // table copy
     const int X0 = g.gx0 + 32 * tx0;
     const int nty = g.O1 - g.O0 + 1;
     if (wv < 2) {
@@ -1650,7 +1532,6 @@ __device__ __forceinline__ void lean_kernel_body(
     }
     int *const s_count = (int *)sh.any;                  // (the `any` flags are not used here)
     __syncthreads();
-    MS_SETUP_STAMP(2);                                   // need flags + barrier (the table copy's LDS writes land)
     // the bands some wave wants, in order, compacted: one wave, 64 bands per round
     if (wv == 0) {
         int count = 0;
@@ -1679,10 +1560,6 @@ __device__ __forceinline__ void lean_kernel_body(
         if (lane == 0) *s_count = count;
     }
     __syncthreads();
-    MS_SETUP_STAMP(3);                                   // list
-#ifdef MB_STAMP
-    if (tid == 0) atomicAdd(&g_mb_setup[7], 1ull);
-#endif
     const int nlist = *s_count;
     const half8 *s_tx = (const half8 *)(smem + my_tx), *s_ty = (const half8 *)(smem + my_ty);
     const int out_level = L.out[level];
@@ -2177,20 +2054,6 @@ static inline int mb_sorted_slots(int cap) { return (cap + MB_SEG_SLOTS + 1) & ~
 // Host side: called by pano_multiband_blur (blur.hip).  taps / ntaps: the caller's
 // padded tables (include/pano360.h); `extra[k]` zeros precede level k's first tap
 // after the PANO_TAP_LEAD ones.
-#ifdef MB_STAMP
-extern "C" int pano_debug_stamps(unsigned long long *out, int reset) {
-    if (out) {
-        PANO_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mb_stamps), sizeof(unsigned long long) * 48));
-        PANO_HIP(hipMemcpyFromSymbol(out + 48, HIP_SYMBOL(g_mb_setup), sizeof(unsigned long long) * 8));
-    }
-    if (reset) {
-        unsigned long long zero[48] = {};
-        PANO_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_mb_stamps), zero, sizeof(zero)));
-        PANO_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_mb_setup), zero, sizeof(unsigned long long) * 8));
-    }
-    return PANO_OK;
-}
-#endif
 
 // The work list of a table of records: tile flags (with an interior map), items, sort.
 // Depends on the records' geometry and the interior map only, not on the warped planes, so
@@ -2372,30 +2235,28 @@ static int launch_levels(pano_ctx *ctx, const pano_patch *table, int n, int max_
     dim3 grid((unsigned)cap * 4 * ngroups, 1, 1);
     // Groups of four levels with real apertures: the kernel that runs the regular items
     // through the lean path (and the others through the general one).
-    int lean = MB_LEAN && ctx->opt[PANO_OPT_BLUR_LEAN] && group == 4 ? 1 : 0;
+    int lean = ctx->opt[PANO_OPT_BLUR_LEAN] && group == 4 ? 1 : 0;
     // five levels in one group (blur_lean_kernel: the two lightest on one wave pair), when their
     // reaches allow: 1 and 2 K-steps (equal DMAX) for the lightest two
     const bool five = lean && cnt == 5 && mb_c_of(L.ntaps[0]) == 1 &&
                       mb_c_of(L.ntaps[1]) == 2;
-    if (cnt > 4 && !five) lean = lean && false;          // (more than one group: the general kernel)
+    if (cnt > 4 && !five) lean = 0;                      // (more than one group: the general kernel)
     for (int i = 0; i < cnt; ++i)
         if (L.ntaps[i] < 3) lean = 0;
-    int lds_lean = lds;
     for (int i = 0; i < cnt; ++i)    // (ms_body stages at most 1280 chunks per band: a reach of 3 K-steps)
         if (mb_c_of(L.ntaps[i]) > 3) lean = 0;
-    if (ML_OVERLAP) {            // + the second band buffer, behind the largest group's tables
-        lds_lean = 0;
-        for (int gidx = 0; gidx < (five ? 1 : ngroups); ++gidx) {
-            int bytes = 0, cm = 1;
-            for (int i = group * gidx; i < cnt && (five || i < group * (gidx + 1)); ++i) {
-                bytes += mb_table_bytes(L.ntaps[i]);
-                cm = mb_c_of(L.ntaps[i]) > cm ? mb_c_of(L.ntaps[i]) : cm;
-            }
-            bytes = (bytes + mb_fixed_bytes(cm) + 15) / 16 * 16 + 2 * 32 * mb_pitch_of(cm) * 2;
-            lds_lean = bytes > lds_lean ? bytes : lds_lean;
+    // the lean kernel's LDS: the tables, then the second band buffer behind the largest group's
+    int lds_lean = 0;
+    for (int gidx = 0; gidx < (five ? 1 : ngroups); ++gidx) {
+        int bytes = 0, cm = 1;
+        for (int i = group * gidx; i < cnt && (five || i < group * (gidx + 1)); ++i) {
+            bytes += mb_table_bytes(L.ntaps[i]);
+            cm = mb_c_of(L.ntaps[i]) > cm ? mb_c_of(L.ntaps[i]) : cm;
         }
-        if (lds_lean > 160 * 1024) lean = 0;             // (apertures above 97 taps: the general kernel)
+        bytes = (bytes + mb_fixed_bytes(cm) + 15) / 16 * 16 + 2 * 32 * mb_pitch_of(cm) * 2;
+        lds_lean = bytes > lds_lean ? bytes : lds_lean;
     }
+    if (lds_lean > 160 * 1024) lean = 0;                 // (apertures above 97 taps: the general kernel)
     if (lean) {
         if (five) {
             grid = dim3((unsigned)cap * 4, 1, 1);        // one group
@@ -2445,17 +2306,11 @@ int pano_launch_blur_mfma(pano_ctx *ctx, const pano_patch *table, int n, int max
             return rc;
     ctx->prepared_table = nullptr;
     const uint8_t *flags = interior ? tile_flags : nullptr;
-#ifndef MB_SPLIT_LAUNCH
-#define MB_SPLIT_LAUNCH 1
-#endif
-#ifndef MB_FIVE_IN_ONE
-#define MB_FIVE_IN_ONE 1
-#endif
     if (narrow && n_blur == 5 && ctx->opt[PANO_OPT_BLUR_LEAN] &&
-        mb_c_of(ntaps[0]) == 1 && mb_c_of(ntaps[1]) == 2 && ntaps[0] >= 3 && MB_FIVE_IN_ONE)
+        mb_c_of(ntaps[0]) == 1 && mb_c_of(ntaps[1]) == 2 && ntaps[0] >= 3)
         // six pyramid levels: all five Gaussian levels in ONE launch (every band staged once)
         return launch_levels(ctx, table, n, max_aw, owner, W, host_taps, ntaps, 0, 5, rmax, 4, flags);
-    if (MB_SPLIT_LAUNCH && narrow && (n_blur == 5 || n_blur == 6)) {
+    if (narrow && (n_blur == 5 || n_blur == 6)) {
         // four levels as one group of four, the rest in a launch of their own (small workgroups,
         // several per CU): the band is staged twice per item instead of three times.  Config 5
         // (five levels): 8.9-9.05 ms against 9.2 ms as 2 + 2 + 1 in one launch.

@@ -1,7 +1,7 @@
 // One instance of the two-level ownership kernel for OW_SUBS sub-tiles (64 x 16) per workgroup:
 // included by blend.hip once per tile height, with OW_FN(name) giving the instance's names.
-// (The common definitions - OW_T, OW_Q, OW_CAMS, OW_QLIST, OW_ILP, the fill codes, the phase timers -
-// stand in blend.hip in front of the first inclusion.)
+// (The common definitions - OW_T, OW_Q, OW_CAMS, OW_QLIST, OW_ILP, the fill codes - stand in
+// blend.hip in front of the first inclusion.)
 #define OW_TH (OW_Q * OW_SUBS)      // the tile is 64 x (16 OW_SUBS) pixels
 #define OW_NQ (4 * OW_SUBS)         // quarters per tile
 
@@ -42,10 +42,8 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
                                          int H, int W, int bx0, int bx1, int by0, int by1,
                                          int listed, int prune, int vt, int16_t *__restrict__ owner,
                                          uint8_t *__restrict__ valid, int32_t *__restrict__ boxes,
-                                         int box_stride, uint8_t *__restrict__ marks,
-                                         unsigned long long ow_last) {
+                                         int box_stride, uint8_t *__restrict__ marks) {
     const int lane = threadIdx.x, wave = threadIdx.y, tid = wave * 64 + lane;
-    (void)ow_last;
     // position in the list -> camera record / camera index (listed < 0: the list overflowed, a
     // "position" is the camera's index and all n cameras are walked)
     auto index_at = [&](int pos) -> int { return listed < 0 ? pos : S.cl.list[pos]; };
@@ -83,7 +81,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             s_hi[sub * NL + k] = hi;
         }
         __syncthreads();
-        OW_STAMP_AT(2);
         for (int sub = wave; sub < OW_SUBS; sub += 4) {
             // survivors of a sub-tile, order preserved: the first maximum wins
             const float L = __int_as_float(S.low1[sub]);
@@ -110,7 +107,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             }
         }
         __syncthreads();
-        OW_STAMP_AT(3);
         // ---- level 2: a sub-tile's survivors on its four 16 x 16 quarters ---------------------------
         int off[OW_SUBS + 1];
         off[0] = 0;
@@ -144,7 +140,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             S.hi2[sub * 4 + q][j] = hi;
         }
         __syncthreads();
-        OW_STAMP_AT(4);
         if (tid < OW_NQ) {
             const int sub = tid >> 2, q = tid & 3, nc = S.ncand[sub];
             const int sy0 = by0 + OW_Q * sub, sy1 = min(sy0 + OW_Q, H);
@@ -172,7 +167,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             S.qfill[tid] = fill;
         }
         __syncthreads();
-        OW_STAMP_AT(5);
     }
     // ---- the quarters that need their pixels evaluated ---------------------------------------------
     if (wave == 0) {
@@ -184,10 +178,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
         if (lane == 0) S.n_eval = __popcll(bal);
     }
     __syncthreads();
-    OW_STAMP_AT(6);
-#ifdef OW_STAMP
-    if (OW_STAMP_ROW() >= 0) g_ow_stamps[OW_STAMP_ROW()][15] = (unsigned long long)S.n_eval;
-#endif
     // an item = 16 columns x 4 OW_ILP rows of a quarter: lane -> column lane & 15, rows
     // (lane >> 4) + 4 j of the item's rows, OW_ILP independent pixels in flight per lane
     constexpr int PER_Q = 4 / OW_ILP;
@@ -260,7 +250,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             S.town[row0 + 4 * j][col] = (short)(who[j] >= 0 ? who[j] : (any[j] ? OW_UNOWNED : OW_NOBODY));
     }
     __syncthreads();
-    OW_STAMP_AT(7);
     // ---- the tile leaves in 16-byte pieces: a lane takes eight pixels of a row, a wave eight rows per
     // store (a row per store - 64 two-byte and 64 one-byte lanes - was 64 stores a wave and, with the
     // run tracking in the same loop, a quarter of the workgroup's life: profiles/r05/own_stamps_*.txt)
@@ -298,7 +287,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
             }
         }
     }
-    OW_STAMP_AT(8);
     if (!marks) return;
     // ---- boxes and column marks: a run of one owner down a column, per 16-row sub-tile; a quarter with
     // one owner (most of them) is one run without a look at its pixels
@@ -359,7 +347,6 @@ __device__ __forceinline__ void OW_FN(own_tile)(OW_FN(OwnShared) &S, int (*__res
         const int *b = s_box[tid];
         if (b[1] >= b[0]) box_merge(boxes + (size_t)box_stride * tid, b[0], b[1], b[2], b[3]);
     }
-    OW_STAMP_AT(9);
 }
 
 __global__ __launch_bounds__(256) void OW_FN(ownership_cameras_kernel)(
@@ -380,11 +367,6 @@ __global__ __launch_bounds__(256) void OW_FN(ownership_cameras_kernel)(
     // (a workgroup's wave w sits on SIMD w: the few threads of the bound passes rotate with the
     // workgroup so that they do not all queue on SIMD 0)
     const int vt = (tid + 64 * (int)((blockIdx.x + blockIdx.y) & 3)) & 255;
-    unsigned long long ow_last = 0;
-#ifdef OW_STAMP
-    ow_last = __builtin_readcyclecounter();
-    if (OW_STAMP_ROW() >= 0) g_ow_stamps[OW_STAMP_ROW()][14] = 1ull;
-#endif
     if (marks && tid < NL) {
         int *b = s_box[tid];
         b[0] = b[2] = 0x7fffffff;
@@ -415,7 +397,6 @@ __global__ __launch_bounds__(256) void OW_FN(ownership_cameras_kernel)(
         for (int r = 0; r < OW_TH / 64; ++r) trow[r] = table_f64(tan_p, min(by0 + 64 * r + lane, by1 - 1));
     }
     const int listed = build_camera_list(S.cl, cams, n, bx0, bx1, by0, by1);
-    OW_STAMP_AT(0);
     const int mode = all_cams ? 2 : (listed >= 0 && listed <= OW_CAMS ? 1 : 0);
     uint32_t *dst = (uint32_t *)S.cam;
     if (all_cams) {
@@ -473,10 +454,9 @@ __global__ __launch_bounds__(256) void OW_FN(ownership_cameras_kernel)(
         if (lane < OW_SUBS) S.low1[lane] = 0, S.ncand[lane] = 0;
     }
     __syncthreads();
-    OW_STAMP_AT(1);
 #define OW_CALL(M)                                                                                  \
     OW_FN(own_tile)<M>(S, s_box, s_hi, s_keep, NL, cams, n, H, W, bx0, bx1, by0, by1, listed, prune, vt,  \
-                owner, valid, boxes, box_stride, marks, ow_last)
+                owner, valid, boxes, box_stride, marks)
     if (mode == 2)
         OW_CALL(2);
     else if (mode == 1)

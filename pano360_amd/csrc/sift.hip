@@ -259,9 +259,7 @@ __global__ __launch_bounds__(256) void sift_extrema_kernel(
 // column), which sift_refine_kernel then works through, one thread per entry.  (One thread
 // per sample with the refinement inside it took 1.58 ms for the DoG planes of a 4K frame, more
 // than building the scale space.)
-#ifndef SIFT_SCAN_WAVES
 #define SIFT_SCAN_WAVES 4096        // a launch's rows are cut until it has this many waves (if it can)
-#endif
 template <int NL>                   // DoG layers of the octave = layers per octave + 2
 __global__ __launch_bounds__(256) void sift_scan_kernel(const float *__restrict__ dog, int rows,
                                                         int cols, float threshold, int seg_rows,
@@ -509,9 +507,7 @@ __global__ __launch_bounds__(64 * SIFT_WAVES) void sift_describe_kernel(
     // SIFT_HCOPIES copies of a wave's histogram, one per group of 64 / SIFT_HCOPIES lanes: the 64
     // samples of a step are neighbours in the window and mostly vote into the same two or three
     // cells - same-address atomics, which the LDS serialises
-#ifndef SIFT_HCOPIES
 #define SIFT_HCOPIES 1                   // (2 or 4 copies against same-address atomics: no faster)
-#endif
     constexpr int HSIZE = CELLS * PAIRS;
     __shared__ unsigned long long s_hist[SIFT_WAVES][SIFT_HCOPIES * HSIZE];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -63,13 +63,12 @@ __global__ __launch_bounds__(256) void warp_spherical_kernel(
 }
 
 // Colour planes of window V of every patch in one launch (blockIdx.z = patch).
-// WARP_ROWS rows per thread (rows y and y + 4 of a 64 x 8 block): the kernel is bound by the
-// latency of its dependent loads (trig tables -> taps -> LUT), not by their number, and at
-// 22 registers the CU already holds all the waves it can; two independent pixels per thread
-// put twice as many loads in flight.  The two share their column's sin / cos.
-#ifndef WARP_ROWS
+// WARP_ROWS rows per thread (rows y, y + 4, y + 8, y + 12 of a 64 x 16 block): the kernel is
+// bound by the latency of its dependent loads (trig tables -> taps -> LUT), not by their number,
+// and at 22 registers the CU already holds all the waves it can; independent pixels per thread
+// put more loads in flight (1 row 0.371 ms, 2 rows 0.301, 4 rows 0.281: profiles/r01/notes.md).
+// They share their column's sin / cos.
 #define WARP_ROWS 4
-#endif
 __global__ __launch_bounds__(256) void warp_windows_kernel(
     const pano_camera *__restrict__ cams, const pano_patch *__restrict__ patches,
     const double *__restrict__ sin_t, const double *__restrict__ cos_t,

@@ -541,14 +541,14 @@ class WindowInfo:
 class FusedPatches:
     """Windows of every patch packed into three arenas (colour planes over V,
     blurred copies over A, row-pass scratch) + the patch table pointing into
-    them.  ``entries`` = [(camera index, patch rect, ``windows_for`` output)], one
-    per owned column span, in camera order."""
+    them, one record per owned column span, in camera order."""
 
     @classmethod
     def from_regions(cls, raw, max_spans, rects, have, radius, strip, n_blur, eng, rec=None):
         """The record table straight from the region search's output: one native call
         lays out rectangles, pitches, arena offsets and tile offsets
-        (``pano_layout_windows``); the arenas are (re)used as in ``__init__``.
+        (``pano_layout_windows``); the arenas are the engine's, grown as needed
+        (``Engine.arena``).
         ``have``: uint8 [n], 0 = that camera's frame is not resident."""
         lib = _lib.lib()
         n = len(rects)
@@ -601,54 +601,6 @@ class FusedPatches:
             self._window = np.stack([i64("vy0"), i64("vy0") + i64("vh"), i64("vx0"),
                                      i64("vx0") + i64("vw")], axis=1)
         return self._area, self._window
-
-    def __init__(self, entries, eng, n_blur):
-        if isinstance(entries, tuple):                   # (index [k], rects [k][4], A [k][4], V [k][4])
-            index, rects, area, window = (np.asarray(v, np.int64) for v in entries)
-        else:
-            index = np.array([e[0] for e in entries], np.int64)
-            rects = np.array([e[1] for e in entries], np.int64).reshape(-1, 4)
-            area = np.array([e[2][0] for e in entries], np.int64).reshape(-1, 4)
-            window = np.array([e[2][1] for e in entries], np.int64).reshape(-1, 4)
-        n = len(index)
-        rec = np.zeros(n, dtype=PATCH_DTYPE)
-        self._area, self._window = area, window
-        rec["y0"], rec["x0"] = rects[:, 0], rects[:, 2]
-        rec["h"], rec["w"] = rects[:, 1] - rects[:, 0], rects[:, 3] - rects[:, 2]
-        rec["index"] = index
-        rec["vy0"], rec["vx0"] = window[:, 0], window[:, 2]
-        rec["vh"], rec["vw"] = window[:, 1] - window[:, 0], window[:, 3] - window[:, 2]
-        rec["ay0"], rec["ax0"] = area[:, 0], area[:, 2]
-        rec["ah"], rec["aw"] = area[:, 1] - area[:, 0], area[:, 3] - area[:, 2]
-        rec["vpitch"] = (rec["vw"] + 3) & ~3
-        vh, ah = rec["vh"].astype(np.int64), rec["ah"].astype(np.int64)
-        planes_sz = 3 * vh * rec["vpitch"]
-        lead = np.zeros(n, np.int64)
-        if eng.tile_grid == 32:
-            # the matrix-core blur writes 32-column tile rows anchored at multiples of 32 in
-            # patch coordinates: 128-byte rows, and the anchor column on a 128-byte boundary,
-            # make each such row one cache line instead of two; no row-pass scratch
-            rec["apitch"] = (rec["aw"] + 31) & ~31
-            lead = rec["ax0"].astype(np.int64) & 31
-            blurred_sz = n_blur * 4 * ah * rec["apitch"] + 32
-            scratch_sz = np.zeros(n, np.int64)
-        else:
-            rec["apitch"] = (rec["aw"] + 3) & ~3
-            blurred_sz = n_blur * 4 * ah * rec["apitch"]
-            scratch_sz = n_blur * 4 * vh * rec["apitch"]
-        self.planes = eng.arena("planes", int(planes_sz.sum()))
-        self.blurred = eng.arena("blurred", int(blurred_sz.sum()) + 32)
-        self.scratch = eng.arena("scratch", int(scratch_sz.sum()))
-        for key, sizes, arena in (("planes", planes_sz, self.planes),
-                                  ("blurred", blurred_sz, self.blurred),
-                                  ("scratch", scratch_sz, self.scratch)):
-            offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-            base = arena.data_ptr()
-            if key == "blurred":
-                base += -base % 128                         # arenas come 512-byte aligned anyway
-                offs = offs + lead
-            rec[key] = base + 4 * offs
-        self.table = PatchTable(rec, eng)
 
     @property
     def info(self):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A second build of the library with extra compiler flags, for A/B timing through PANO_LIB:
-#   tools/build_variant.sh NAME "-DMB_SOMETHING=1 ..."   ->  build/variants/NAME/libpano360_hip.so
+#   tools/build_variant.sh NAME "-DPANO_INTERIOR_BLOCK=8 ..."   ->  build/variants/NAME/libpano360_hip.so
 # (build/ is git-ignored but travels to the GPU box with the snapshot)
 set -eu
 cd "$(dirname "$0")/.."
