@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: blended megapixels/s of warp + multiband blend.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg5|cfg4]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg5|cfg4] [--full]
 
 One "step" = one full stitch of the workload: uint8 frames + cameras resident
 in HBM -> uint8 mosaic in HBM (the boundary of the reference's own timer,
@@ -21,15 +21,20 @@ strips; ``--exchange reduce``: one sum-reduce of zero-padded full-width mosaics)
 the exchange of stitch k overlapping the kernels of stitch k + 1.  Strong
 scaling: total work is fixed as N grows.  The same launch then also times the
 other exchange and N independent image sets (replicas, no collective) and
-reports them as secondary fields.
+reports them as secondary fields (``--full``).
 
 ``--workload cfg4``: the Gaussian / DoG scale space (features.py:192-201) of 4K
 frames, one frame per step, with its own metric (input megapixels/s).
 
-Prints ONE JSON line on rank 0, under 4 KB: the headline (metric, value, ms_per_step, settings,
-roofline, cpu_baseline).  Everything else - per-kernel times, the other BASELINE configs, the
-scaling projection, the prose - goes to the side file the line names (`side_file`, under
-gpurun_out/): the driver keeps a few KB of stdout and a 28 KB line lost its front there.
+A plain run does what its headline needs and nothing else: it sets up, warms up, times the K
+steps, writes ``--dump-outputs`` if asked, and prints ONE JSON line on rank 0 (metric, value,
+unit, ms_per_step, settings, config).  ``--full`` measures and checks everything else as well:
+the same K steps once more with per-kernel events (kernel_ms_per_step, roofline), one stitch at
+a time, the other BASELINE configs and settings (secondary), the CPU baseline, the untimed busy
+loop, and with N > 1 the replicas and the other exchange.  Its line stays under 4 KB (headline,
+settings, roofline, cpu_baseline); the whole record - per-kernel times, the scaling projection,
+the prose - goes to the side file the line names (`side_file`): a driver keeps a few KB of
+stdout, and a 28 KB line lost its front there.
 
 ``--dump-outputs DIR``: after the timed steps, what the headline's last timed step computed - the
 arrays its caller receives (a stitch: the mosaic and the valid mask; cfg4: the pyramid, and with
@@ -86,10 +91,11 @@ def compact_line(full, side_file=None):
     if "alt_settings" in full:
         out["alt_settings"] = {k: _num(v) for k, v in full["alt_settings"].items()}
     roof = full.get("roofline") or {}
-    out["roofline"] = {k: _num(roof[k]) for k in
-                       ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
-                        "traffic_source", "avg_launch_ms", "launches", "blend_frac",
-                        "blend_frac_tile_count", "weighted_frac") if k in roof}
+    if roof:                                              # (a plain run has none)
+        out["roofline"] = {k: _num(roof[k]) for k in
+                           ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
+                            "traffic_source", "avg_launch_ms", "launches", "blend_frac",
+                            "blend_frac_tile_count", "weighted_frac") if k in roof}
     if isinstance(roof.get("frac_range"), dict):         # [min, max, processes]: the side file says where from
         fr = roof["frac_range"]
         out["roofline"]["frac_range"] = [_num(fr["min"], 4), _num(fr["max"], 4), fr["n"]]
@@ -140,20 +146,22 @@ def compact_line(full, side_file=None):
     return line
 
 
-SIDE_FILE = {"path": None}       # --side-file
+SIDE_FILE = {"path": None, "write": True}    # --side-file; "write": False on a plain run without it
 
 
 def emit(full, workload=None, world=1):
-    """Rank 0's output: the whole record into the side file (gpurun_out/ travels back from a GPU
-    box), then the ONE stdout line."""
-    path = SIDE_FILE["path"] or side_file_path(workload or "run", world)
-    try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as fid:
-            json.dump(full, fid, indent=1)
-    except OSError as err:                       # a read-only tree: the line still goes out
-        print(f"bench.py: side file not written: {err}", file=sys.stderr)
-        path = None
+    """Rank 0's output: the whole record into the side file (with --full or --side-file), then
+    the ONE stdout line."""
+    path = None
+    if SIDE_FILE["write"]:
+        path = SIDE_FILE["path"] or side_file_path(workload or "run", world)
+        try:
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as fid:
+                json.dump(full, fid, indent=1)
+        except OSError as err:                   # a read-only tree: the line still goes out
+            print(f"bench.py: side file not written: {err}", file=sys.stderr)
+            path = None
     if os.environ.get("PANO_BENCH_FULL_LINE") == "1":   # (tools/ab_*.sh: the whole record as the line)
         print(json.dumps(full), flush=True)
         return
@@ -167,7 +175,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg3",
                     choices=["cfg2", "cfg3", "cfg5", "cfg4", "tiny"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline: the instrumented pass "
+                         "(kernel_ms_per_step, roofline), one stitch at a time, the secondaries, the "
+                         "CPU baseline, the busy loop, and the side file; without it a run sets up, "
+                         "warms up, times the K steps, dumps (--dump-outputs) and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--mode", default="strips", choices=["strips", "sets"],
                     help="N > 1: 'strips' = one image set per step, its mosaic split into "
                          "column strips (default, strong scaling); 'sets' = one independent "
@@ -175,8 +189,8 @@ def parse():
     ap.add_argument("--exchange", default="gather", choices=["gather", "reduce"],
                     help="N > 1, strips: how the strips are composed on rank 0")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements (N = 1, default workload: the other "
-                         "BASELINE configs and the float32 vector-ALU blur; N > 1: the other "
+                    help="--full: skip the secondary measurements (N = 1, default workload: the "
+                         "other BASELINE configs and the float32 vector-ALU blur; N > 1: the other "
                          "exchange, replicas)")
     ap.add_argument("--secondary-timeout", type=float, default=180.0)
     ap.add_argument("--in-flight", type=int, default=0,
@@ -186,19 +200,20 @@ def parse():
     ap.add_argument("--busy-seconds", type=float, default=None,
                     help="after the measurements keep stitching for this long (untimed), so that a "
                          "sampler polling the GPU every few seconds sees it busy; default 6 for "
-                         "the plain one-GPU config-3 run, else 0")
+                         "the one-GPU config-3 run with --full, else 0")
     ap.add_argument("--plan", default="per_stitch", choices=["per_stitch", "memo"],
                     help="the host geometry (engine.Plan) of the headline, at EVERY --gpus: "
                          "'per_stitch' (default) recomputes it every stitch as the reference does "
                          "(stitcher.py:276-302), two stitches in flight; 'memo' takes it out of the "
                          "content-keyed memo (engine.PlanMemo; exact: same cameras -> same plan) with "
                          "trusted layouts (no host wait inside a stitch) and three stitches in flight. "
-                         "The line's `settings` says which; the other one is timed as a secondary "
-                         "(`alt_settings`), so N = 1 and N = 8 compare like with like either way")
+                         "The line's `settings` says which; with --full the other one is timed as a "
+                         "secondary (`alt_settings`), so N = 1 and N = 8 compare like with like either way")
     ap.add_argument("--no-plan-cache", action="store_true",
                     help="(rounds 4 - 5; now the default) same as --plan per_stitch")
     ap.add_argument("--side-file", default=None,
-                    help="where the whole record goes (default gpurun_out/bench_full_<workload>_n<N>.json)")
+                    help="where the whole record goes (written with --full or this option; "
+                         "default: bench_full_<workload>_n<N>.json, see side_file_path)")
     ap.add_argument("--detect", action="store_true",
                     help="cfg4: time detectAndCompute (keypoints + descriptors) too")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -552,16 +567,16 @@ def dump_outputs(directory, outputs):
         left -= sum(os.path.getsize(f) for f in files)
 
 
-def timed_steps(eng, step, steps, warmup, fence, finish=None, keep=None):
+def timed_steps(eng, step, steps, warmup, fence, finish=None, keep=None, instrument=True):
     """W untimed steps, then exactly K steps between two fences: the headline time, with no
-    instrumentation inside.  Then the same K steps once more with HIP events around every
-    launch (`pano_timing_enable`): the per-kernel times of the roofline.  (The events cost
-    2 % of a config-3 stitch, 7 % of config 2 and 29 % of config 4's seventy launches per
-    frame - too much to charge the headline with.)  Returns (headline seconds on this rank,
-    last step's result, per-kernel times); ``finish`` completes what the steps left in
-    flight (the exchange of the last stitch) inside each timed region.  ``keep`` is called
-    with the headline region's last step result and what ``finish`` returned, after its
-    closing fence and before anything else runs (--dump-outputs)."""
+    instrumentation inside.  Then, if ``instrument`` (--full), the same K steps once more with
+    HIP events around every launch (`pano_timing_enable`): the per-kernel times of the roofline.
+    (The events cost 2 % of a config-3 stitch, 7 % of config 2 and 29 % of config 4's seventy
+    launches per frame - too much to charge the headline with.)  Returns (headline seconds on
+    this rank, last step's result, per-kernel times or None); ``finish`` completes what the
+    steps left in flight (the exchange of the last stitch) inside each timed region.  ``keep``
+    is called with the headline region's last step result and what ``finish`` returned, after
+    its closing fence and before anything else runs (--dump-outputs)."""
     def region(events):
         fence()
         eng.timing(events)
@@ -578,6 +593,8 @@ def timed_steps(eng, step, steps, warmup, fence, finish=None, keep=None):
     elapsed, result, last = region(False)
     if keep is not None:
         keep(result, last)
+    if not instrument:
+        return elapsed, result, None
     INSTRUMENTED["seconds"], result, _ = region(True)
     times = eng.kernel_times()
     eng.timing(False)
@@ -625,9 +642,11 @@ class Watchdog:
             return True
 
 
-def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None, keep=None):
-    """Config 4: Gaussian / DoG scale space of 3840 x 2160 frames, one frame per step.  ``keep``:
-    as in timed_steps, called with (pyramid, detection or None) of the last timed frame."""
+def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None, keep=None,
+             instrument=True):
+    """Config 4: Gaussian / DoG scale space of 3840 x 2160 frames, one frame per step.  ``keep``
+    and ``instrument``: as in timed_steps, ``keep`` called with (pyramid, detection or None) of
+    the last timed frame."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     detect = args.detect if detect is None else detect
@@ -706,7 +725,8 @@ def run_cfg4(args, eng, rank, world, steps=None, warmup=None, detect=None, keep=
             return total
     elapsed, (pyr, n_kp, _), times = timed_steps(
         AllLanes(), step, steps, warmup, fence,
-        keep=None if keep is None else (lambda result, _: keep(result[0], result[2])))
+        keep=None if keep is None else (lambda result, _: keep(result[0], result[2])),
+        instrument=instrument)
     for lane in range(len(lanes)):           # the last frames' keypoints are still in flight
         job = state.get(("job", lane))
         if job is not None:
@@ -797,21 +817,25 @@ def cfg4_line(args, world, elapsed, pyr, n_kp, times, size):
                    "parallelism": "independent frames, one per GPU (replicas only); on a GPU "
                                   "consecutive frames alternate between two streams (a frame's "
                                   "small octaves are a chain of few-workgroup launches)"},
-        "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(times.items())},
-        "instrumented_ms_per_step": INSTRUMENTED.get("seconds", 0.0) / args.steps * 1e3,
-        "instrumentation": "ms_per_step / value: K steps with no instrumentation inside, two frames in "
-                           "flight, graph replay; kernel_ms_per_step: the same K steps once more ONE "
-                           "frame at a time, launch by launch, with HIP events around every launch "
-                           "(29 % of overhead on a frame's seventy launches: its kernels' times add up "
-                           "to MORE than ms_per_step and are no evidence for the roofline - that is "
-                           "the step time's; per-kernel durations: profiles/*/cfg4_*_kernel_stats_steady.txt, "
-                           "rocprofv3)",
     }
+    if times is not None:                    # the instrumented pass ran (--full)
+        out.update({
+            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(times.items())},
+            "instrumented_ms_per_step": INSTRUMENTED.get("seconds", 0.0) / args.steps * 1e3,
+            "instrumentation": "ms_per_step / value: K steps with no instrumentation inside, two frames "
+                               "in flight, graph replay; kernel_ms_per_step: the same K steps once more "
+                               "ONE frame at a time, launch by launch, with HIP events around every "
+                               "launch (29 % of overhead on a frame's seventy launches: its kernels' "
+                               "times add up to MORE than ms_per_step and are no evidence for the "
+                               "roofline - that is the step time's; per-kernel durations: "
+                               "profiles/*/cfg4_*_kernel_stats_steady.txt, rocprofv3)",
+        })
     if n_kp is not None:
         out["config"]["keypoints_per_frame"] = n_kp
-        out["sift"] = sift_backend_roofline(SIFT_KPS.get("last"), times, args.steps)
-        if out["sift"]:
-            out["sift"]["keypoints_per_s_end_to_end"] = n_kp * world / (ms * 1e-3)
+        if times is not None:
+            out["sift"] = sift_backend_roofline(SIFT_KPS.get("last"), times, args.steps)
+            if out["sift"]:
+                out["sift"]["keypoints_per_s_end_to_end"] = n_kp * world / (ms * 1e-3)
     name = max(times, key=lambda k: times[k][0]) if times else None
     out["roofline"] = dict(kernel=name or "scale space (all launches)", bound="hbm",
                            achieved=algo / (ms * 1e-3) / 1e9, peak=HBM_PEAK_GBPS, unit="GB/s",
@@ -1125,6 +1149,7 @@ def main():
     args = parse()
     if args.side_file:
         SIDE_FILE["path"] = os.path.abspath(args.side_file)
+    SIDE_FILE["write"] = args.full or bool(args.side_file)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
     import torch
@@ -1177,11 +1202,11 @@ def main():
                 out["descriptors"] = desc
             return out
         elapsed, pyr, n_kp, times, size = run_cfg4(args, eng, rank, world,
-                                                   keep=dumper(cfg4_outputs))
+                                                   keep=dumper(cfg4_outputs), instrument=args.full)
         elapsed = pdist.max_over_ranks(elapsed, reduce_device)
         if rank == 0:
             out = cfg4_line(args, world, elapsed, pyr, n_kp, times, size)
-            if not args.no_cpu_baseline and world == 1:
+            if args.full and not args.no_cpu_baseline and world == 1:
                 out["cpu_baseline"] = cpu_baseline_cfg4()
             out["comm"] = dict(COMM)
             emit(out, args.workload, world)
@@ -1271,7 +1296,7 @@ def main():
         fence()
         elapsed, (plan, _, patches), times = timed_steps(
             AllLanes(engines, serial), strips_step, args.steps, args.warmup, fence, runner.finish,
-            keep)
+            keep, instrument=args.full)
         runner.close()                    # the lanes' communicators (collective: every rank, same order)
         return pdist.max_over_ranks(elapsed, reduce_device), plan, patches, times, runner
 
@@ -1321,12 +1346,13 @@ def main():
         fence()
         elapsed, (plan, _, patches), times = timed_steps(
             AllLanes([use for use, _ in lanes], serial), step, args.steps, args.warmup, fence,
-            keep=keep)
-        # the same K steps one stitch at a time on one engine and stream, no instrumentation: what a
-        # caller who hands in one image set and waits for its mosaic sees (the reference's timer,
-        # stitcher.py:441-444, brackets one stitch) - `ms_per_stitch_one_in_flight` of the line
+            keep=keep, instrument=args.full)
+        # (--full) the same K steps one stitch at a time on one engine and stream, no
+        # instrumentation: what a caller who hands in one image set and waits for its mosaic sees
+        # (the reference's timer, stitcher.py:441-444, brackets one stitch) -
+        # `ms_per_stitch_one_in_flight` of the line
         ONE["ms"] = None
-        if len(lanes) > 1 and not setting["trusted"]:
+        if args.full and len(lanes) > 1 and not setting["trusted"]:
             serial["on"] = True
             for _ in range(2):
                 step()
@@ -1381,13 +1407,12 @@ def main():
         if not strips and in_flight > 1:
             how += (f"; {in_flight} consecutive stitches in flight per GPU (alternating "
                     f"engines / streams: ms_per_step is the time per stitch of the pipelined "
-                    f"sequence; ms_per_stitch_one_in_flight: one at a time)")
+                    f"sequence" + ("; ms_per_stitch_one_in_flight: one at a time)" if args.full
+                                   else ")"))
         how += ("; plan out of the content-keyed memo, trusted layouts" if setting["plan"] == "memo"
                 else "; plan recomputed per stitch (stitcher.py:276-302)")
         warped = sum((p.window[1] - p.window[0]) * (p.window[3] - p.window[2]) for p in patches)
         blurred = sum((p.area[1] - p.area[0]) * (p.area[3] - p.area[2]) for p in patches)
-        timed_kernel_ms = sum(v[0] for v in times.values()) / args.steps
-        gathered = eng.gather_bytes(plan.shape, n_levels)       # this rank's last stitch
         out = {
             "metric": "blended megapixels/sec (multiband)",
             "value": sets_per_step * P / (ms * 1e-3) / 1e6,
@@ -1396,24 +1421,17 @@ def main():
             # (a) WHAT is counted: the reference's patch pixels P, not the pixels the kernels touch
             "value_kind": "reference_equivalent_px",
             "processed_MPps": warped / (ms * 1e-3) / 1e6 * (1 if strips or world == 1 else world),
-            # (b) HOW it is timed: `pipelined` consecutive stitches in flight; one stitch alone beside it
+            # (b) HOW it is timed: `pipelined` consecutive stitches in flight (--full: one stitch
+            # alone beside it)
             "pipelined": in_flight,
-            "ms_per_stitch_one_in_flight": (None if strips else
-                                            (ONE.get("ms") if in_flight > 1
-                                             else ms / sets_per_step)),
             # (c) the ARITHMETIC behind `dtype`: float32 storage and accumulation, every product of
             # the Gaussian levels as three float16 matrix-core products of split operands (the
-            # dropped lo x lo term is 2^-22 relative); the strict-float32 blur's step time is
-            # lifted beside it from secondary.blur_valu_f32 when that ran
+            # dropped lo x lo term is 2^-22 relative) (--full: the strict-float32 blur's step time
+            # beside it)
             "arithmetic": "f16x3-split products, f32 accumulate (2^-22)",
-            "ms_per_step_strict_f32": None,
             # the settings of this measurement - identical at every --gpus
             "settings": dict(setting, exchange=args.exchange if strips else None,
                              mode="strips" if strips else "sets"),
-            # share of the timed region the GPU spent inside the timed kernels (the kernels' HIP-event
-            # times of the instrumented pass, added up, over the headline's wall time per step):
-            # what a utilisation sampler would see if it sampled the timed region only
-            "duty_cycle": (timed_kernel_ms / ms) if ms > 0 else None,
             "value_counts": "reference-equivalent patch pixels: the pixels P the reference's "
                             "algorithm warps and blends for this image set (SURVEY §8d) per second; "
                             "the kernels warp and blur far fewer (processed.*), exactly",
@@ -1464,28 +1482,44 @@ def main():
                 "ratio_to_hbm_peak_all_gpus": ref_bytes / (ms * 1e-3) / 1e9
                                               / (HBM_PEAK_GBPS * world),
             },
-            "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(times.items())},
-            "instrumented_ms_per_step": INSTRUMENTED.get("seconds", 0.0) / args.steps * 1e3,
-            "instrumentation": "ms_per_step / value: K steps with no instrumentation inside; "
-                               "kernel_ms_per_step and roofline: the same K steps once more with HIP "
-                               "events around every launch (instrumented_ms_per_step), rank 0",
-            "hbm_traffic": (lambda b: None if b is None else {
-                "GB_per_step_per_gpu": b / 1e9,
-                "GBps_per_gpu": b / (ms * 1e-3) / 1e9,
-                "frac_of_hbm_peak": b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                "source": "profiles/*/pmc_traffic*.json (FETCH_SIZE x 2 + WRITE_SIZE per launch) "
-                          "x launches per step, this rank's kernels"})(
-                measured_traffic(times, args.steps, args.workload) if world == 1 else None),
-            "roofline": roofline_for(times, plan, patches, n_levels, args.steps,
-                                     eng.active_tile_pixels(), args.workload, gathered),
         }
-        out["roofline_by_kernel"] = roofline_by_kernel(times, plan, patches, n_levels, args.steps,
-                                                       eng.active_tile_pixels(), args.workload,
-                                                       gathered)
-        out["collapse_gather_GB"] = None if gathered is None else gathered / 1e9
-        projection = scaling_projection(args.workload)
-        if projection is not None:
-            out["scaling_projection"] = projection
+        if args.full:
+            # what the instrumented pass (timed_steps), the one-at-a-time pass (run_sets) and the
+            # secondaries add to the headline
+            timed_kernel_ms = sum(v[0] for v in times.values()) / args.steps
+            gathered = eng.gather_bytes(plan.shape, n_levels)       # this rank's last stitch
+            out.update({
+                "ms_per_stitch_one_in_flight": (None if strips else
+                                                (ONE.get("ms") if in_flight > 1
+                                                 else ms / sets_per_step)),
+                # lifted from secondary.blur_valu_f32 when that ran
+                "ms_per_step_strict_f32": None,
+                # share of the timed region the GPU spent inside the timed kernels (the kernels'
+                # HIP-event times of the instrumented pass, added up, over the headline's wall time
+                # per step): what a utilisation sampler would see if it sampled the timed region only
+                "duty_cycle": (timed_kernel_ms / ms) if ms > 0 else None,
+                "kernel_ms_per_step": {k: v[0] / args.steps for k, v in sorted(times.items())},
+                "instrumented_ms_per_step": INSTRUMENTED.get("seconds", 0.0) / args.steps * 1e3,
+                "instrumentation": "ms_per_step / value: K steps with no instrumentation inside; "
+                                   "kernel_ms_per_step and roofline: the same K steps once more with "
+                                   "HIP events around every launch (instrumented_ms_per_step), rank 0",
+                "hbm_traffic": (lambda b: None if b is None else {
+                    "GB_per_step_per_gpu": b / 1e9,
+                    "GBps_per_gpu": b / (ms * 1e-3) / 1e9,
+                    "frac_of_hbm_peak": b / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                    "source": "profiles/*/pmc_traffic*.json (FETCH_SIZE x 2 + WRITE_SIZE per launch) "
+                              "x launches per step, this rank's kernels"})(
+                    measured_traffic(times, args.steps, args.workload) if world == 1 else None),
+                "roofline": roofline_for(times, plan, patches, n_levels, args.steps,
+                                         eng.active_tile_pixels(), args.workload, gathered),
+            })
+            out["roofline_by_kernel"] = roofline_by_kernel(times, plan, patches, n_levels, args.steps,
+                                                           eng.active_tile_pixels(), args.workload,
+                                                           gathered)
+            out["collapse_gather_GB"] = None if gathered is None else gathered / 1e9
+            projection = scaling_projection(args.workload)
+            if projection is not None:
+                out["scaling_projection"] = projection
         if world > 1:
             out["scaling_note"] = "unmeasured on multi-GPU hardware by the builder (1-GPU boxes)"
             # north_star's >= 6 x at 8 GPUs: config 5 (the 120 x 8K roofline run) is the config
@@ -1503,7 +1537,7 @@ def main():
     if not strips:
         elapsed, plan, patches, times = run_sets(headline_setting, sets_outputs)
         out = build_line(False, headline_setting, elapsed, plan, patches, times) if rank == 0 else None
-        if world == 1 and not args.no_secondary and args.workload == "cfg3":
+        if args.full and world == 1 and not args.no_secondary and args.workload == "cfg3":
             out["secondary"] = secondary_single_gpu(eng, fence, other_setting)
             strict = out["secondary"].get("blur_valu_f32", {})
             out["ms_per_step_strict_f32"] = strict.get("ms_per_step")
@@ -1515,12 +1549,12 @@ def main():
         # secondaries that are bound by the host's launch rate measured 0.52 / 5.28 ms - config 2
         # with two stitches in flight, config 4 with detection - right behind it and 0.44 / 3.03 ms
         # without it, profiles/r05/notes.md; the driver's round-4 run had it in front: 4.94 ms).
-        if rank == 0 and not args.no_cpu_baseline and world == 1:
+        if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(cfg)
             out["cpu_baseline"]["pipelined"] = False     # one stitch at a time, start to finish
         busy = args.busy_seconds
         if busy is None:
-            busy = 6.0 if world == 1 and args.workload == "cfg3" else 0.0
+            busy = 6.0 if args.full and world == 1 and args.workload == "cfg3" else 0.0
         if busy > 0 and world == 1:
             # untimed: the driver samples GPU utilisation every ~5 s and the timed region is 0.03 s
             frames = upload(0, range(cfg["n"]))
@@ -1532,7 +1566,7 @@ def main():
                 torch.cuda.synchronize()
                 n_busy += 50
             out["busy_loop"] = {"seconds": busy, "stitches": n_busy, "timed": False}
-        if world > 1 and not args.no_secondary and args.workload != "cfg5":
+        if args.full and world > 1 and not args.no_secondary and args.workload != "cfg5":
             dog = Watchdog(args.secondary_timeout, rank, out, out=say)
             dog.start()
             extra = {}
@@ -1559,11 +1593,12 @@ def main():
 
     # ---- N > 1, one panorama over all GPUs -----------------------------------------------------
     # The strips' exchange is the one part of this repo that a 1-GPU box cannot rehearse on
-    # RCCL.  So the replicas (no data-path collective) are measured FIRST, and everything with
-    # an exchange runs under a watchdog: should it hang or fail, rank 0 still prints a valid
-    # line - the replicas' figure, marked as the fallback it is - and the job ends non-zero.
+    # RCCL.  So with --full the replicas (no data-path collective) are measured FIRST, and
+    # everything with an exchange runs under a watchdog: should it hang or fail, rank 0 still
+    # prints a valid line - the replicas' figure, marked as the fallback it is - and the job ends
+    # non-zero (a plain run has no fallback line: it ends non-zero and prints nothing).
     fallback = None
-    if not args.no_secondary and args.workload != "cfg5":
+    if args.full and not args.no_secondary and args.workload != "cfg5":
         e3, p3, pa3, t3 = run_sets(headline_setting)
         if rank == 0:
             fallback = build_line(False, headline_setting, e3, p3, pa3, t3)
@@ -1589,14 +1624,15 @@ def main():
         out = build_line(True, headline_setting, elapsed, plan, patches, times,
                          len(runner.my_frames),
                          runner.bounds if getattr(runner, "balanced", False) else None)
-        out["secondary"] = {}
+        if args.full:
+            out["secondary"] = {}
         if fallback is not None:
             out["secondary"]["replicas"] = {
                 "what": f"{world} independent image sets per step, one per GPU, no collective",
                 "ms_per_step": fallback["ms_per_step"], "value": fallback["value"],
                 "unit": "MP/s"}
     dog.retarget(out, "secondary_error")    # from here on a timeout still prints the strips line
-    if not args.no_secondary and args.workload != "cfg5":
+    if args.full and not args.no_secondary and args.workload != "cfg5":
         other = "reduce" if args.exchange == "gather" else "gather"
         runner = None
         try:

@@ -532,3 +532,49 @@ def test_bench_stdout_line_is_compact_and_complete():
     # the error notes of a failed multi-rank run ride on the line
     full["strips_error"] = "RuntimeError('x')"
     assert json.loads(bench.compact_line(full, None))["strips_error"] == "RuntimeError('x')"
+
+
+def test_bench_plain_run_times_only_the_headline(monkeypatch):
+    """A plain bench run is W warm-up steps and K timed ones (`timed_steps`, instrument=False): no
+    second, instrumented pass of K steps, no per-kernel times.  --full (off by default) adds that
+    pass back, and the plain record's stdout line carries the headline without an empty roofline
+    or secondaries."""
+    import json
+    bench = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "4", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+
+    class Engine:                                    # what timed_steps asks of an engine
+        def __init__(self):
+            self.events = []
+
+        def timing(self, on):
+            self.events.append(("timing", on))
+
+        def kernel_times(self):
+            self.events.append("kernel_times")
+            return {"k": (1.0, 4)}
+
+    for instrument in (False, True):
+        eng, calls, kept = Engine(), [], []
+
+        def step():
+            calls.append(eng.events[-1] if eng.events else None)
+            return len(calls)
+        elapsed, last, times = bench.timed_steps(eng, step, 4, 2, lambda: None,
+                                                 keep=lambda result, _: kept.append(result),
+                                                 instrument=instrument)
+        assert elapsed >= 0 and kept == [6]          # the headline region's last step, once
+        if instrument:
+            assert len(calls) == 2 + 4 + 4 and times == {"k": (1.0, 4)} and last == 10
+            assert calls[6:] == [("timing", True)] * 4
+        else:
+            assert len(calls) == 2 + 4 and times is None and last == 6
+            assert "kernel_times" not in eng.events and ("timing", True) not in eng.events
+    plain = {"metric": "blended megapixels/sec (multiband)", "value": 1.0, "unit": "MP/s",
+             "n_gpus": 1, "steps": 4, "warmup": 2, "ms_per_step": 1.5, "higher_is_better": True,
+             "dtype": "f32", "config": {"workload": "cfg3"}, "settings": {"plan": "per_stitch"}}
+    got = json.loads(bench.compact_line(plain, None))
+    assert got == plain

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Steady-state profile of one bench workload: rocprofv3 kernel trace of
-#   python3 bench.py --workload WL --steps 50 --warmup 5 --no-cpu-baseline --no-secondary
+#   python3 bench.py --workload WL --steps 50 --warmup 5 --full --no-cpu-baseline --no-secondary
 # reduced by tools/trace_stats.py (first dispatches dropped; the instrumented pass apart), with the
 # bench line of the SAME run beside it.   tools/gpu_profile.sh <tag> [workload] [steps]
 set -u
@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_$WL" -- \
-    python3 "$HERE/bench.py" --workload "$WL" --steps "$STEPS" --warmup 5 --no-cpu-baseline --no-secondary --busy-seconds 0 --side-file "$OUT/bench_${WL}_profiled_full.json" ${BENCH_EXTRA:-} \
+    python3 "$HERE/bench.py" --workload "$WL" --steps "$STEPS" --warmup 5 --full --no-cpu-baseline --no-secondary --busy-seconds 0 --side-file "$OUT/bench_${WL}_profiled_full.json" ${BENCH_EXTRA:-} \
     > "$OUT/bench_${WL}_profiled.json" 2> "$OUT/rocprof_$WL.log"
 echo "rocprof rc=$?"
 cd "$HERE"

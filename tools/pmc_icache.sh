@@ -11,7 +11,7 @@ rocprofv3 -L 2>/dev/null | grep -i -E "icache|ifetch|inst_cache|SQC_" | head -60
 run() {
   name=$1; shift
   timeout 600 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/$name" -- \
-      python3 "$HERE/bench.py" --workload cfg3 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary \
+      python3 "$HERE/bench.py" --workload cfg3 --steps 2 --warmup 1 --full --no-cpu-baseline --no-secondary \
       > "$OUT/$name.log" 2>&1
   echo "pass $name rc=$?"
 }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How the kernels of the stitches in flight share the GPU: from a rocprofv3 --kernel-trace CSV of
-bench.py, over the TIMED steps (the K stitches in front of the last K, which are the instrumented
+bench.py --full, over the TIMED steps (the K stitches in front of the last K, which are the instrumented
 one-at-a-time pass).
 
     tools/trace_overlap.py KERNEL_TRACE.csv --steps K

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Steady-state per-kernel durations from a rocprofv3 --kernel-trace CSV of bench.py.
+"""Steady-state per-kernel durations from a rocprofv3 --kernel-trace CSV of bench.py --full.
 
     tools/trace_stats.py KERNEL_TRACE.csv --steps K [--drop N] [--out FILE.csv]
 
-bench.py runs setup and warm-up stitches, K timed steps (two stitches in flight on config 3:
+bench.py --full runs setup and warm-up stitches, K timed steps (two stitches in flight on config 3:
 the kernels of two streams overlap and stretch each other) and then the SAME K steps once
 more, one at a time, with HIP events around every launch - the pass its `kernel_ms_per_step`
 and `roofline` come from.  rocprofv3's own *_kernel_stats.csv averages all of that, cold
