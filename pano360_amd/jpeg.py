@@ -3,8 +3,8 @@
 ``parse`` reads the markers of one file on the host and returns a ``Header``, or None for
 anything the device path does not cover: progressive, arithmetic, lossless or 12-bit files,
 more than one scan, CMYK / YCCK / Adobe-transform files, sampling other than 4:4:4, 4:2:2 and
-4:2:0, quantisers above 255, XMP orientation, and every truncated or inconsistent file.  Those go
-to Pillow.
+4:2:0, quantisers above 255, XMP orientation, Huffman tables libjpeg refuses, and every truncated or
+inconsistent file.  Those go to Pillow.
 
 ``pack`` lays a batch out as the native call expects it (the layout is documented at
 ``pano_jpeg_decode`` in include/pano360.h): one int64 descriptor table, the per-image Huffman
@@ -213,6 +213,8 @@ def parse(blob):
                 if t >> 4 > 3 or t & 15 > 3 or dc[t >> 4] is None or ac[t & 15] is None \
                         or qt[comps[i][3]] is None:
                     return None
+                if max(dc[t >> 4][1], default=0) > 15:
+                    return None                         # libjpeg: a bad DC table
             ss, se, ahl = body[1 + 2 * ns:4 + 2 * ns]
             if ss != 0 or se != 63 or ahl != 0:
                 return None

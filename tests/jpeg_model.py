@@ -241,8 +241,13 @@ def decode(blob, hdr=None):
     """uint8 BGR [h][w][3] of an in-scope JPEG."""
     hdr = hdr or J.parse(blob)
     assert hdr is not None
+    return pixels(hdr, coefficients(hdr, blob))
+
+
+def pixels(hdr, coef):
+    """uint8 BGR [h][w][3] of the coefficients (``coefficients``' layout) of a header."""
     w, h = hdr.width, hdr.height
-    pl = planes(hdr, coefficients(hdr, blob))
+    pl = planes(hdr, coef)
     if len(hdr.comps) == 1:
         g = pl[0][:h, :w]
         img = np.stack([g, g, g], axis=-1)
@@ -255,3 +260,79 @@ def decode(blob, hdr=None):
             ch.append(upsample(pl[c], cw, chh, hm // hc, vm // vc, w, h))
         img = ycc_to_bgr(pl[0][:h, :w], ch[0], ch[1])
     return np.ascontiguousarray(orient(img, hdr.orientation))
+
+
+# ---- the device's Huffman synchronisation schedule (jpeg_huff_sync_kernel) ---------------------
+def _lut(table):
+    """16-bit prefix -> (length << 8) | symbol; an invalid code reads as symbol 0 of 1 bit."""
+    lut = np.full(1 << 16, 1 << 8, np.int64)
+    for length, code, sym in J.huff_codes(*table):
+        lo = code << (16 - length)
+        lut[lo:lo + (1 << (16 - length))] = (length << 8) | sym
+    return lut.tolist()
+
+
+def sync_rounds(hdr, blob):
+    """The rounds ``pano_jpeg_decode`` runs for this image decoded alone (the
+    ``jpeg_huff_sync_kernel`` launch count - 1), restated: each interval is cut into
+    ``J.SUBSEQ``-bit subsequences; round 0 decodes each from its first bit, the first of an
+    interval in the true state and the others guessing (block 0, coefficient 0); round r
+    re-decodes a subsequence only when its predecessor's exit (bit, block, coefficient) changed
+    in round r - 1; the rounds end with the first that changes no exit, or at the kernel's
+    bound.  Decoding runs while the position is before the subsequence's end; an invalid code
+    reads as symbol 0 and consumes 1 bit; bytes past the interval read as zero.  A Python loop
+    per symbol: for entropy data up to a few hundred KB."""
+    mx, my, bpm = hdr.mcus
+    order = block_order(hdr)
+    comp_of = [c for c, _, _ in order[:bpm]]
+    dcl = {t: _lut(hdr.dc[t]) for t in {c[4] for c in hdr.comps}}
+    acl = {t: _lut(hdr.ac[t]) for t in {c[5] for c in hdr.comps}}
+    dc_u = [dcl[hdr.comps[c][4]] for c in comp_of]
+    ac_u = [acl[hdr.comps[c][5]] for c in comp_of]
+    data_len = hdr.data_end - hdr.data_start
+    bound = data_len * 8 // J.SUBSEQ + 2
+    worst = 1
+    for data in destuff(blob[hdr.data_start:hdr.data_end]):
+        nbits = 8 * len(data)
+        padded = data + bytes(8)
+        win = [int.from_bytes(padded[i:i + 4], "big") for i in range(len(data) + 4)]
+
+        def run(pos, u, k, stop):
+            while pos < stop:
+                w = ((win[pos >> 3] << (pos & 7)) >> 16) & 0xFFFF
+                f = (dc_u if k == 0 else ac_u)[u][w]
+                pos += f >> 8
+                sym = f & 255
+                s = sym & 15
+                if s:
+                    pos += s
+                if k == 0:
+                    k = 1
+                elif s:
+                    k += (sym >> 4) + 1
+                elif sym >> 4 == 15:
+                    k += 16
+                else:
+                    k = 64
+                if k >= 64:
+                    k = 0
+                    u = u + 1 if u + 1 < bpm else 0
+            return pos, u, k
+
+        nsub = max(1, -(-nbits // J.SUBSEQ))
+        stops = [min((j + 1) * J.SUBSEQ, nbits) for j in range(nsub)]
+        exits = [run(j * J.SUBSEQ, 0, 0, stops[j]) for j in range(nsub)]
+        changed = [True] * nsub
+        rounds = 0
+        while True:
+            rounds += 1
+            nxt, nchanged = list(exits), [False] * nsub
+            for j in range(1, nsub):
+                if changed[j - 1]:
+                    nxt[j] = run(*exits[j - 1], stops[j])
+                    nchanged[j] = nxt[j] != exits[j]
+            exits, changed = nxt, nchanged
+            if not any(changed) or rounds >= bound:
+                break
+        worst = max(worst, rounds)
+    return min(worst, bound)
