@@ -415,18 +415,14 @@ int pano_layout_place(pano_patch *records, int n_records, void *planes, void *bl
  * which needs cams, the trig tables and the colour tables (all NULL
  * otherwise).
  * classes (optional, with interior): the level classes of pano_interior_classes - a pixel
- * of class j >= 1 gathers the copies j - 1 and up only (see there).
- * part: 0 = every pixel of the strip; 1 = the interior pixels only - they depend
- * on the owner map and the frames, not on the patches (patches / valid may be
- * NULL), so this part can be queued on another stream beside the warp and the
- * blur; 2 = the remaining pixels only. */
+ * of class j >= 1 gathers the copies j - 1 and up only (see there). */
 int pano_multiband_compose(pano_ctx *ctx, const pano_patch *patches, int n, int H, int W,
                            int xs0, int xs1, int n_levels, const int16_t *owner,
                            const uint8_t *valid, const uint8_t *interior,
                            const uint8_t *classes, const pano_camera *cams,
                            const double *sin_t, const double *cos_t, const double *tan_p,
                            const float *lut, int lut_stride, uint8_t *mosaic,
-                           float *mosaic_f32, int part);
+                           float *mosaic_f32);
 
 /* linear_blend (linear != 0) or no_blend (linear == 0) of the mosaic columns
  * [xs0, xs1) straight from the frames         stitcher.py:160-183 + :300-317

@@ -135,7 +135,7 @@ _SIGNATURES = {
     "pano_interior_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pano_interior_classes": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "pano_multiband_compose": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _i, _vp, _vp, _i]),
+                                    _vp, _vp, _vp, _i, _vp, _vp]),
     "pano_blend_cameras": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp,
                                 _vp]),
     "pano_blur_tile_grid": (_i, [_vp]),

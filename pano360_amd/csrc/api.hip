@@ -258,7 +258,7 @@ int pano_ctx_tap_set_built(pano_ctx *ctx, PanoTapSet *set) {
 // bench.py measures the dominant kernel's launch durations live with HIP events
 // recorded on the stream the kernel is launched on.  Instrumentation only: off
 // unless pano_timing_enable(ctx, 1) was called.
-static const char *const g_kernel_names[PK_COUNT] = {
+static const char *const g_kernel_names[] = {
     "add_weights_kernel", "warp_spherical_kernel", "ownership_kernel", "blur_rows_kernel",
     "blur_cols_kernel",   "multiband_compose_kernel", "linear_blend_kernel",
     "no_blend_kernel",    "crop_heights_kernel", "crop_rows_kernel", "pyr_down_kernel",
@@ -266,13 +266,15 @@ static const char *const g_kernel_names[PK_COUNT] = {
     "blend_cameras_kernel", "owned_spans_kernel",
     "block_owner_kernel", "tile_flags_kernel", "overlap_stats_kernel",
     "blur_mfma_kernel", "sift_extrema_kernel", "sift_orient_kernel", "sift_describe_kernel",
-    "compose_interior_kernel", "scale_step_kernel", "knn2_kernel", "blur_lean_kernel", "blur_lean5_kernel",
+    "scale_step_kernel", "knn2_kernel", "blur_lean_kernel", "blur_lean5_kernel",
     "ransac_score_kernel", "ransac_finish_kernel", "match_pack_kernel",
     "ba_residual_kernel", "ba_pair_kernel", "ba_assemble_kernel",
     "jpeg_destuff_kernel", "jpeg_scan_kernel", "jpeg_intervals_kernel", "jpeg_huff_sync_kernel",
     "jpeg_huff_write_kernel", "jpeg_dc_kernel", "jpeg_idct_kernel", "jpeg_pixels_kernel",
     "jpeg_enc_blocks_kernel", "jpeg_enc_count_kernel", "jpeg_enc_scan_kernel", "jpeg_enc_emit_kernel",
     "jpeg_enc_stuff_kernel"};
+static_assert(sizeof(g_kernel_names) / sizeof(g_kernel_names[0]) == PK_COUNT,
+              "one name per PanoKernelId, in enum order");
 
 void pano_timing_edge(pano_ctx *ctx, int kid, hipStream_t stream, bool begin) {
     hipEvent_t ev;

@@ -860,7 +860,6 @@ struct InteriorArgs {
     const pano_camera *cams;
     const double *sin_t, *cos_t, *tan_p;
     const float *lut;            // [256], or [n][256] when PERCAM
-    int part;                    // 0 every pixel, 2 only the pixels the interior pass left
     const uint8_t *classes;      // [H8][W8] level classes (interior_tile_kernel), NULL = all class 0
 };
 
@@ -918,29 +917,6 @@ __device__ __forceinline__ void shade_interior_of(int own, const float *__restri
         shade_interior<LUT>(ia.cams + own, table + (size_t)own * stride, ia, x, y, W, mosaic, mosaic_f32);
 }
 
-// The interior pixels alone (part 1 of the collapse): they need the owner map and the
-// frames, not the blurred planes, so a caller can run them on a second stream.  (Beside the
-// blur, with no LDS so that its waves fit on a CU next to the blur's workgroup, it costs the blur
-// more than it saves the collapse: profiles/r05/notes.md, section 10.)
-template <int LUT>
-__global__ __launch_bounds__(256) void compose_interior_kernel(
-    int H, int W, int xs0, int xs1, const int16_t *__restrict__ owner,
-    uint8_t *__restrict__ mosaic, float *__restrict__ mosaic_f32, InteriorArgs ia, int lut_stride) {
-    __shared__ float s_lut[LUT == LUT_LDS ? 256 : 1];
-    if (LUT == LUT_LDS) {
-        s_lut[threadIdx.y * 64 + threadIdx.x] = ia.lut[threadIdx.y * 64 + threadIdx.x];
-        __syncthreads();
-    }
-    const int x = xs0 + blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= xs1 || y >= H) return;
-    if (!ia.interior[(size_t)(y / IB) * ia.W8 + x / IB]) return;
-    const int own = owner[(size_t)y * W + x];
-    if (LUT == LUT_LDS)
-        shade_interior_of<LUT>(own, s_lut, 0, ia, x, y, W, mosaic, mosaic_f32);
-    else
-        shade_interior_of<LUT>(own, ia.lut, lut_stride, ia, x, y, W, mosaic, mosaic_f32);
-}
-
 #define COMPOSE_MASKS 4            // 256 records through the wave-wide test, more: plain scan
 // CLS: the gathers follow the pixels' level classes (ia.classes; option PANO_OPT_LEVEL_CLASSES).  A
 // template parameter, not a test of the pointer: with the class a run-time value in every pixel's
@@ -982,7 +958,6 @@ __global__ __launch_bounds__(256) void multiband_compose_kernel(
     if (!inside) return;
     if (is_interior) {
         // interior pixel: the mosaic is the owner's warped colour, clipped, quantised
-        if (ia.part == 2) return;                // compose_interior_kernel wrote it
         const int own = owner[(size_t)y * W + x];
         if (PERCAM)
             shade_interior_of<LUT_GLOBAL>(own, ia.lut, 256, ia, x, y, W, mosaic, mosaic_f32);
@@ -1410,15 +1385,11 @@ extern "C" int pano_multiband_compose(pano_ctx *ctx, const pano_patch *patches, 
                                       const uint8_t *classes, const pano_camera *cams,
                                       const double *sin_t,
                                       const double *cos_t, const double *tan_p, const float *lut,
-                                      int lut_stride, uint8_t *mosaic, float *mosaic_f32,
-                                      int part) {
+                                      int lut_stride, uint8_t *mosaic, float *mosaic_f32) {
     PANO_ENTER(ctx, "pano_multiband_compose");
-    PANO_REQUIRE(part >= 0 && part <= 2, "pano_multiband_compose: part %d outside 0..2", part);
-    PANO_REQUIRE(part == 0 || interior, "pano_multiband_compose: parts need the interior map");
-    if (part != 1)
-        if (int rc = check_table(patches, n, H, W, "pano_multiband_compose")) return rc;
+    if (int rc = check_table(patches, n, H, W, "pano_multiband_compose")) return rc;
     PANO_REQUIRE(H > 0 && W > 0, "pano_multiband_compose: bad mosaic shape %dx%d", H, W);
-    PANO_REQUIRE(owner && mosaic && (valid || part == 1), "pano_multiband_compose: null pointer");
+    PANO_REQUIRE(owner && mosaic && valid, "pano_multiband_compose: null pointer");
     PANO_REQUIRE(n_levels >= 1 && n_levels <= PANO_MAX_LEVELS,
                  "pano_multiband_compose: n_levels %d outside [1, %d]", n_levels, PANO_MAX_LEVELS);
     PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1,
@@ -1430,23 +1401,11 @@ extern "C" int pano_multiband_compose(pano_ctx *ctx, const pano_patch *patches, 
                  lut_stride);
     if (xs0 == xs1) return PANO_OK;
     PANO_REQUIRE(!classes || interior, "pano_multiband_compose: level classes without the interior map");
-    InteriorArgs ia = {interior, ceil_div(W, IB), cams, sin_t, cos_t, tan_p, lut, part,
+    InteriorArgs ia = {interior, ceil_div(W, IB), cams, sin_t, cos_t, tan_p, lut,
                        ctx->opt[PANO_OPT_LEVEL_CLASSES] ? classes : nullptr};
     const bool percam = interior && lut_stride != 0;
     dim3 block(64, 4), grid(ceil_div(xs1 - xs0, 64), ceil_div(H, 4));
     hipStream_t s = (hipStream_t)stream;
-    if (part == 1) {
-        if (percam)
-            PANO_TIMED(PK_COMPOSE_INTERIOR, s,
-                       hipLaunchKernelGGL(compose_interior_kernel<LUT_GLOBAL>, grid, block, 0, s, H,
-                                          W, xs0, xs1, owner, mosaic, mosaic_f32, ia, lut_stride));
-        else
-            PANO_TIMED(PK_COMPOSE_INTERIOR, s,
-                       hipLaunchKernelGGL(compose_interior_kernel<LUT_LDS>, grid, block, 0, s, H,
-                                          W, xs0, xs1, owner, mosaic, mosaic_f32, ia, lut_stride));
-        PANO_LAUNCH_CHECK("compose_interior_kernel");
-        return PANO_OK;
-    }
 #define COMPOSE_AS(L, PC, CL)                                                            \
     PANO_TIMED(PK_COMPOSE, s,                                                           \
                hipLaunchKernelGGL((multiband_compose_kernel<L, PC, CL>), grid, block, 0, s, \

@@ -62,7 +62,6 @@ enum PanoKernelId {
     PK_SIFT_EXTREMA,
     PK_SIFT_ORIENT,
     PK_SIFT_DESCRIBE,
-    PK_COMPOSE_INTERIOR,
     PK_SCALE_STEP,
     PK_KNN2,
     PK_BLUR_LEAN,

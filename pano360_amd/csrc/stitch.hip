@@ -313,7 +313,7 @@ static int queue_tail(pano_ctx *ctx, pano_stitch_args *a, const pano_layout &lay
                                   interior && stitch_has_classes(ctx, a, n_blur) ? a->classes : nullptr,
                                   interior ? a->cams : nullptr, interior ? a->sin_t : nullptr,
                                   interior ? a->cos_t : nullptr, interior ? a->tan_p : nullptr,
-                                  a->lut, a->lut_stride, a->mosaic, a->mosaic_f32, 0);
+                                  a->lut, a->lut_stride, a->mosaic, a->mosaic_f32);
 }
 
 // The buffers a stitch leaves its geometry in (and reads it from when it is kept).

@@ -9,7 +9,6 @@ resolution), :283-302 (mosaic shape, patch rectangles, angle grids), :218
 (level sigmas); OpenCV's getGaussianKernel for the taps (host, 33..97 floats).
 """
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -630,14 +629,11 @@ class Engine:
 
     ``blur``: which kernels run the multiband Gaussian levels - "mfma" (default, the fused
     matrix-core kernel) or "valu" (separate float32 row / column passes on the vector ALU).
-    ``side_stream``: 0 = one stream (default); 1 = interior collapse and the blur's work
-    list on a second stream; 2 = the work list only.  The second stream paid while the host
-    kept the GPU waiting between the region search and the warp (2.76 -> 2.67 ms); with the
-    native record layout there is no gap left to fill and one stream is as fast or faster
-    (cfg3 medians of 5 x 20 stitches: 2.352 / 2.421 / 2.350 ms; cfg2 0.661 / 0.654 /
-    0.669), so it stays an option for hosts slower than this pool's."""
+    A second stream for the launch-by-launch path's interior collapse and work list was
+    measured and removed: with the native record layout one stream was as fast or faster
+    (DESIGN.md §4, item 8)."""
 
-    def __init__(self, device=None, blur="mfma", side_stream=0, own_prune=True):
+    def __init__(self, device=None, blur="mfma", own_prune=True):
         torch = _torch()
         self.lib = _lib.lib()
         if not torch.cuda.is_available() or self.lib.pano_device_count() < 1:
@@ -655,9 +651,7 @@ class Engine:
         if blur not in ("mfma", "valu"):
             raise ValueError(f"blur kernel {blur!r}: 'mfma' or 'valu'")
         self.set_option(_lib.OPT_BLUR_KERNEL, _lib.BLUR_VALU if blur == "valu" else _lib.BLUR_MFMA)
-        # (PANO_OWN_PRUNE: A/B timing of the ownership kernels - 3 = round 4's one-level kernel)
-        self.set_option(_lib.OPT_OWN_PRUNE, int(os.environ.get("PANO_OWN_PRUNE", "1")) if own_prune
-                        else 0)
+        self.set_option(_lib.OPT_OWN_PRUNE, 1 if own_prune else 0)
         self.tile_grid = int(self.lib.pano_blur_tile_grid(self._ctx))
         self.interior_block = int(self.lib.pano_interior_block())
         lut = np.arange(256, dtype=np.float32) / np.float32(255)   # stitcher.py:259
@@ -667,26 +661,11 @@ class Engine:
         self._region_bufs = {}
         self._arenas = {}           # name -> float32 tensor kept across stitches
         self._ring = None
-        # second stream for the part of the collapse that needs no blurred planes
-        self.side = torch.cuda.Stream(self.device)
-        self.overlap_interior = side_stream == 1
-        self.overlap_prepare = side_stream in (1, 2)
-        self.warp_need = {"1": True, "0": False}.get(os.environ.get("PANO_WARP_NEED", ""), "auto")
-        # ("auto" | True | False: see multiband_fused; the environment switch is for A/B timing)
+        self.warp_need = "auto"             # "auto" | True | False: see multiband_fused
         self._cam_template = None
         # the whole launch sequence of a fused stitch in one native call (pano_stitch_multiband);
-        # False: launch by launch from here (the same entry points; what the side streams use)
-        self.native_stitch = side_stream == 0 and os.environ.get("PANO_NATIVE_STITCH", "1") != "0"
-        if os.environ.get("PANO_STITCH_STREAMS", "1") == "0":       # (A/B timing)
-            self.set_option(_lib.OPT_STITCH_STREAMS, 0)
-        if os.environ.get("PANO_STITCH_ASYNC", "0") == "1":         # (A/B timing)
-            self.set_option(_lib.OPT_STITCH_ASYNC, 1)
-        if os.environ.get("PANO_LEVEL_CLASSES", "0") == "1":        # (A/B: the collapse by level classes)
-            self.set_option(_lib.OPT_LEVEL_CLASSES, 1)
-        if os.environ.get("PANO_SIFT_GRAPH", "1") == "0":           # (A/B timing: launch by launch)
-            self.set_option(_lib.OPT_SIFT_GRAPH, 0)
-        if os.environ.get("PANO_BLUR_SEG_T"):                       # (A/B timing of the segments' length)
-            self.set_option(_lib.OPT_BLUR_SEG_LEN, int(os.environ["PANO_BLUR_SEG_T"]))
+        # False: launch by launch from here (the same entry points)
+        self.native_stitch = True
         self._stitch_ws = {}
         self._plans = PlanMemo()
         # Trusted stitches (ShardedStitcher with the plan memo, bench's plan-cached figures):
@@ -951,8 +930,6 @@ class Engine:
         n_blur, radius = self.blur_tables(n_levels)[2:]
         owner, valid = self.ownership_cameras(plan)
         a, b, g = self.COLUMN_COST_SHARES
-        if os.environ.get("PANO_COST_SHARES"):                      # (A/B of the model's weights)
-            a, b, g = (float(v) for v in os.environ["PANO_COST_SHARES"].split(","))
         cost = np.full(W, a / W)
         per = valid.ne(0).sum(0, dtype=torch.int64).cpu().numpy().astype(np.float64)
         if per.sum() > 0:
@@ -1030,96 +1007,37 @@ class Engine:
         mid = ((px > 0) & (px < nb)).sum().double() * 12.0
         return float((total + mid).item())
 
-    def compose_interior_async(self, owner, shape, strip, interior, cams, plan, luts,
-                               want_float=False, mosaic_out=None):
-        """Part 1 of the collapse - the interior pixels, which need the owner map and
-        the frames only - queued on the side stream behind everything queued so far.
-        Returns (mosaic, float mosaic, event) for ``blur_and_compose(out=...)``."""
-        torch = _torch()
-        H, W = shape
-        main = torch.cuda.current_stream(self.device)
-        mosaic = (mosaic_out if mosaic_out is not None else
-                  torch.empty((H, W, 3), dtype=torch.uint8, device=self.device))
-        fl = (torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-              if want_float else None)
-        ready = torch.cuda.Event()
-        ready.record(main)
-        self.side.wait_event(ready)
-        for t in (mosaic, fl, owner, interior, cams):
-            if t is not None:
-                t.record_stream(self.side)
-        _lib.check(self.lib.pano_multiband_compose(
-            self.ctx(self.side), None, 0, H, W, strip[0], strip[1], 1, _ptr(owner), None,
-            _ptr(interior), None, _ptr(cams),
-            _ptr(plan.dev[0]), _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts),
-            _ptr(mosaic), _ptr(fl), 1),
-            "pano_multiband_compose")
-        done = torch.cuda.Event()
-        done.record(self.side)
-        return mosaic, fl, done
-
-    def prepare_blur_async(self, table, W, interior, flags=None):
-        """Tile flags and the sorted work list of the blur (they depend on the records and
-        the interior map, not on the warped planes) on the side stream, beside the warp.
-        Returns (tile flags, event) for ``blur_and_compose(prepared=...)``."""
-        torch = _torch()
-        if flags is None and interior is not None:
-            flags = torch.empty(max(table.n_tiles, 1), dtype=torch.uint8, device=self.device)
-        uploaded = torch.cuda.Event()
-        uploaded.record(torch.cuda.current_stream(self.device))      # the record table
-        self.side.wait_event(uploaded)
-        for t in (flags, interior, table.dev):
-            if t is not None:
-                t.record_stream(self.side)
-        _lib.check(self.lib.pano_multiband_blur_prepare(
-            self.ctx(self.side), table.ptr, table.n, table.max_aw, table.max_ah, W, _ptr(interior),
-            _ptr(flags)), "pano_multiband_blur_prepare")
-        listed = torch.cuda.Event()
-        listed.record(self.side)
-        return flags, listed
-
     def blur_and_compose(self, table, owner, valid, shape, n_levels, want_float=False,
-                         strip=None, interior=None, cams=None, plan=None, luts=None, out=None,
-                         prepared=None, mosaic_out=None, classes=None):
+                         strip=None, interior=None, cams=None, plan=None, luts=None, flags=None,
+                         mosaic_out=None, classes=None):
         """All Gaussian levels of all patches (n_levels launches), then the gather
         over the mosaic columns ``strip`` (default: all of them).  With an
         ``interior`` map, blur tiles and gathers are skipped where the result is
-        the owner's colour (needs ``cams`` with frame pointers and ``plan``)."""
+        the owner's colour (needs ``cams`` with frame pointers and ``plan``).
+        ``flags``: tile flags pano_blur_tiles already wrote for this table."""
         torch = _torch()
         H, W = shape
         c0, c1 = strip if strip is not None else (0, W)
         taps, ntaps, n_blur, _ = self.blur_tables(n_levels)
         if n_blur:
-            if prepared is not None:        # tile flags and work list queued on the side stream
-                flags, listed = prepared
-                if listed is not None:
-                    torch.cuda.current_stream(self.device).wait_event(listed)
-            else:
-                flags = (torch.empty(max(table.n_tiles, 1), dtype=torch.uint8,
-                                     device=self.device) if interior is not None else None)
+            if flags is None and interior is not None:
+                flags = torch.empty(max(table.n_tiles, 1), dtype=torch.uint8, device=self.device)
             _lib.check(self.lib.pano_multiband_blur(
                 self.ctx(), table.ptr, table.n, table.max_aw, table.max_vh, table.max_ah,
                 _ptr(owner), W, taps.ctypes.data, ntaps, n_blur, _ptr(interior), _ptr(flags)),
                 "pano_multiband_blur")
             self.last_tiles = (table, flags)        # for active_tile_pixels (reporting)
-        if out is None:
-            mosaic = (mosaic_out if mosaic_out is not None else
-                      torch.empty((H, W, 3), dtype=torch.uint8, device=self.device))
-            fl = (torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-                  if want_float else None)
-            part = 0
-        else:                       # the interior pixels are being written on the side stream
-            mosaic, fl, done = out
-            part = 2
+        mosaic = (mosaic_out if mosaic_out is not None else
+                  torch.empty((H, W, 3), dtype=torch.uint8, device=self.device))
+        fl = (torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
+              if want_float else None)
         tabs = plan.dev if interior is not None else (None, None, None)
         _lib.check(self.lib.pano_multiband_compose(
             self.ctx(), table.ptr, table.n, H, W, c0, c1, n_levels, _ptr(owner), _ptr(valid),
             _ptr(interior), _ptr(classes) if interior is not None else None,
             _ptr(cams) if interior is not None else None, _ptr(tabs[0]),
-            _ptr(tabs[1]), _ptr(tabs[2]), *self._lut_args(luts), _ptr(mosaic), _ptr(fl),
-            part), "pano_multiband_compose")
-        if out is not None:
-            torch.cuda.current_stream(self.device).wait_event(done)
+            _ptr(tabs[1]), _ptr(tabs[2]), *self._lut_args(luts), _ptr(mosaic), _ptr(fl)),
+            "pano_multiband_compose")
         return mosaic, fl
 
     def simple_blend(self, patches, shape, linear, table=None):
@@ -1332,13 +1250,6 @@ class Engine:
                 interior, classes = self.interior_classes(owner, self.level_radii(n_levels), ext)
             else:
                 interior = self.interior_map(owner, radius, ext)
-        # The interior pixels of the mosaic need nothing but the owner map: queued now, on
-        # the side stream, they fill the GPU while the host waits for the regions and lays
-        # out the windows, and run beside the warp.  (Queued behind the warp instead they
-        # share the CUs with the blur and slow it by as much as they take: measured.)
-        early = (self.compose_interior_async(owner, plan.shape, (c0, c1), interior, cams, plan,
-                                             luts, want_float, mosaic_out)
-                 if interior is not None and self.overlap_interior else None)
         # the host is on the critical path from here to the warp: one native call lays out
         # the records (rectangles A and V, arena offsets, tile offsets)
         # (everything that does not need the regions is made ready before the wait)
@@ -1349,8 +1260,7 @@ class Engine:
         patches = FusedPatches.from_regions(regions.raw(), regions.max_spans, rects32,
                                             resident, radius, (c0, c1), n_blur, self, records)
         table = patches.table
-        # tile flags first (this stream): they tell the warp which blocks of the windows
-        # anything will read; the blur's work list then goes to the side stream
+        # tile flags first: they tell the warp which blocks of the windows anything will read
         flags = need = None
         # (worth it when the rectangles are wide against the blur's reach of ~3 tiles either
         # side of a seam: 8 x 1080p -4 %; on 32 x 4K nearly every tile is within reach and the
@@ -1365,17 +1275,13 @@ class Engine:
             _lib.check(self.lib.pano_blur_tiles(
                 self.ctx(), table.ptr, table.n, table.max_aw, table.max_ah, plan.shape[1], radius,
                 _ptr(interior), _ptr(flags), _ptr(need)), "pano_blur_tiles")
-        prepared = (self.prepare_blur_async(table, plan.shape[1], interior, flags)
-                    if n_blur and self.overlap_prepare else
-                    ((flags, None) if flags is not None else None))
         _lib.check(self.lib.pano_warp_windows(
             self.ctx(), _ptr(cams), table.ptr, table.n, table.max_vw, table.max_vh,
             _ptr(plan.dev[0]),
             _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(need)), "pano_warp_windows")
         mosaic, fl = self.blur_and_compose(table, owner, valid, plan.shape, n_levels,
                                            want_float, (c0, c1), interior, cams, plan, luts,
-                                           out=early, prepared=prepared, mosaic_out=mosaic_out,
-                                           classes=classes)
+                                           flags=flags, mosaic_out=mosaic_out, classes=classes)
         self.last_classes, self.last_interior = classes, interior
         return mosaic, fl, valid, patches
 

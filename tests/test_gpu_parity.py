@@ -1450,10 +1450,8 @@ def test_full_size_properties_1080p(eng):
 def test_full_size_properties_32x4k(eng):
     """BASELINE config 3 at full size (32 x 4K, native resolution: the bench workload),
     through properties that need no oracle: the eight column strips of a multi-GPU run
-    compose the single-GPU mosaic bit for bit; the optional two-stream schedule (interior
-    pixels and the blur's work list on a side stream) equals the single-stream one bit for
-    bit; the interior shortcut moves no pixel by more than one level; a constant scene
-    comes back constant."""
+    compose the single-GPU mosaic bit for bit; the interior shortcut moves no pixel by more
+    than one level; a constant scene comes back constant."""
     import torch
     from pano360_amd import dist as pdist
     from pano360_amd import engine, synth
@@ -1468,14 +1466,6 @@ def test_full_size_properties_32x4k(eng):
     plan = engine.Plan(shapes, rots, intrs, True, 10 ** 9)
     assert plan.shape == (2474, 13760)
     whole, fl, valid, _ = eng.stitch(frames, plan, "multiband", 5, want_float=True)
-    # two streams: interior collapse and the blur's work list on the side stream
-    eng.overlap_interior = eng.overlap_prepare = True
-    try:
-        two, _, _, _ = eng.stitch(frames, engine.Plan(shapes, rots, intrs, True, 10 ** 9),
-                                  "multiband", 5)
-    finally:
-        eng.overlap_interior = eng.overlap_prepare = False
-    assert torch.equal(whole, two)
     # column strips of 8 ranks, run one after the other on this GPU
     strips, bounds = pdist.emulate_on_one_device(eng, imgs, rots, intrs, 5, 8)
     assert bounds[-1] == plan.shape[1] and torch.equal(strips, whole)
@@ -1484,7 +1474,7 @@ def test_full_size_properties_32x4k(eng):
                                      "multiband", 5, want_float=True, shortcut=False)
     assert (whole.int() - full.int()).abs().max().item() <= 1
     assert (fl - fl_full).abs().max().item() <= 1e-6
-    del strips, full, fl_full, two
+    del strips, full, fl_full
     # a constant scene telescopes back to the constant
     const = eng.upload_frames([np.full((h, w, 3), (200, 90, 30), np.uint8)] * 2)
     flat, fl2, valid2, _ = eng.stitch(
@@ -1664,23 +1654,6 @@ def test_native_stitch_equals_the_launch_by_launch_path(oracle):
     assert torch.equal(target.cpu(), whole)
     with pytest.raises(_lib.PanoError, match="not resident"):
         native.multiband_fused(native.upload_frames(imgs[:2]), plan, 5, frame_ids=[0, 1])
-
-
-@pytest.mark.parametrize("mode", [1, 2])
-def test_side_stream_modes_give_the_same_mosaic(eng, mode):
-    """``Engine(side_stream=...)``: 2 = the blur's tile flags and work list are made on a second
-    stream beside the warp, 1 = also the interior pixels of the collapse.  Same mosaic bit for
-    bit as on one stream, stitch after stitch (the streams are ordered by events only)."""
-    import torch
-    from pano360_amd import engine, synth
-    imgs, rots, intrs = synth.make_scene(10, 640, 360, sweep_deg=120.0, jitter=0.01, seed=77, kind="A")
-    shapes = [im.shape[:2] for im in imgs]
-    frames = eng.upload_frames(imgs)
-    want = eng.stitch(frames, engine.Plan(shapes, rots, intrs, True, 10 ** 9), "multiband", 5)[0]
-    other = engine.Engine(side_stream=mode)
-    for _ in range(12):
-        got = other.stitch(frames, engine.Plan(shapes, rots, intrs, True, 10 ** 9), "multiband", 5)[0]
-        assert torch.equal(got, want)
 
 
 @pytest.mark.parametrize("step_deg", [0.9, 0.02])

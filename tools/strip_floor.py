@@ -9,6 +9,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
+from pano360_amd import _lib  # noqa: E402
 from pano360_amd import dist as pdist  # noqa: E402
 from pano360_amd import engine, synth  # noqa: E402
 
@@ -129,7 +130,7 @@ print("Plan alone: %.3f ms" % ((time.perf_counter() - t0) / 50 * 1e3))
 if JSON_OUT:
     # appended to: one visit runs this tool once per (lanes, plan) setting
     entry = dict(config=name, lanes=len(LANES), plan_cached=os.environ.get("PANO_PLAN_CACHED", "0") != "0",
-                 stitch_async=os.environ.get("PANO_STITCH_ASYNC", "0"),
+                 stitch_async=LANES[0][0].get_option(_lib.OPT_STITCH_ASYNC),
                  trusted_layouts=bool(LANES[0][0].trust_layout),
                  kept_geometry=bool(LANES[0][0].keep_geometry), balanced_strips=BALANCE,
                  what="rank r of world N emulated on ONE GPU: its strip's kernels only, no exchange; "
