@@ -9,9 +9,11 @@ defaults the reference uses (nfeatures 0, 3 octave layers, contrast threshold
 0.04, edge threshold 10, sigma 1.6, first octave -1):
 
   findScaleSpaceExtrema  26-neighbour extrema of the DoG layers above the
-                         pre-threshold floor(0.5 * 0.04 / 3 * 255)
+                         pre-threshold floor(0.5 * 0.04 / 3 * 255) (3 = the layers per
+                         octave: ``n_layers`` of the functions below, 3 by default)
   adjustLocalExtrema     up to 5 Newton steps on the 3-D quadratic fit (float
-                         LU solve), contrast and edge-response tests
+                         LU solve, pivots below 10 FLT_EPSILON singular, as sift.hip), contrast
+                         and edge-response tests
   calcOrientationHist    36-bin gradient histogram, radius round(4.5 s),
                          Gaussian 1.5 s, [1 4 6 4 1]/16 smoothing, peaks >= 80 %
                          with parabolic refinement -> one keypoint per peak
@@ -53,6 +55,7 @@ DESCR_SCL_FCTR = 3.0
 DESCR_MAG_THR = 0.2
 INT_DESCR_FCTR = 512.0
 FLT_EPSILON = np.finfo(np.float32).eps
+PIVOT_EPS = F(FLT_EPSILON * 10)
 
 _P1 = F(0.9997878412794807 * (180 / np.pi))
 _P3 = F(-0.3258083974640975 * (180 / np.pi))
@@ -83,12 +86,14 @@ def cv_round(v):
 
 def _solve3(h, b):
     """Matx33f::solve(b, DECOMP_LU): float32 Gaussian elimination with partial
-    pivoting; None when singular."""
+    pivoting; None when singular - a pivot below 10 FLT_EPSILON.  The threshold of
+    ``hal::LU32f`` and of sift.hip's solve3: the project's choice, as OpenCV itself sends a
+    single right-hand side to Cramer's rule (tests/sift_f64.py gives the reasoning)."""
     a = np.array(h, dtype=F).copy()
     x = np.array(b, dtype=F).copy()
     for i in range(3):
         k = i + int(np.argmax(np.abs(a[i:, i])))
-        if np.abs(a[k, i]) < FLT_EPSILON:
+        if np.abs(a[k, i]) < PIVOT_EPS:
             return None
         if k != i:
             a[[i, k]] = a[[k, i]]
@@ -107,8 +112,8 @@ def _solve3(h, b):
     return out
 
 
-def adjust_local_extrema(dog_oct, octv, layer, r, c):
-    """sift.cpp adjustLocalExtrema.  dog_oct: list of the octave's DoG planes.
+def adjust_local_extrema(dog_oct, octv, layer, r, c, n_layers=N_LAYERS):
+    """sift.cpp adjustLocalExtrema.  dog_oct: list of the octave's DoG planes (n_layers + 2).
     Returns None or a dict with the refined keypoint (octave coordinates kept)."""
     img_scale = F(1.0 / 255.0)
     deriv_scale = F(img_scale * F(0.5))
@@ -146,7 +151,7 @@ def adjust_local_extrema(dog_oct, octv, layer, r, c):
         c += cv_round(xc)
         r += cv_round(xr)
         layer += cv_round(xi)
-        if (layer < 1 or layer > N_LAYERS or c < IMG_BORDER or c >= cols - IMG_BORDER
+        if (layer < 1 or layer > n_layers or c < IMG_BORDER or c >= cols - IMG_BORDER
                 or r < IMG_BORDER or r >= rows - IMG_BORDER):
             return None
     img, prv, nxt = dog_oct[layer], dog_oct[layer - 1], dog_oct[layer + 1]
@@ -155,7 +160,7 @@ def adjust_local_extrema(dog_oct, octv, layer, r, c):
                    (nxt[r, c] - prv[r, c]) * deriv_scale], F)
     t = F(dd[0] * xc + dd[1] * xr + dd[2] * xi)
     contr = F(img[r, c] * img_scale + t * F(0.5))
-    if abs(contr) * N_LAYERS < CONTRAST_THR:
+    if abs(contr) * n_layers < CONTRAST_THR:
         return None
     v2 = F(img[r, c] * 2)
     dxx = F((img[r, c + 1] + img[r, c - 1] - v2) * second_deriv_scale)
@@ -169,7 +174,7 @@ def adjust_local_extrema(dog_oct, octv, layer, r, c):
     scale = float(1 << octv)
     return dict(x=F((c + xc) * scale), y=F((r + xr) * scale),
                 octave=octv + (layer << 8) + (cv_round((xi + F(0.5)) * 255) << 16),
-                size=F(SIGMA * np.power(F(2.0), F((layer + xi) / N_LAYERS)) * scale * 2),
+                size=F(SIGMA * np.power(F(2.0), F((layer + xi) / n_layers)) * scale * 2),
                 response=F(abs(contr)), r=r, c=c, layer=layer, octv=octv)
 
 
@@ -214,18 +219,18 @@ def orientation_hist(img, c, r, radius, sigma):
     return hist, F(hist.max())
 
 
-def find_keypoints(gauss, dog):
-    """findScaleSpaceExtrema over a pyramid (lists over octaves of lists of planes).
-    Returns keypoints in detection order, coordinates of the doubled base image."""
-    threshold = int(np.floor(0.5 * CONTRAST_THR / N_LAYERS * 255))
-    n = ORI_HIST_BINS
+def find_keypoints(gauss, dog, n_layers=N_LAYERS):
+    """findScaleSpaceExtrema over a pyramid (lists over octaves of lists of planes) of
+    ``n_layers`` layers per octave.  Returns keypoints in detection order, coordinates of
+    the doubled base image."""
+    threshold = int(np.floor(0.5 * CONTRAST_THR / n_layers * 255))
     out = []
     for o, dog_oct in enumerate(dog):
         rows, cols = dog_oct[0].shape
         if rows <= 2 * IMG_BORDER or cols <= 2 * IMG_BORDER:
             continue
-        stack = np.stack(dog_oct)                                   # [5][rows][cols]
-        for i in range(1, N_LAYERS + 1):
+        stack = np.stack(dog_oct)                                   # [n_layers + 2][rows][cols]
+        for i in range(1, n_layers + 1):
             cur = stack[i, IMG_BORDER:rows - IMG_BORDER, IMG_BORDER:cols - IMG_BORDER]
             neigh = [stack[i + dl, IMG_BORDER + dy:rows - IMG_BORDER + dy,
                            IMG_BORDER + dx:cols - IMG_BORDER + dx]
@@ -233,23 +238,34 @@ def find_keypoints(gauss, dog):
             hi, lo = np.maximum.reduce(neigh), np.minimum.reduce(neigh)
             cand = (np.abs(cur) > threshold) & (((cur > 0) & (cur >= hi)) | ((cur < 0) & (cur <= lo)))
             for rr, cc in zip(*np.nonzero(cand)):
-                kp = adjust_local_extrema(dog_oct, o, i, int(rr) + IMG_BORDER, int(cc) + IMG_BORDER)
+                kp = adjust_local_extrema(dog_oct, o, i, int(rr) + IMG_BORDER, int(cc) + IMG_BORDER,
+                                          n_layers)
                 if kp is None:
                     continue
-                scl = F(kp["size"] * F(0.5) / (1 << o))
-                hist, omax = orientation_hist(gauss[o][kp["layer"]], kp["c"], kp["r"],
-                                              cv_round(ORI_RADIUS * scl), F(ORI_SIG_FCTR * scl))
-                mag_thr = F(omax * F(ORI_PEAK_RATIO))
-                for j in range(n):
-                    left, right = (j - 1) % n, (j + 1) % n
-                    if hist[j] > hist[left] and hist[j] > hist[right] and hist[j] >= mag_thr:
-                        b = F(j + F(0.5) * (hist[left] - hist[right])
-                              / (hist[left] - 2 * hist[j] + hist[right]))
-                        b = b + n if b < 0 else (b - n if b >= n else b)
-                        angle = F(360.0 - F(360.0 / n) * b)
-                        if abs(angle - 360.0) < FLT_EPSILON:
-                            angle = F(0.0)
-                        out.append(dict(kp, angle=angle))
+                for angle in orientation_angles(gauss[o][kp["layer"]], kp["r"], kp["c"],
+                                                kp["size"], o):
+                    out.append(dict(kp, angle=angle))
+    return out
+
+
+def orientation_angles(img, r, c, size, octv):
+    """The angles of a refined keypoint (octave coordinates r, c; its size) on its Gaussian
+    layer: calcOrientationHist, the peaks of at least 80 % of the maximum, the parabola."""
+    n = ORI_HIST_BINS
+    scl = F(F(size) * F(0.5) / (1 << octv))
+    hist, omax = orientation_hist(img, c, r, cv_round(ORI_RADIUS * scl), F(ORI_SIG_FCTR * scl))
+    mag_thr = F(omax * F(ORI_PEAK_RATIO))
+    out = []
+    for j in range(n):
+        left, right = (j - 1) % n, (j + 1) % n
+        if hist[j] > hist[left] and hist[j] > hist[right] and hist[j] >= mag_thr:
+            b = F(j + F(0.5) * (hist[left] - hist[right])
+                  / (hist[left] - 2 * hist[j] + hist[right]))
+            b = b + n if b < 0 else (b - n if b >= n else b)
+            angle = F(360.0 - F(360.0 / n) * b)
+            if abs(angle - 360.0) < FLT_EPSILON:
+                angle = F(0.0)
+            out.append(angle)
     return out
 
 
@@ -359,10 +375,11 @@ def descriptor(img, ptx, pty, ori, scl):
     return np.clip(np.rint(dst * scale), 0, 255).astype(F)      # saturate_cast<uchar>, kept as float
 
 
-def detect_and_compute(gauss, dog):
-    """SIFT::detectAndCompute on a prebuilt pyramid (first octave -1).  Returns
-    (keypoints as dicts with x, y, size, angle, response, octave; descriptors [K][128])."""
-    kps = sort_unique(find_keypoints(gauss, dog))
+def detect_and_compute(gauss, dog, n_layers=N_LAYERS):
+    """SIFT::detectAndCompute on a prebuilt pyramid (first octave -1) of ``n_layers`` layers per
+    octave.  Returns (keypoints as dicts with x, y, size, angle, response, octave; descriptors
+    [K][128])."""
+    kps = sort_unique(find_keypoints(gauss, dog, n_layers))
     first_octave = -1
     final = []
     for k in kps:

@@ -106,7 +106,9 @@ __device__ __forceinline__ void wave_sync() {
 }
 #define SIFT_WAVES 4                     // waves (keypoints in flight) per workgroup
 
-// Matx33f::solve(b, DECOMP_LU): float Gaussian elimination with partial pivoting
+// Matx33f::solve(b, DECOMP_LU) restated as float Gaussian elimination with partial pivoting and
+// hal::LU32f's pivot threshold (the project's choice: OpenCV sends a single right-hand side to
+// Cramer's rule, singular only at det == 0; tests/sift_f64.py)
 __device__ __forceinline__ bool solve3(float a[3][3], float b[3], float x[3]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

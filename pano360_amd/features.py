@@ -154,7 +154,9 @@ def sift_pyramid_device(frame, n_octaves=None, sigma=SIFT_SIGMA, layers=SIFT_LAY
     [layers+3][h][w] / [layers+2][h][w] (index them like lists of planes).
     One native call (``pano_scale_space``) queues every launch of the frame; one launch per
     layer (``scale_step_kernel``) blurs layer i-1 into layer i - both passes, the row-pass
-    image staying in LDS - and writes the DoG layer i-1 from the same tile."""
+    image staying in LDS - and writes the DoG layer i-1 from the same tile.
+    ``layers`` = 2 is refused (``PanoError``): its last step needs a 37-tap aperture
+    (sigma 4.53), and ``pano_scale_step`` takes apertures up to 33."""
     import torch
     eng = eng or _eng.engine()
     h, w = (int(v) for v in frame.shape[:2])
@@ -459,7 +461,9 @@ def sift_detect_async(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
     candidate and keypoint counts stay on the device (``n_dev`` of ``pano_sift_sort_unique`` /
     ``pano_sift_describe``), so consecutive frames follow each other on the GPU.  (With a wait
     for every counter a 4K frame took 12.4 ms for 7.1 ms of kernels.)  ``pyramid`` =
-    (gauss, dog) device stacks replaces the scale space of ``frame``."""
+    (gauss, dog) device stacks replaces the scale space of ``frame``; its layers per octave
+    (DoG depth - 2, ``sift_pyramid_device(layers=...)``) are searched, ``ValueError`` if the
+    octaves do not agree on them."""
     import torch
     eng = eng or _eng.engine()
     lib = eng.lib
@@ -472,20 +476,31 @@ def sift_detect_async(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
         return _pipeline_for(eng, h, w, max_keypoints).detect(frame.contiguous())
     gauss, dog = pyramid
     dev = eng.device
-    dims_host = np.array([v for g in gauss for v in g.shape[1:]], np.int32)
-    gptr_host = np.array([g.data_ptr() for g in gauss], np.int64)
-    dims = eng.to_device(dims_host).view(torch.int32)
+    # the layers per octave are the pyramid's: DoG depth - 2 (sift_pyramid_device(layers=...))
+    n_layers = int(dog[0].shape[0]) - 2
+    if n_layers < 1 or len(gauss) != len(dog) or any(
+            int(d.shape[0]) != n_layers + 2 or int(g.shape[0]) != n_layers + 3
+            for g, d in zip(gauss, dog)):
+        raise ValueError("sift_detect_async: the pyramid's octaves must hold n + 3 Gaussian and "
+                         "n + 2 DoG layers, the same n in every octave")
+    # 256 entries each, zeros beyond the pyramid, as SiftPipeline._slot builds them: a record
+    # whose octave byte is not this pyramid's finds an empty plane and samples nothing
+    dims_host = np.zeros((256, 2), np.int32)
+    dims_host[:len(gauss)] = [tuple(g.shape[1:]) for g in gauss]
+    gptr_host = np.zeros(256, np.int64)
+    gptr_host[:len(gauss)] = [g.data_ptr() for g in gauss]
+    dims = eng.to_device(dims_host.reshape(-1)).view(torch.int32)
     gptr = eng.to_device(gptr_host).view(torch.int64)
     cands = torch.empty(max_keypoints * 32, dtype=torch.uint8, device=dev)
     kpts = torch.empty(max_keypoints * 32, dtype=torch.uint8, device=dev)
     counts = torch.zeros(3, dtype=torch.int32, device=dev)    # candidates, keypoints, kept
     for o, diff in enumerate(dog):
         _, oh, ow = diff.shape
-        _lib.check(lib.pano_sift_extrema(eng.ctx(), _eng._ptr(diff), oh, ow, o, SIFT_LAYERS,
+        _lib.check(lib.pano_sift_extrema(eng.ctx(), _eng._ptr(diff), oh, ow, o, n_layers,
                                          SIFT_CONTRAST, SIFT_EDGE, SIFT_SIGMA, _eng._ptr(cands),
                                          _eng._ptr(counts[0:]), max_keypoints),
                    "pano_sift_extrema")
-    _lib.check(lib.pano_sift_orient(eng.ctx(), _eng._ptr(gptr), _eng._ptr(dims), SIFT_LAYERS,
+    _lib.check(lib.pano_sift_orient(eng.ctx(), _eng._ptr(gptr), _eng._ptr(dims), n_layers,
                                     _eng._ptr(cands), _eng._ptr(counts[0:]), max_keypoints,
                                     _eng._ptr(kpts), _eng._ptr(counts[1:]), max_keypoints),
                "pano_sift_orient")

@@ -1266,10 +1266,10 @@ def test_sift_pipeline_graph_replay_equals_launch_by_launch(eng):
     """``features.SiftPipeline`` - one native call per frame (``pano_sift_detect``), captured into
     a HIP graph the second time a workspace is used and replayed afterwards - against the entry
     points called one by one from Python (``sift_pyramid_device`` + ``sift_detect_async`` on that
-    pyramid): the scale space bit for bit, the keypoints bit for bit in position, size, response and
-    octave (angles and descriptors to the summation order of their LDS atomics, as between any two
-    runs).  Three frames go round two workspaces four times: every workspace sees a launch-by-launch
-    frame, a captured one and replays; then once more with graphs switched off."""
+    pyramid): the scale space, the keypoints and the descriptors bit for bit (the histograms are
+    integer fixed-point sums, independent of their atomics' order).  Three frames go round two
+    workspaces four times: every workspace sees a launch-by-launch frame, a captured one and
+    replays; then once more with graphs switched off."""
     import torch
     from pano360_amd import _lib, engine, features, synth
     w, h = 320, 200

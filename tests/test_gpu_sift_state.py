@@ -4,7 +4,8 @@ rings of ``features.SiftPipeline`` and the engine's ring of pinned counters.  He
 on one engine, in an order that grows the extrema list after graphs were captured, and results are
 taken late or kept while later frames go through the same ring.  Every detection is compared with
 the same frame detected launch by launch (``OPT_SIFT_GRAPH`` = 0) on an engine of its own
-(tests/sift_reference.py: keypoints bit for bit, angles and descriptors to their atomics' order)."""
+(tests/sift_reference.py: keypoints, angles and descriptors bit for bit - the histograms are sums
+of integer fixed-point votes, independent of the atomics' order)."""
 import os
 import sys
 
