@@ -57,6 +57,7 @@ extern "C" {
 #define PANO_EINVAL (-1)   /* bad argument (shape, null pointer, limits)   */
 #define PANO_EHIP (-2)     /* a HIP runtime call failed                    */
 #define PANO_ELIMIT (-3)   /* size beyond a compiled-in limit              */
+#define PANO_ESOLVE (-4)   /* an iterative solve hit its cap or broke down */
 
 #define PANO_MAX_TAPS 129      /* largest Gaussian aperture (sigma <= 16)  */
 #define PANO_MAX_LEVELS 8      /* n_levels of multiband_blend              */
@@ -540,6 +541,41 @@ int pano_u8_to_f32(pano_ctx *ctx, const uint8_t *src, size_t n, float *dst);
 int pano_laplacian_mix(pano_ctx *ctx, const float *la, const float *lb, const void *gm, size_t n,
                        int is_f64, void *out);
 int pano_clip_u8(pano_ctx *ctx, const void *src, size_t n, int is_f64, uint8_t *dst);
+
+/* Poisson (seamless cloning) blend of two uint8 images          blend.py:143-203
+ * (blend.poisson_blend: per channel the sparse system A sol = b, one unknown per pixel, and
+ * target = np.array(np.clip(sol, 0, 255), uint8).)  The reference factorises A; this call
+ * iterates BiCGStab in float64 on the pixel grid and builds no matrix (csrc/poisson.hip).
+ *   src, tgt   dev uint8 [h][w][c] interleaved, c <= 4; tgt is overwritten at the mask pixels
+ *   mask       dev uint8 [h][w], nonzero = a pixel to solve (the reference's img_mask != 0)
+ * The system, with i = y w + x, N = h w, "flat neighbours" n in {i-1, i+1, i-w, i+w} kept when
+ * 0 <= n < N (so a row's last pixel and the next row's first are neighbours), as the
+ * reference's spdiags calls with their zeroed slots make it (poisson_matrix, :143-172):
+ *   b    outside the mask tgt[i]; inside 4 src[i] - src[n] over the flat neighbours whose
+ *        COLUMN is not w-1: nobody reads the last column, and a last-column pixel reads only
+ *        i-1 and i+1.
+ *   A    identity rows outside the mask; a mask row is 4 on the diagonal and -1 at the flat
+ *        neighbours, without i+1 when x == w-2 and without i-1 when x == 0.  A pixel at
+ *        x == w-1 keeps i+1 (a wrap link) and both vertical neighbours.  Not symmetric.
+ * Solver: x0 = tgt, unpreconditioned BiCGStab (the diagonal is constant on the mask, Jacobi
+ * scaling changes nothing), every vector, dot product and scalar float64, scalars and flags in
+ * device memory, all channels in the same launches, a converged channel frozen.  A channel
+ * stops when ||r||_2 <= rtol ||b||_2 with r the recurrence's residual and b the whole right-hand
+ * side, identity rows included.  The host queues PANO_POISSON_CHUNK iterations at a time and
+ * reads the channels' flags back once per chunk.  Sums have a fixed order (per lane, xor
+ * butterfly per wave, waves in order, blocks' partials in order; no atomics): the same input
+ * gives the same bits.
+ *   rtol, max_iters   the stopping threshold and the iteration cap (per channel)
+ *   solution   dev double [c][h][w] or NULL: the float64 solution, every pixel
+ *   iters, resid   HOST int32 [c] / double [c] or NULL: iterations used and the final
+ *              ||r|| / ||b|| per channel, also written when the call fails
+ * Returns PANO_ESOLVE when a channel reaches max_iters unconverged or BiCGStab breaks down
+ * (rho, omega or (rhat, v) at zero, a scalar that is not finite); tgt is then untouched.  The
+ * call waits for the stream (the readbacks); scratch is the context's and grows on demand. */
+#define PANO_POISSON_CHUNK 32
+int pano_poisson_blend(pano_ctx *ctx, const uint8_t *src, uint8_t *tgt, const uint8_t *mask,
+                       int h, int w, int c, double rtol, int max_iters, double *solution,
+                       int32_t *iters, double *resid);
 
 /* cv2.resize(im, None, fx=1/shrink, fy=1/shrink) on a uint8 image   stitcher.py:419-420
  * (INTER_LINEAR, OpenCV's 8-bit fixed-point path restated; parity unpinned).

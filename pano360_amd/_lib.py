@@ -79,6 +79,7 @@ class StitchArgs(C.Structure):
 
 
 EINVAL = -1     # PANO_EINVAL
+ESOLVE = -4     # PANO_ESOLVE: pano_poisson_blend did not converge (cap or breakdown)
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
 
 
@@ -157,6 +158,7 @@ _SIGNATURES = {
     "pano_u8_to_f32": (_i, [_vp, _vp, C.c_size_t, _vp]),
     "pano_laplacian_mix": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, _i, _vp]),
     "pano_clip_u8": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
+    "pano_poisson_blend": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
     "pano_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "pano_sift_extrema": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _vp,
                                _vp, _i]),

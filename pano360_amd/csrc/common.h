@@ -170,6 +170,10 @@ struct pano_ctx {
     // and its pinned host copy (what the call returns)
     uint8_t *enc_dev, *enc_out, *enc_host;
     size_t enc_dev_cap, enc_out_cap, enc_host_cap;
+    // pano_poisson_blend (poisson.hip): the solver's vectors, partial sums and per-channel
+    // scalars, and the pinned host copy of those scalars (the convergence readback)
+    uint8_t *poisson_dev, *poisson_host;
+    size_t poisson_cap;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);
