@@ -577,6 +577,72 @@ int pano_poisson_blend(pano_ctx *ctx, const uint8_t *src, uint8_t *tgt, const ui
                        int h, int w, int c, double rtol, int max_iters, double *solution,
                        int32_t *iters, double *resid);
 
+/* The overlap seam: blend.graph_cut of the reference             blend.py:56-100
+ * (not a min-cut but a two-marker priority flood: cells leave a heap of (-difference, colour,
+ * x, y) smallest first and hand their colour to their unlabelled 4-neighbours), in three calls
+ * (csrc/graphcut.hip), and blend.alpha_blend (blend.py:48-53).
+ *
+ * pano_seam_levels   the priorities ("levels") of the flood, higher first: per pixel
+ *     max over channels |img1 - img2|, -1 where a fourth channel is 0 in either image, cropped
+ *     to a multiple of shrink and reduced by the MINIMUM over shrink x shrink cells ->
+ *     level dev int16 [h / shrink][w / shrink], -1 .. 255.  img1, img2: dev [h][w][c]
+ *     interleaved, c <= 4, of one dtype (PANO_SEAM_*), holding integers 0 .. 255; *bad (dev
+ *     int32, zeroed by the call) becomes 1 when a value is not one.  PANO_SEAM_U8 restates what
+ *     the reference's uint8 arithmetic does: the difference wraps (3 - 5 = 254), and so does
+ *     the heap key -difference (-0 = 0, -d = 256 - d), which orders the differences 0, 255,
+ *     254, .. 1; the level is therefore 255 for a pooled difference of 0 and d - 1 otherwise
+ *     (c == 4 is refused for uint8: the reference cannot store its -1 there).
+ * pano_seam_flood    labels dev int8 [rows][cols] from the levels.  Presets (blend.py:74-80):
+ *     columns [0, border) and the seed column `border` are -1, the seed column cols - border
+ *     and columns (cols - border, cols) are +1; border >= 2, cols >= 2 border + 1.  The heap's
+ *     order is a pure function of the data and the labels depend only on the order of the
+ *     CLASSES (level descending, colour -1 before +1): while (d, c) is the smallest class
+ *     waiting, every entry the flood creates has colour c and those of a level >= d sort before
+ *     everything of the other colour.  So for d = 255 .. -1 and c = -1, +1 the call labels with c
+ *     every connected component of unlabelled cells of level >= d that touches a c-labelled
+ *     cell - at most 514 closures, each a data-parallel fill, bit-identical to the heap loop.
+ *     A closure alternates row and column passes; a pass spreads c over every maximal run of
+ *     open cells that holds a cell with a c neighbour (a 64-cell ballot per wave, carries
+ *     between a line's chunks), until a pass labels nothing.  Levels that do not occur are
+ *     skipped; a class without a frontier costs the one pass that finds none.
+ *     path 0: by size, 1: resident - the grid and a one-cell wall live in the LDS of ONE
+ *     1024-thread workgroup (two bytes a cell, (rows + 2)(cols + 2) <= PANO_SEAM_RESIDENT_CELLS),
+ *     which runs every class without leaving the kernel; 2: tiled - 64 x 64 tiles with a
+ *     one-cell halo flood to their own fixed point in LDS and write back, one launch per round,
+ *     a class ends with the round in which no tile changed; the class and the "changed" word
+ *     live in device memory and the host reads one word per PANO_SEAM_BATCH queued rounds.
+ *     A cell only ever goes from 0 to the colour of the running class, so the races between
+ *     waves (and tiles) are benign: no atomics, the same bits on every run.
+ *     stats (optional, dev int32 [4]): classes that labelled a cell, passes (resident) or
+ *     rounds (tiled) that labelled one, the most of them in one class, the path taken.
+ * pano_seam_mask     cv2.resize of the float32 plane (labels == -1) to [h][w], INTER_LINEAR,
+ *     times 255, truncated to uint8 (blend.py:99-100).  OpenCV's float path restated (parity
+ *     unpinned: a build that fuses the multiply-add can differ by one grey level where a value
+ *     sits within an ulp of an integer): xtab / ytab dev int32 [w][4] / [h][4] = (first tap,
+ *     second tap, bits of the float32 weight of the first, of the second), built by the host;
+ *     s0 a0 + s1 a1 along x, then r0 b0 + r1 b1 along y, one rounding per operation.
+ * pano_alpha_blend   (img1 mask + img2 (1 - mask)) truncated to uint8: two products and one sum,
+ *     unfused, in NumPy's promoted type (float64, or float32 when the mask is float32 and the
+ *     images are uint8, int16 or float32); 1 - mask in the mask's own type.  img1, img2 as
+ *     for pano_seam_levels (any values), mask dev float32 / float64 read at
+ *     y mask_sy + x mask_sx + k mask_sc (0 = broadcast), out dev uint8 [h][w][c]. */
+#define PANO_SEAM_U8 0
+#define PANO_SEAM_I16 1
+#define PANO_SEAM_I32 2
+#define PANO_SEAM_F32 3
+#define PANO_SEAM_F64 4
+#define PANO_SEAM_RESIDENT_CELLS 81408
+#define PANO_SEAM_BATCH 64
+int pano_seam_levels(pano_ctx *ctx, const void *img1, const void *img2, int dtype, int h, int w,
+                     int c, int shrink, int16_t *level, int32_t *bad);
+int pano_seam_flood(pano_ctx *ctx, const int16_t *level, int rows, int cols, int border,
+                    int path, int8_t *labels, int32_t *stats);
+int pano_seam_mask(pano_ctx *ctx, const int8_t *labels, int rows, int cols,
+                   const int32_t *xtab, const int32_t *ytab, uint8_t *mask, int h, int w);
+int pano_alpha_blend(pano_ctx *ctx, const void *img1, const void *img2, int dtype,
+                     const void *mask, int mask_f64, int64_t mask_sy, int64_t mask_sx,
+                     int64_t mask_sc, int h, int w, int c, uint8_t *out);
+
 /* cv2.resize(im, None, fx=1/shrink, fy=1/shrink) on a uint8 image   stitcher.py:419-420
  * (INTER_LINEAR, OpenCV's 8-bit fixed-point path restated; parity unpinned).
  * xtab / ytab: dev int32 [ow][4] / [oh][4] = (first tap, second tap, coefficient of

@@ -80,6 +80,9 @@ class StitchArgs(C.Structure):
 
 EINVAL = -1     # PANO_EINVAL
 ESOLVE = -4     # PANO_ESOLVE: pano_poisson_blend did not converge (cap or breakdown)
+# pano_seam_levels' dtype codes, the resident flood's capacity in cells (wall included)
+SEAM_DTYPES = {"uint8": 0, "int16": 1, "int32": 2, "float32": 3, "float64": 4}
+SEAM_RESIDENT_CELLS = 81408
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
 
 
@@ -159,6 +162,11 @@ _SIGNATURES = {
     "pano_laplacian_mix": (_i, [_vp, _vp, _vp, _vp, C.c_size_t, _i, _vp]),
     "pano_clip_u8": (_i, [_vp, _vp, C.c_size_t, _i, _vp]),
     "pano_poisson_blend": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp]),
+    "pano_seam_levels": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pano_seam_flood": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "pano_seam_mask": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i]),
+    "pano_alpha_blend": (_i, [_vp, _vp, _vp, _i, _vp, _i, C.c_int64, C.c_int64, C.c_int64, _i, _i,
+                              _i, _vp]),
     "pano_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "pano_sift_extrema": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _vp,
                                _vp, _i]),

@@ -106,6 +106,8 @@ extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     if (ctx->enc_host) (void)hipHostFree(ctx->enc_host);
     if (ctx->poisson_dev) (void)hipFree(ctx->poisson_dev);
     if (ctx->poisson_host) (void)hipHostFree(ctx->poisson_host);
+    if (ctx->seam_dev) (void)hipFree(ctx->seam_dev);
+    if (ctx->seam_host) (void)hipHostFree(ctx->seam_host);
     pano_sift_graphs_free(ctx);
     if (ctx->lay_sum_host) (void)hipHostFree(ctx->lay_sum_host);
     if (ctx->lay_rects_dev) (void)hipFree(ctx->lay_rects_dev);

@@ -174,6 +174,9 @@ struct pano_ctx {
     // scalars, and the pinned host copy of those scalars (the convergence readback)
     uint8_t *poisson_dev, *poisson_host;
     size_t poisson_cap;
+    // pano_seam_flood (graphcut.hip), tiled path: the class being flooded and its "changed" word
+    // (device), and the pinned host word the batches' "done" is read into
+    uint8_t *seam_dev, *seam_host;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);
