@@ -993,6 +993,65 @@ int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pi
                      int subsampling, const uint8_t *qt, void *work, int64_t work_bytes,
                      const uint8_t **stream, int64_t *stream_bytes);
 
+/* PNG output: the scanline filters and a deflate coder            stitcher.py:446-447 (cv2.imwrite)
+ * A PNG cannot be zlib's bytes (its match search is serial); the contract is: the file decodes
+ * to exactly the image's pixels, the same input gives the same bytes on every run, and the file
+ * is about as small as Pillow's.  The host (pano360_amd/png.py) wraps the stream as zlib data
+ * and cuts it into the container's chunks.
+ *
+ * pano_png_filter: the scanlines of an 8-bit RGB PNG, filtered.  Asynchronous on the stream.
+ *   img          dev uint8, pixel (x, y) at img[y * pitch + 3 x], channels R, G, B (flags 0) or
+ *                B, G, R (PANO_PNG_BGR); pitch >= 3 w (a cropped view needs no copy).  The caller
+ *                guarantees (h - 1) * pitch + 3 w readable bytes.
+ *   filtered     dev uint8 [h][1 + 3 w]: per row the filter's number, then the filtered bytes in
+ *                R, G, B order
+ * All five filters at 3 bytes per pixel: bytes left of the row and the row above row 0 count as
+ * 0, Average is (left + up) >> 1, Paeth breaks ties in the order left, up, upper left.  Per row
+ * the filter with the smallest sum of the filtered bytes' absolute values as signed 8-bit
+ * wins, the first minimum in the order 0 .. 4.  One workgroup per row, every candidate from the
+ * unfiltered neighbours: rows are independent.
+ *
+ * pano_deflate: a raw deflate stream (RFC 1951) of a device byte buffer, and its Adler-32.
+ *   data, n      dev bytes, 0 <= n < PANO_DEFLATE_MAX_BYTES (2^34)
+ *   work         dev scratch of pano_deflate_work_bytes(n) bytes (0: bad size)
+ *   *stream, *stream_bytes   out: the stream, in pinned host memory the context owns, valid
+ *                until its next pano_deflate or its destruction
+ *   *adler       out: Adler-32 of data
+ * The stream is one dynamic-Huffman block per PANO_DEFLATE_CHUNK input bytes (n = 0: one empty
+ * block), concatenated bit by bit without alignment, BFINAL on the last.  Stages:
+ *   1. runs: maximal runs of equal bytes over the whole buffer.  A run's first byte is a
+ *      literal; the rest is matches of length 3 .. 258 at distance 1, a leftover of 1 - 2 bytes
+ *      literals.  Tokens are cut at chunk borders; a match may reach the byte before its chunk,
+ *      never before byte 0.  One workgroup per chunk holds it in LDS; a thread finds the run
+ *      starts of its 64 bytes as a mask, two scans give it the starts around them.
+ *   2. per chunk: literal/length and distance histograms by integer LDS atomics (order-free);
+ *      code lengths limited to 15 bits, the code-length alphabet to 7, both optimal under the
+ *      limit (package-merge, see pano_deflate_lengths); the lengths run-length coded with the
+ *      16 / 17 / 18 repeat codes, HCLEN order; the dynamic-block header; the chunk's bit count;
+ *      Adler-32 partial sums (a, b) of the chunk.
+ *   3. an exclusive scan of the bit counts into int64 bit offsets (a stream may pass 2^31
+ *      bits).  The call waits for the total, and combines the Adler partials in order.
+ *   4. emission, LSB first, canonical codes: a thread writes its tokens' bits at their offset,
+ *      words wholly inside its range stored, its first and last word atomicOr'ed into the
+ *      zeroed stream (integer, disjoint bits: order-free); the header likewise.
+ * Then the stream is copied to the host and the call waits for that.  Not capturable.
+ *
+ * pano_deflate_lengths: the length-limited code builder as a stage of its own.
+ *   freq         dev uint32 [n_sym], their sum below 2^32;  lengths  dev uint8 [n_sym]
+ *   n_sym        1 .. 288, at most 2^max_bits;  max_bits  1 .. 15
+ * Zero frequency <=> length 0; one used symbol gets length 1; otherwise the lengths minimise
+ * sum freq * length under the limit and their Kraft sum is exactly 1.  Asynchronous. */
+#define PANO_PNG_BGR 1
+#define PANO_DEFLATE_CHUNK 65536
+#define PANO_DEFLATE_MAX_BYTES ((int64_t)1 << 34)
+int pano_png_filter(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch, int flags,
+                    uint8_t *filtered);
+size_t pano_deflate_work_bytes(int64_t n);
+int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void *work, int64_t work_bytes,
+                 const uint8_t **stream, int64_t *stream_bytes, uint32_t *adler);
+int pano_deflate_lengths(pano_ctx *ctx, const uint32_t *freq, int n_sym, int max_bits,
+                         uint8_t *lengths);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

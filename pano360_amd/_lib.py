@@ -187,6 +187,11 @@ _SIGNATURES = {
     "pano_jpeg_encode_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_jpeg_encode": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _vp, _vp, C.c_int64,
                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "pano_png_filter": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _vp]),
+    "pano_deflate_work_bytes": (C.c_size_t, [C.c_int64]),
+    "pano_deflate": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_void_p),
+                         C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]),
+    "pano_deflate_lengths": (_i, [_vp, _vp, _i, _i, _vp]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -45,6 +45,7 @@ extern "C" int pano_ctx_create(int device, void *stream, pano_ctx **out) {
     // kernels whose tiles need more than the default 64 KiB of LDS (per device, idempotent)
     if (int rc = pano_blur_mfma_opt_in()) return rc;
     if (int rc = pano_blur_valu_opt_in()) return rc;
+    if (int rc = pano_deflate_opt_in()) return rc;
     pano_ctx *ctx = new pano_ctx();
     ctx->device = device;
     ctx->stream = (hipStream_t)stream;
@@ -104,6 +105,8 @@ extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     if (ctx->enc_dev) (void)hipFree(ctx->enc_dev);
     if (ctx->enc_out) (void)hipFree(ctx->enc_out);
     if (ctx->enc_host) (void)hipHostFree(ctx->enc_host);
+    if (ctx->png_dev) (void)hipFree(ctx->png_dev);
+    if (ctx->png_host) (void)hipHostFree(ctx->png_host);
     if (ctx->poisson_dev) (void)hipFree(ctx->poisson_dev);
     if (ctx->poisson_host) (void)hipHostFree(ctx->poisson_host);
     if (ctx->seam_dev) (void)hipFree(ctx->seam_dev);
@@ -276,7 +279,8 @@ static const char *const g_kernel_names[] = {
     "jpeg_destuff_kernel", "jpeg_scan_kernel", "jpeg_intervals_kernel", "jpeg_huff_sync_kernel",
     "jpeg_huff_write_kernel", "jpeg_dc_kernel", "jpeg_idct_kernel", "jpeg_pixels_kernel",
     "jpeg_enc_blocks_kernel", "jpeg_enc_count_kernel", "jpeg_enc_scan_kernel", "jpeg_enc_emit_kernel",
-    "jpeg_enc_stuff_kernel"};
+    "jpeg_enc_stuff_kernel", "png_filter_kernel", "deflate_code_kernel", "deflate_scan_kernel",
+    "deflate_emit_kernel", "deflate_lengths_kernel"};
 static_assert(sizeof(g_kernel_names) / sizeof(g_kernel_names[0]) == PK_COUNT,
               "one name per PanoKernelId, in enum order");
 

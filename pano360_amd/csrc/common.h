@@ -85,6 +85,11 @@ enum PanoKernelId {
     PK_JPEG_ENC_SCAN,
     PK_JPEG_ENC_EMIT,
     PK_JPEG_ENC_STUFF,
+    PK_PNG_FILTER,
+    PK_DEFLATE_CODE,
+    PK_DEFLATE_SCAN,
+    PK_DEFLATE_EMIT,
+    PK_DEFLATE_LENGTHS,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------
@@ -177,6 +182,10 @@ struct pano_ctx {
     // pano_seam_flood (graphcut.hip), tiled path: the class being flooded and its "changed" word
     // (device), and the pinned host word the batches' "done" is read into
     uint8_t *seam_dev, *seam_host;
+    // pano_deflate (png_enc.hip): the zeroed stream the emission ORs into, and its pinned host
+    // copy (what the call returns)
+    uint8_t *png_dev, *png_host;
+    size_t png_dev_cap, png_host_cap;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);
@@ -228,6 +237,7 @@ int pano_tiles_blur_mfma(pano_ctx *ctx, const pano_patch *table, int n, int max_
                          uint8_t *warp_need);
 int pano_blur_mfma_opt_in(void);
 int pano_blur_valu_opt_in(void);
+int pano_deflate_opt_in(void);                     // png_enc.hip
 static inline bool pano_blur_uses_mfma(const pano_ctx *ctx) {
     return ctx->opt[PANO_OPT_BLUR_KERNEL] == PANO_BLUR_MFMA;
 }

@@ -413,16 +413,21 @@ def main(argv=None):
 
 def _save(path, dev_mosaic, rect, mosaic):
     """Write the mosaic as Pillow's ``save(path)`` would.  A JPEG of a device mosaic is
-    encoded on the device at Pillow's defaults (``jpeg.encode_device``: the same bytes); every
-    other format, and the host mosaic of a custom blender, goes through Pillow."""
+    encoded on the device at Pillow's defaults (``jpeg.encode_device``: the same bytes), a PNG
+    of one by ``png.encode_device`` (the same pixels, not zlib's bytes); every other format,
+    and the host mosaic of a custom blender, goes through Pillow."""
     from . import jpeg as _jpeg
-    if path.lower().endswith(_jpeg.JPEG_EXTENSIONS) and hasattr(dev_mosaic, "cpu"):
+    from . import png as _png
+    lower = path.lower()
+    codec = _jpeg if lower.endswith(_jpeg.JPEG_EXTENSIONS) else \
+        _png if lower.endswith(_png.PNG_EXTENSIONS) else None
+    if codec is not None and hasattr(dev_mosaic, "cpu"):
         view = dev_mosaic
         if rect is not None:
             y0, x0, h, w = rect
             view = dev_mosaic[y0:y0 + h, x0:x0 + w, :]
-        if _jpeg.encodable(view):
-            data = _jpeg.encode_device(view, order="bgr")
+        if codec.encodable(view):
+            data = codec.encode_device(view, order="bgr")
             with open(path, "wb") as fid:
                 fid.write(data)
             return
