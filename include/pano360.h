@@ -1052,6 +1052,66 @@ int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void *work, int6
 int pano_deflate_lengths(pano_ctx *ctx, const uint32_t *freq, int n_sym, int max_bits,
                          uint8_t *lengths);
 
+/* The MSOP detector                                  features.py:27-156, 204-212 (csrc/msop.hip)
+ * OpenCV's cornerHarris / Sobel / warpPerspective restated, parity unpinned; the arithmetic is
+ * stated in NumPy in tests/msop_model.py and in DESIGN 5i.  All planes dense float [h][w].
+ * pano_harris      features.py:140: cornerHarris(gray, blockSize 2, ksize 3, k) -> out, fused
+ *     (Sobel / 8, REFLECT_101; the products; the 2 x 2 box sum, anchor (1, 1);
+ *     a c - b b - k (a + c)(a + c) left to right).
+ * pano_sobel       features.py:112-113: the unscaled Sobel 3 x 3 planes dx, dy (REFLECT_101).
+ * pano_msop_smooth features.py:20-24, 112-114: cv2.GaussianBlur of one plane (REFLECT_101) in the
+ *     operation order of OpenCV's sepFilter2D, multiply and add rounded separately - row pass
+ *     s = k[0] x[0]; s += k[j] x[j] ascending, column pass s = k[r] y[0];
+ *     s += k[r + j] (y[+j] + y[-j]) - so that g_x, g_y and the blurred plane equal the model
+ *     bit for bit (pano_blur_plane's FMA sums differ in the last bit).  taps: HOST float [ntaps]
+ *     (cv::getGaussianKernel), ntaps odd, at most PANO_MSOP_SMOOTH_TAPS; tmp, dst dev [h][w];
+ *     dst may be src.
+ * pano_msop_candidates  features.py:142: the pixels >= their 8 neighbours, compacted in row-major
+ *     order: keys (order-preserving uint32 of the response, -0 = +0), pos (y w + x), both dev
+ *     [h w]; *count dev.  work: pano_msop_candidates_work_bytes bytes.
+ * pano_msop_cut    features.py:143-146: one stable ascending sort of the n candidates (equal
+ *     responses stay in row-major order) and the last `keep` of them as points dev int32
+ *     [keep][2] = (row, col), weakest first.  work: pano_msop_cut_work_bytes(n) bytes.
+ * pano_ssc_probe   features.py:71-89: ONE greedy walk of ssc over points dev int32 [n][2] in
+ *     order, for the grid of one width: cgr = width / 2, a point's cell is
+ *     (floor(p[1] / cgr), floor(p[0] / cgr)) in double - the reference's swap - in a grid of
+ *     (n_cell_rows + 1) x (n_cell_cols + 1) cells; a point whose cell is uncovered is taken and
+ *     covers the cells within `reach` of its own, clipped.  sel dev int32 [n]: the indices taken,
+ *     in order; *count dev.  One wave walks 64 points a step.  path PANO_SSC_AUTO: by size,
+ *     PANO_SSC_ONCHIP: the coverage bitmap in LDS (at most PANO_SSC_ONCHIP_CELLS cells),
+ *     PANO_SSC_GLOBAL: in work, pano_ssc_probe_work_bytes bytes (may be NULL on the on-chip
+ *     path).  A point outside the grid is never taken.  The scalar search around the probes
+ *     (features.py:36-69, 91-97) is the host's.
+ * pano_msop_describe  features.py:116-128 for the n points points[sel[i]] (sel NULL: points[i]),
+ *     one wave each: theta = atan2f(gx, gy) at the point; the 8 x 8 tile of `blurred` turned by
+ *     theta (x = cs (u - 4) + sn (v - 4) + col, y = -sn (u - 4) + cs (v - 4) + row in double,
+ *     cs = (float)cos((double)theta); 5-bit fixed-point bilinear taps, constant border 0);
+ *     (t - mean) / (std + 1e-8) with NumPy's pairwise float32 sums.  Out, all dev: points_out
+ *     double [n][4] = (scale row, scale col, theta, scale), theta float [n], tiles float [n][64]
+ *     (each optional), desc float [n][64]. */
+#define PANO_SSC_AUTO 0
+#define PANO_SSC_ONCHIP 1
+#define PANO_SSC_GLOBAL 2
+#define PANO_SSC_ONCHIP_CELLS 524288
+#define PANO_MSOP_SMOOTH_TAPS 15
+int pano_harris(pano_ctx *ctx, const float *gray, int h, int w, float k, float *out);
+int pano_sobel(pano_ctx *ctx, const float *gray, int h, int w, float *dx, float *dy);
+int pano_msop_smooth(pano_ctx *ctx, const float *src, int h, int w, const float *taps, int ntaps,
+                     float *tmp, float *dst);
+size_t pano_msop_candidates_work_bytes(int h, int w);
+int pano_msop_candidates(pano_ctx *ctx, const float *hrs, int h, int w, void *work,
+                         uint32_t *keys, uint32_t *pos, int *count);
+size_t pano_msop_cut_work_bytes(int n);
+int pano_msop_cut(pano_ctx *ctx, const uint32_t *keys, const uint32_t *pos, int n, int keep,
+                  int w, void *work, int32_t *points);
+size_t pano_ssc_probe_work_bytes(int n_cell_rows, int n_cell_cols);
+int pano_ssc_probe(pano_ctx *ctx, const int32_t *points, int n, double cgr, int n_cell_rows,
+                   int n_cell_cols, int reach, int path, void *work, int32_t *sel,
+                   int32_t *count);
+int pano_msop_describe(pano_ctx *ctx, const float *gx, const float *gy, const float *blurred,
+                       int h, int w, const int32_t *points, const int32_t *sel, int n, int scale,
+                       double *points_out, float *theta, float *tiles, float *desc);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -83,6 +83,9 @@ ESOLVE = -4     # PANO_ESOLVE: pano_poisson_blend did not converge (cap or break
 # pano_seam_levels' dtype codes, the resident flood's capacity in cells (wall included)
 SEAM_DTYPES = {"uint8": 0, "int16": 1, "int32": 2, "float32": 3, "float64": 4}
 SEAM_RESIDENT_CELLS = 81408
+# pano_ssc_probe's paths, the on-chip bitmap's capacity in cells
+SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
+SSC_ONCHIP_CELLS = 524288
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
 
 
@@ -192,6 +195,17 @@ _SIGNATURES = {
     "pano_deflate": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_void_p),
                          C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]),
     "pano_deflate_lengths": (_i, [_vp, _vp, _i, _i, _vp]),
+    "pano_harris": (_i, [_vp, _vp, _i, _i, C.c_float, _vp]),
+    "pano_sobel": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "pano_msop_smooth": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "pano_msop_candidates_work_bytes": (C.c_size_t, [_i, _i]),
+    "pano_msop_candidates": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "pano_msop_cut_work_bytes": (C.c_size_t, [_i]),
+    "pano_msop_cut": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "pano_ssc_probe_work_bytes": (C.c_size_t, [_i, _i]),
+    "pano_ssc_probe": (_i, [_vp, _vp, _i, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "pano_msop_describe": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
+                                _vp]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -23,6 +23,12 @@ restated, parity unpinned.
   ``cv2.RANSAC``: ``pano_hom_ransac`` scores every hypothesis of every pair of a batch on the
   GPU and refits the winner (a Hartley-normalised DLT; no adaptive stop, no Levenberg-Marquardt
   polish - include/pano360.h pins the contract).
+* ``msop_detect`` / ``msop_detector`` / ``ssc`` / ``rot_mat`` - features.py:27-156, 204-212: the
+  MSOP detector.  Harris corners (``pano_harris``), the cut of the strongest local maxima
+  (``pano_msop_candidates``, ``pano_msop_cut``), the greedy walks of the adaptive non-maximal
+  suppression (``pano_ssc_probe``; the scalar binary search around them stays in Python) and the
+  oriented 8 x 8 descriptors (``pano_sobel``, ``pano_msop_smooth``, ``pano_msop_describe``).
+  OpenCV's part restated, parity unpinned; DESIGN 5i states the arithmetic.
 * ``matching(imgs)``, ``_match_hom``, ``_reverse`` - features.py:235-283: detection, 2-NN, the
   ratio test (``pano_match_pack``) and one RANSAC launch over every pair; ``main`` writes the
   ``matches_<name>.npz`` the reference's stitcher.py:423-428 loads.
@@ -30,6 +36,7 @@ restated, parity unpinned.
 import argparse
 import ctypes as C
 import logging
+import math
 import os
 import time
 from collections import defaultdict
@@ -553,6 +560,240 @@ def sift_pyramid(img, n_octaves=None):
     return to_np(gauss), to_np(dog)
 
 
+# ------------------------------------------------------------------ MSOP detector
+DSIZE = 8                   # features.py:16: descriptor size
+MSOP_MAX_FEAT = (5000, 100, 25, 10)
+HARRIS_K = 0.04             # features.py:140
+SSC_PATHS = {"auto": _lib.SSC_AUTO, "onchip": _lib.SSC_ONCHIP, "global": _lib.SSC_GLOBAL}
+
+
+def rot_mat(theta, pp_):
+    """The 3 x 3 float32 matrix that turns by ``theta`` about the origin and then moves the origin
+    to the point ``pp_`` = (row, col), in (x, y) order (features.py:102-106)."""
+    row, col = pp_[0], pp_[1]
+    turn = np.eye(3, dtype=np.float32)
+    turn[0, 0] = turn[1, 1] = np.cos(theta)
+    turn[0, 1] = np.sin(theta)
+    turn[1, 0] = -turn[0, 1]
+    turn[0, 2], turn[1, 2] = col, row
+    return turn
+
+
+class _SscSearch:
+    """The scalar control of ``ssc``'s binary search (features.py:36-69, 91-97) in Python float64
+    and Python ``round``: ``next_width()`` is the width to probe, None once the search is over;
+    ``report(count)`` takes what the probe selected.  ``im_size`` is handed (H, W) and, as in the
+    reference, its first entry is used as the number of columns."""
+
+    def __init__(self, n_keypoints, im_size, n_points, tol=0.1):
+        n_points = int(n_points)
+        if n_points == 1:
+            raise ValueError("ssc: n_points = 1 divides by zero in the search range")
+        self.cols, self.rows = int(im_size[0]), int(im_size[1])
+        # The widest suppression square that still lets n_points squares into the image (Bailo et
+        # al., "Efficient adaptive non-maximal suppression algorithms for homogeneous spatial
+        # keypoint distribution") is a root of  qa w^2 + qb w + qc = 0.  The coefficients and the
+        # discriminant are exact integers; float64 enters at the square root.
+        qa = n_points - 1
+        qb = 2 * (self.rows + self.cols + 2 * n_points)
+        qc = 4 * (n_points + self.cols - self.rows * self.cols)
+        spread = math.sqrt(qb * qb - 4 * qa * qc)
+        self.high = max(-round((qb + spread) / (2 * qa)), -round((qb - spread) / (2 * qa)))
+        self.low = math.floor(math.sqrt(n_keypoints / n_points))
+        slack = n_points * tol
+        self.k_min, self.k_max = round(n_points - slack), round(n_points + slack)
+        self.prev_width, self.complete, self.width = -1, False, None
+
+    def next_width(self):
+        if self.complete or self.low > self.high:
+            return None
+        width = self.low + (self.high - self.low) / 2
+        if width == self.prev_width:
+            return None
+        self.width = width
+        return width
+
+    def grid(self):
+        """(cgr, cell rows - 1, cell columns - 1, reach in cells) for the width to probe."""
+        cgr = self.width / 2
+        return (cgr, int(math.floor(self.rows / cgr)), int(math.floor(self.cols / cgr)),
+                int(math.floor(self.width / cgr)))
+
+    def report(self, count):
+        if self.k_min <= count <= self.k_max:
+            self.complete = True
+        elif count < self.k_min:
+            self.high = self.width - 1
+        else:
+            self.low = self.width + 1
+        self.prev_width = self.width
+
+
+def ssc_device(points, im_size, n_points, tol=0.1, eng=None, path="auto"):
+    """``ssc`` over device points int32 [n][2] = (row, col): (indices int32 [n] on the device,
+    how many of them count), the selection of the last probe that ran, in walk order.  Every
+    probe is one launch of ``pano_ssc_probe`` and one 4-byte readback of its count; the search
+    between them is ``_SscSearch``.  ``path``: "auto" | "onchip" | "global" (the coverage bitmap in
+    LDS or in device memory, sized from the probe's width)."""
+    import torch
+    eng = eng or _eng.engine()
+    n = int(points.shape[0])
+    search = _SscSearch(n, im_size, n_points, tol)
+    sel = torch.empty(max(n, 1), dtype=torch.int32, device=eng.device)
+    count = torch.zeros(1, dtype=torch.int32, device=eng.device)
+    taken = 0
+    while search.next_width() is not None:
+        cgr, ncr, ncc, reach = search.grid()
+        onchip = (ncr + 1) * (ncc + 1) <= _lib.SSC_ONCHIP_CELLS
+        work = None
+        if path == "global" or (path == "auto" and not onchip):
+            work = torch.empty(int(eng.lib.pano_ssc_probe_work_bytes(ncr, ncc)), dtype=torch.uint8,
+                               device=eng.device)
+        _lib.check(eng.lib.pano_ssc_probe(eng.ctx(), _eng._ptr(points), n, C.c_double(cgr), ncr,
+                                          ncc, reach, SSC_PATHS[path], _eng._ptr(work),
+                                          _eng._ptr(sel), _eng._ptr(count)), "pano_ssc_probe")
+        taken = int(count.cpu()[0])
+        search.report(taken)
+    return sel, taken
+
+
+def ssc(keypoints, im_size, n_points, tol=0.1, path="auto"):
+    """Fast adaptive non-maximal suppression (features.py:27-99) of host keypoints, integer
+    ``(kpt[0], kpt[1])`` inside ``im_size``; returns the list of the keypoints selected.  The
+    walks run on the GPU (``ssc_device``)."""
+    import torch
+    kps = np.asarray(keypoints)
+    if len(kps) == 0:
+        return []
+    pts = np.asarray(kps[:, :2], np.int64)
+    if not np.array_equal(pts, np.asarray(kps[:, :2], np.float64)):
+        raise ValueError("ssc: keypoints must hold integer positions")
+    if pts.min() < 0 or pts[:, 0].max() >= im_size[0] or pts[:, 1].max() >= im_size[1]:
+        raise ValueError("ssc: a keypoint lies outside im_size")
+    eng = _eng.engine()
+    dev = torch.from_numpy(np.ascontiguousarray(pts, np.int32)).to(eng.device)
+    sel, taken = ssc_device(dev, im_size, n_points, tol, eng, path)
+    return [keypoints[i] for i in sel[:taken].cpu().numpy()]
+
+
+_SMOOTH_TAPS = {}
+
+
+def _msop_smooth(eng, plane, sigma, tmp, out):
+    """``gaussian_filter(plane, sigma)`` (features.py:20-24) of a dense device plane into ``out``
+    by ``pano_msop_smooth``: OpenCV's operation order without FMA, where ``pano_blur_plane``
+    spends one FMA per tap and differs in the last bit."""
+    h, w = (int(v) for v in plane.shape)
+    if sigma not in _SMOOTH_TAPS:
+        ksz = max(int((sigma - 0.35) / 0.15), 1)
+        ksz += not ksz % 2
+        _SMOOTH_TAPS[sigma] = np.ascontiguousarray(_eng.gaussian_taps(ksz, sigma))
+    taps = _SMOOTH_TAPS[sigma]
+    _lib.check(eng.lib.pano_msop_smooth(eng.ctx(), _eng._ptr(plane), h, w, taps.ctypes.data,
+                                        len(taps), _eng._ptr(tmp), _eng._ptr(out)),
+               "pano_msop_smooth")
+    return out
+
+
+def msop_detect_device(frame, max_feat=MSOP_MAX_FEAT, eng=None, want_stages=False):
+    """``msop_detect`` (features.py:133-156) of a uint8 BGR frame on the device: (points float64
+    [N][4] = (scale row, scale col, theta, scale), descs float32 [N][64]), both on the device.
+    Per level: ``pano_harris``, ``pano_msop_candidates`` (one readback: their count),
+    ``pano_msop_cut``, ``ssc_device``, ``pano_sobel`` + ``pano_msop_smooth`` for the gradient and the
+    blurred plane, ``pano_msop_describe``, ``pano_pyr_down``.  ``want_stages``: also a list with,
+    per level, a dict of the response ``hrs``, the cut's ``cut`` (row, col), the ``sel`` indices
+    of ``ssc``, ``g_x``, ``g_y``, ``blurred``, ``theta`` and the raw ``tiles``.  ``ValueError``
+    when a level is left without points or asks for a single one (the reference fails there)."""
+    import torch
+    eng = eng or _eng.engine()
+    lib, dev = eng.lib, eng.device
+    frame = frame.contiguous()
+    gray = _Dev(eng).gray(frame)
+    points, descs, stages = [], [], []
+    for lvl, maxf in enumerate(max_feat):
+        maxf = int(maxf)
+        h, w = (int(v) for v in gray.shape)
+        hrs = torch.empty_like(gray)
+        _lib.check(lib.pano_harris(eng.ctx(), _eng._ptr(gray), h, w, C.c_float(HARRIS_K),
+                                   _eng._ptr(hrs)), "pano_harris")
+        keys = torch.empty(h * w, dtype=torch.int32, device=dev)
+        pos = torch.empty(h * w, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        work = torch.empty(int(lib.pano_msop_candidates_work_bytes(h, w)), dtype=torch.uint8,
+                           device=dev)
+        _lib.check(lib.pano_msop_candidates(eng.ctx(), _eng._ptr(hrs), h, w, _eng._ptr(work),
+                                            _eng._ptr(keys), _eng._ptr(pos), _eng._ptr(count)),
+                   "pano_msop_candidates")
+        n_cand = int(count.cpu()[0])
+        keep = min(n_cand, 20 * maxf)
+        if keep == 0:
+            raise ValueError(f"msop_detect: level {lvl} has no candidates")
+        cut = torch.empty((keep, 2), dtype=torch.int32, device=dev)
+        work = torch.empty(int(lib.pano_msop_cut_work_bytes(n_cand)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.pano_msop_cut(eng.ctx(), _eng._ptr(keys), _eng._ptr(pos), n_cand, keep, w,
+                                     _eng._ptr(work), _eng._ptr(cut)), "pano_msop_cut")
+        sel, taken = ssc_device(cut, (h, w), maxf, eng=eng)
+        if taken == 0:
+            raise ValueError(f"msop_detect: ssc left level {lvl} without points")
+        d_x, d_y = torch.empty_like(gray), torch.empty_like(gray)
+        _lib.check(lib.pano_sobel(eng.ctx(), _eng._ptr(gray), h, w, _eng._ptr(d_x),
+                                  _eng._ptr(d_y)), "pano_sobel")
+        tmp = torch.empty_like(gray)
+        g_x = _msop_smooth(eng, d_x, 1.0, tmp, d_x)           # gaussian_filter(.., 1.0): ksize 5
+        g_y = _msop_smooth(eng, d_y, 1.0, tmp, d_y)
+        blurred = _msop_smooth(eng, gray, 2.0, tmp, torch.empty_like(gray))   # ksize 11
+        pts = torch.empty((taken, 4), dtype=torch.float64, device=dev)
+        theta = torch.empty(taken, dtype=torch.float32, device=dev)
+        tiles = torch.empty((taken, DSIZE, DSIZE), dtype=torch.float32, device=dev) \
+            if want_stages else None
+        desc = torch.empty((taken, DSIZE * DSIZE), dtype=torch.float32, device=dev)
+        _lib.check(lib.pano_msop_describe(eng.ctx(), _eng._ptr(g_x), _eng._ptr(g_y),
+                                          _eng._ptr(blurred), h, w, _eng._ptr(cut), _eng._ptr(sel),
+                                          taken, 2 ** lvl, _eng._ptr(pts), _eng._ptr(theta),
+                                          _eng._ptr(tiles), _eng._ptr(desc)), "pano_msop_describe")
+        points.append(pts)
+        descs.append(desc)
+        if want_stages:
+            stages.append({"hrs": hrs, "cut": cut, "sel": sel[:taken], "g_x": g_x, "g_y": g_y,
+                           "blurred": blurred, "theta": theta, "tiles": tiles})
+        if lvl + 1 < len(max_feat):
+            gray = eng.pyr_down(gray)
+    out = (torch.cat(points), torch.cat(descs))
+    return out + (stages,) if want_stages else out
+
+
+def msop_detect(img, max_feat=MSOP_MAX_FEAT):
+    """Extract MSOP features (features.py:133-156): (points float64 [N][4], descs float32
+    [N][64]) on the host."""
+    eng = _eng.engine()
+    frame = eng.upload_frames([img])[0]
+    points, descs = msop_detect_device(frame, max_feat, eng)
+    return points.cpu().numpy(), descs.cpu().numpy()
+
+
+def msop_detector(max_feat=MSOP_MAX_FEAT, eng=None):
+    """Closure, returns a MSOP detector (features.py:204-212): ``_detect(img) -> (keypoints,
+    descriptors [N][64])``.  As there, a keypoint's ``size`` carries theta."""
+    def _detect(img):
+        eng_ = eng if eng is not None else _eng.engine()
+        frame = eng_.upload_frames([img])[0]
+        points, des = msop_detect_device(frame, max_feat, eng_)
+        kp_ = [KeyPoint(p[1], p[0], p[2]) for p in points.cpu().numpy()]
+        return kp_, des.cpu().numpy().reshape(-1, 64)
+
+    return _detect
+
+
+def detector_kwargs(name):
+    """``matching``'s keyword for the command line's ``--detector``: none for "sift" (the
+    default detector stays what it is)."""
+    if name == "sift":
+        return {}
+    if name == "msop":
+        return {"detect": msop_detector()}
+    raise ValueError(f"detector {name!r} (sift or msop)")
+
+
 # ------------------------------------------------------------------ matching
 class DMatch:
     """The fields of ``cv2.DMatch`` the reference reads (features.py:238)."""
@@ -807,15 +1048,19 @@ def _assemble(kpts, found):
 
 def main(argv=None):
     """Script entry point (features.py:300-320): the images of ``--path``, shrunk by half,
-    matched; writes ``matches_<name>.npz``.  Read with Pillow, resized on the device."""
+    matched; writes ``matches_<name>.npz`` (``--detector msop``: ``matches_<name>_msop.npz``).  Read with Pillow, resized on the device."""
     from .stitcher import ingest
     parser = argparse.ArgumentParser(description="Extract features.")
     parser.add_argument("--path", type=str, default="../data/ppwwyyxx/CMU2",
                         help="directory with the images to process.")
+    parser.add_argument("--detector", default="sift", choices=["sift", "msop"],
+                        help="feature detector (msop writes matches_<name>_msop.npz).")
     args = parser.parse_args(argv)
     name = os.path.basename(args.path)
+    if args.detector == "msop":
+        name += "_msop"
     imgs = ingest(args.path, 2)
-    kpts, matches = matching(imgs)
+    kpts, matches = matching(imgs, **detector_kwargs(args.detector))
     np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
     return kpts, matches
 

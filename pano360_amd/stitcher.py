@@ -325,17 +325,19 @@ def idx_to_keypoints(matches, kpts):
             for i, row in table.items()}
 
 
-def _register(path, name, frames, badjust):
+def _register(path, name, frames, badjust, detector="sift"):
     """Cameras for the frames of ``path`` (stitcher.py:423-439): the match file is read if
     present, else ``features.matching`` runs on the device frames and writes it; then
     ``traverse``, whose cameras are pickled with host uint8 BGR images so that the reference
-    CLI reads the cache too.  Returns the cameras with the device frames attached."""
+    CLI reads the cache too.  Returns the cameras with the device frames attached.
+    ``detector`` "msop" matches with ``features.msop_detector()``; ``name`` then carries the
+    ``_msop`` suffix that keeps its caches apart from SIFT's."""
     from . import features
     try:
         arr = np.load(f"matches_{name}.npz", allow_pickle=True)
         kpts, matches = arr["kpts"], arr["matches"]
     except IOError:
-        kpts, matches = features.matching(frames)
+        kpts, matches = features.matching(frames, **features.detector_kwargs(detector))
         np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
     start = time.time()
     regions = _ba.traverse(list(frames), idx_to_keypoints(matches, kpts), badjust=badjust)
@@ -367,9 +369,14 @@ def main(argv=None):
     parser.add_argument("--register", action="store_true",
                         help="without a camera cache, match the images and run bundle "
                              "adjustment (writes matches_<name>.npz and ba_<name>.pkl)")
+    parser.add_argument("--detector", default="sift", choices=["sift", "msop"],
+                        help="feature detector of --register (msop: the caches are named "
+                             "matches_<name>_msop.npz and ba_<name>_msop.pkl).")
     args = parser.parse_args(argv)
 
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
+    if args.detector == "msop":
+        name += "_msop"
     cache = f"ba_{name}.pkl"
     try:
         with open(cache, "rb") as fid:
@@ -392,7 +399,8 @@ def main(argv=None):
             "cameras here (the reference CLI's registration), or produce the camera cache with "
             "the reference (the pickle written at stitcher.py:438-439) and re-run")
     if regions is None:
-        regions = _register(args.path, name, ingest(args.path, args.shrink), args.ba)
+        regions = _register(args.path, name, ingest(args.path, args.shrink), args.ba,
+                            args.detector)
     if any(reg.img is None for reg in regions):
         frames = ingest(args.path, args.shrink) if os.path.isdir(args.path) else []
         if len(frames) != len(regions):
