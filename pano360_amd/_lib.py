@@ -283,6 +283,11 @@ def lib():
     return _lib
 
 
+def _ptr(t):
+    """A tensor's address as a ctypes argument (None stays a null pointer)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def check(status, what):
     if status != 0:
         msg = lib().pano_last_error().decode("utf-8", "replace")

@@ -26,11 +26,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
 from . import engine as _eng
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+def _dtype_name(t):
+    return str(t.dtype).replace("torch.", "")
 
 
 class _Pyr:
@@ -319,7 +320,7 @@ def seam_levels_device(img1, img2, shrink, eng):
     h, w, c = img1.shape
     level = torch.empty((h // shrink, w // shrink), dtype=torch.int16, device=img1.device)
     bad = torch.empty(1, dtype=torch.int32, device=img1.device)
-    code = _lib.SEAM_DTYPES[str(img1.dtype).replace("torch.", "")]
+    code = _lib.SEAM_DTYPES[_dtype_name(img1)]
     _lib.check(eng.lib.pano_seam_levels(eng.ctx(), _ptr(img1), _ptr(img2), code, h, w, c,
                                         int(shrink), _ptr(level), _ptr(bad)), "pano_seam_levels")
     return level, bad
@@ -359,9 +360,8 @@ def graph_cut_device(img1, img2, shrink=5, eng=None, want_labels=False, path=0):
     read back (the domain check), so the call waits for the stream."""
     import torch
     eng = eng or _eng.engine()
-    name = str(img1.dtype).replace("torch.", "")
-    rows, cols, border = _seam_check(img1.shape, img2.shape, name,
-                                     str(img2.dtype).replace("torch.", ""), shrink)
+    name = _dtype_name(img1)
+    rows, cols, border = _seam_check(img1.shape, img2.shape, name, _dtype_name(img2), shrink)
     shrink = int(shrink)
     h, w = img1.shape[:2]
     img1, img2 = img1.contiguous(), img2.contiguous()
@@ -422,7 +422,7 @@ def alpha_blend_device(img1, img2, mask=None, eng=None):
     eng = eng or _eng.engine()
     if img1.dim() != 3 or img1.shape != img2.shape or img1.dtype != img2.dtype:
         raise ValueError("alpha_blend: two H x W x C images of one shape and dtype")
-    name = str(img1.dtype).replace("torch.", "")
+    name = _dtype_name(img1)
     if name not in _SEAM_TYPES:
         raise NotImplementedError(f"alpha_blend: images of {name}")
     h, w, c = img1.shape

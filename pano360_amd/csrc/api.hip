@@ -89,6 +89,24 @@ static void tap_set_free(PanoTapSet &ts) {
     ts.host = nullptr;
 }
 
+static hipError_t buf_free(PanoBuf &b) {
+    const hipError_t e = !b.p ? hipSuccess : b.pinned ? hipHostFree(b.p) : hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    return e;
+}
+
+int pano_buf_reserve(PanoBuf &b, size_t need, bool pinned, size_t slack) {
+    if (need <= b.cap) return PANO_OK;
+    PANO_HIP(buf_free(b));
+    need += slack;
+    void *p = nullptr;
+    if (pinned) PANO_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+    else PANO_HIP(hipMalloc(&p, need));
+    b = PanoBuf{p, need, pinned};
+    return PANO_OK;
+}
+
 extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     if (!ctx) return PANO_OK;
     PANO_HIP(hipSetDevice(ctx->device));
@@ -99,22 +117,8 @@ extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     }
     timing_clear(ctx);
     for (PanoTapSet &ts : ctx->tap_sets) tap_set_free(ts);
-    if (ctx->item_buf) (void)hipFree(ctx->item_buf);
-    if (ctx->item_counter) (void)hipFree(ctx->item_counter);
-    if (ctx->sift_raw) (void)hipFree(ctx->sift_raw);
-    if (ctx->enc_dev) (void)hipFree(ctx->enc_dev);
-    if (ctx->enc_out) (void)hipFree(ctx->enc_out);
-    if (ctx->enc_host) (void)hipHostFree(ctx->enc_host);
-    if (ctx->png_dev) (void)hipFree(ctx->png_dev);
-    if (ctx->png_host) (void)hipHostFree(ctx->png_host);
-    if (ctx->poisson_dev) (void)hipFree(ctx->poisson_dev);
-    if (ctx->poisson_host) (void)hipHostFree(ctx->poisson_host);
-    if (ctx->seam_dev) (void)hipFree(ctx->seam_dev);
-    if (ctx->seam_host) (void)hipHostFree(ctx->seam_host);
+    for (PanoBuf &b : ctx->buf) (void)buf_free(b);
     pano_sift_graphs_free(ctx);
-    if (ctx->lay_sum_host) (void)hipHostFree(ctx->lay_sum_host);
-    if (ctx->lay_rects_dev) (void)hipFree(ctx->lay_rects_dev);
-    if (ctx->lay_have_dev) (void)hipFree(ctx->lay_have_dev);
     if (ctx->side) {
         (void)hipStreamSynchronize(ctx->side);
         (void)hipStreamDestroy(ctx->side);

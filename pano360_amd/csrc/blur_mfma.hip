@@ -48,6 +48,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wave.h"
 
 // The hand-written hazard handling below (s_nop counts behind v_mfma_f32_32x32x16_f16 results
 // read by inline-asm vector instructions, vmcnt values that assume loads and stores retire in
@@ -1898,7 +1899,7 @@ __global__ __launch_bounds__(256) void mb_sort_kernel(const int2 *__restrict__ i
                     }
                 }
                 // one add per wave
-                for (int off = 32; off > 0; off >>= 1) segs += __shfl_xor(segs, off, 64);
+                segs = wave_sum(segs);
                 if (lane == 0 && segs) atomicAdd(&s_segs[c], segs);
             }
         }
@@ -1925,7 +1926,7 @@ __global__ __launch_bounds__(256) void mb_sort_kernel(const int2 *__restrict__ i
                 cnt[e] = (int)((word[e >> 1] >> (16 * (e & 1))) & 0xffffu) * wgs_per_item;
                 total += cnt[e];
             }
-            int seen = total;                                            // inclusive prefix over the group
+            int seen = total;                  // inclusive prefix over the group (16 lanes: not wave.h's)
 #pragma unroll
             for (int off = 1; off < 16; off <<= 1) {
                 const int v = __shfl_up(seen, off, 16);
@@ -2093,6 +2094,13 @@ int pano_tiles_blur_mfma(pano_ctx *ctx, const pano_patch *table, int n, int max_
     return PANO_OK;
 }
 
+// The context's work list: `items` unsorted items, then as many sorted ones and the segment slots.
+static size_t mb_list_bytes(size_t items) { return (items * 2 + MB_SEG_SLOTS + 2) * sizeof(int2); }
+static int2 *mb_sorted_list(const pano_ctx *ctx) {
+    const PanoBuf &list = ctx->buf[BUF_ITEM_LIST];
+    return (int2 *)list.p + (list.cap / sizeof(int2) - MB_SEG_SLOTS - 2) / 2;
+}
+
 int pano_prepare_blur_mfma(pano_ctx *ctx, const pano_patch *table, int n, int max_aw, int max_ah,
                            int W, const uint8_t *interior, uint8_t *tile_flags) {
     const hipStream_t stream = ctx->stream;
@@ -2109,30 +2117,28 @@ int pano_prepare_blur_mfma(pano_ctx *ctx, const pano_patch *table, int n, int ma
     }
     // at most ceil(ntx / 2) pairs per record
     const int cap = n * ceil_div(ntx_max, 2);
-    if (cap > ctx->item_cap) {
-        if (ctx->item_buf) {
-            PANO_HIP(hipStreamSynchronize(stream));          // a queued blur may still read it
-            PANO_HIP(hipFree(ctx->item_buf));
-            ctx->item_buf = nullptr;
-        }
-        ctx->item_cap = cap * 2;
-        PANO_HIP(hipMalloc((void **)&ctx->item_buf,
-                           ((size_t)ctx->item_cap * 2 + MB_SEG_SLOTS + 2) * sizeof(int2)));
+    PanoBuf &list = ctx->buf[BUF_ITEM_LIST], &counter = ctx->buf[BUF_ITEM_COUNTER];
+    if (mb_list_bytes(cap) > list.cap) {                     // grows to twice the items asked for
+        if (list.p) PANO_HIP(hipStreamSynchronize(stream));  // a queued blur may still read it
+        if (int rc = pano_buf_reserve(list, mb_list_bytes(cap), false,
+                                      mb_list_bytes(2 * cap) - mb_list_bytes(cap)))
+            return rc;
     }
-    if (!ctx->item_counter) {
-        PANO_HIP(hipMalloc((void **)&ctx->item_counter, sizeof(int)));
-        PANO_HIP(hipMemsetAsync(ctx->item_counter, 0, sizeof(int), stream));
+    if (!counter.p) {
+        if (int rc = pano_buf_reserve(counter, sizeof(int), false)) return rc;
+        PANO_HIP(hipMemsetAsync(counter.p, 0, sizeof(int), stream));
     }
-    hipLaunchKernelGGL(mb_items_kernel, dim3(n), dim3(256), 0, stream, table, flags, ctx->item_buf,
-                       ctx->item_counter, cap);
+    int2 *const items = (int2 *)list.p;
+    hipLaunchKernelGGL(mb_items_kernel, dim3(n), dim3(256), 0, stream, table, flags, items,
+                       (int *)counter.p, cap);
     PANO_LAUNCH_CHECK("mb_items_kernel");
     // (option PANO_OPT_BLUR_SEG_LEN: a segment length in bands, -1 = no cut, 0 = the estimate's choice)
     const int force_t = ctx->opt[PANO_OPT_BLUR_SEG_LEN];
     // 4 channels (x level groups) workgroups per item
-    hipLaunchKernelGGL(mb_sort_kernel, dim3(1), dim3(256), 0, stream, ctx->item_buf,
-                       ctx->item_counter, cap, mb_sorted_slots(cap), 4,
+    hipLaunchKernelGGL(mb_sort_kernel, dim3(1), dim3(256), 0, stream, items,
+                       (int *)counter.p, cap, mb_sorted_slots(cap), 4,
                        ctx->opt[PANO_OPT_BLUR_SEGMENTS] ? 256 : 0,
-                       ctx->item_buf + ctx->item_cap, table,
+                       mb_sorted_list(ctx), table,
                        ctx->opt[PANO_OPT_BLUR_SEGMENTS] ? (ctx->blur_cm > 0 ? ctx->blur_cm : 3) : 0,
                        force_t);
     PANO_LAUNCH_CHECK("mb_sort_kernel");
@@ -2216,7 +2222,7 @@ static int launch_levels(pano_ctx *ctx, const pano_patch *table, int n, int max_
     }
     const int ntx_max = (max_aw + 62) / 32;
     const int cap = mb_sorted_slots(n * ceil_div(ntx_max, 2));    // slots of the sorted list
-    const int2 *sorted = ctx->item_buf + ctx->item_cap;
+    const int2 *sorted = mb_sorted_list(ctx);
     // dynamic LDS: the largest level group's band, flags and tables
     const int ngroups = ceil_div(cnt, group);
     int lds = 0;

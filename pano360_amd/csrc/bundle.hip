@@ -11,18 +11,13 @@
 // rows are added in wave order.  The assembly kernel then adds the pairs' sums into the dense
 // system in pair order.  Every sum has a fixed order: the same input gives the same bits.
 #include "common.h"
+#include "wave.h"
 
 #define BA_BLOCK 256
 #define BA_WAVES (BA_BLOCK / 64)
 #define BA_TERMS 90          // 21 + 21 + 36 + 12 per pair (include/pano360.h)
 #define BA_TABLE 90          // doubles per pair in the Jacobian table: ten 3 x 3 matrices
 #define ASM_BLOCK 64
-
-__device__ __forceinline__ double ba_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // M p with p = (x, y, 1), left to right as NumPy's dot: (m0 x + m1 y) + m2
 __device__ __forceinline__ void ba_mul_p(const double *__restrict__ M, double x, double y,
@@ -43,7 +38,7 @@ __global__ __launch_bounds__(BA_BLOCK) void ba_residual_kernel(const double *__r
                                                                const int32_t *__restrict__ pairs,
                                                                const double *__restrict__ hom,
                                                                double *__restrict__ ssq) {
-    __shared__ double wave_sum[BA_WAVES];
+    __shared__ double wave_part[BA_WAVES];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int first = pairs[4 * p + 2], count = pairs[4 * p + 3];
     const double *H = hom + 9 * (size_t)p;
@@ -55,13 +50,13 @@ __global__ __launch_bounds__(BA_BLOCK) void ba_residual_kernel(const double *__r
         const double rx = row[0] - t[0] / t[2], ry = row[1] - t[1] / t[2];
         acc += rx * rx + ry * ry;
     }
-    acc = ba_wave_sum(acc);
-    if (lane == 0) wave_sum[wave] = acc;
+    acc = wave_sum(acc);
+    if (lane == 0) wave_part[wave] = acc;
     __syncthreads();
     if (tid == 0) {
-        double s = wave_sum[0];
+        double s = wave_part[0];
 #pragma unroll
-        for (int w = 1; w < BA_WAVES; ++w) s += wave_sum[w];
+        for (int w = 1; w < BA_WAVES; ++w) s += wave_part[w];
         ssq[p] = s;
     }
 }
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(BA_BLOCK) void ba_pair_kernel(const double *__restr
         int k = 0;
 #define BA_PUT(value)                                 \
     do {                                              \
-        const double v_ = ba_wave_sum(value);         \
+        const double v_ = wave_sum(value);            \
         if (lane == 0) acc[wave][k] += v_;            \
         ++k;                                          \
     } while (0)

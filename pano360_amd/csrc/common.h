@@ -117,6 +117,51 @@ struct PanoSiftGraph {               // detect.hip: one captured launch sequence
     uint64_t used;                  // last use (eviction order)
 };
 
+// A buffer the context owns (device memory, or pinned host memory), grown on demand and never
+// shrunk.  A stage that needs one adds an id here and calls pano_buf_reserve; pano_ctx_destroy
+// frees them all.
+struct PanoBuf {
+    void *p;
+    size_t cap;                     // bytes
+    bool pinned;                    // hipHostMalloc rather than hipMalloc
+};
+enum PanoBufId {
+    // matrix-core blur: the work list (unsorted, sorted) and its counter
+    BUF_ITEM_LIST = 0,
+    BUF_ITEM_COUNTER,
+    // pano_stitch_multiband without its host round trip (stitch.hip): the device-side layout's
+    // summary (pinned: the layout kernel writes it, the host reads it), device copies of the patch
+    // rectangles and resident flags
+    BUF_LAY_SUM_HOST,
+    BUF_LAY_RECTS,
+    BUF_LAY_HAVE,
+    // pano_sift_extrema: the list of scale-space extrema between its two kernels (+ its counter)
+    BUF_SIFT_RAW,
+    // pano_jpeg_encode (jpeg_enc.hip): the raw stream and its stuffing scan, the stuffed stream,
+    // and its pinned host copy (what the call returns)
+    BUF_ENC_DEV,
+    BUF_ENC_OUT,
+    BUF_ENC_HOST,
+    // pano_poisson_blend (poisson.hip): the solver's vectors, partial sums and per-channel
+    // scalars, and the pinned host copy of those scalars (the convergence readback)
+    BUF_POISSON_DEV,
+    BUF_POISSON_HOST,
+    // pano_seam_flood (graphcut.hip), tiled path: the class being flooded and its "changed" word
+    // (device), and the pinned host word the batches' "done" is read into
+    BUF_SEAM_DEV,
+    BUF_SEAM_HOST,
+    // pano_deflate (png_enc.hip): the zeroed stream the emission ORs into, and its pinned host
+    // copy (what the call returns)
+    BUF_PNG_DEV,
+    BUF_PNG_HOST,
+    PANO_BUF_COUNT
+};
+// Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it
+// is freed and `need + slack` bytes are allocated, and a failure leaves {nullptr, 0} behind.  The
+// old contents are lost, and NOTHING here waits for queued work that still uses them: a caller
+// whose stream may not be idle synchronises first, and only when `need > b.cap`.
+int pano_buf_reserve(PanoBuf &b, size_t need, bool pinned, size_t slack = 0);
+
 #define GEOM_BUFS 11
 #define STITCH_SIG 13             // stitch.hip: stitch_signature
 struct pano_ctx {
@@ -125,15 +170,12 @@ struct pano_ctx {
     int opt[PANO_OPT_COUNT];
     bool timing_on;
     std::vector<hipEvent_t> t_begin[PK_COUNT], t_end[PK_COUNT];
-    // matrix-core blur: work list (unsorted, sorted), its counter, and whose list / tile
-    // flags the buffers currently hold
-    int2 *item_buf;
-    int *item_counter;
+    PanoBuf buf[PANO_BUF_COUNT];    // (by PanoBufId)
+    // matrix-core blur: whose list / tile flags the work-list buffers currently hold
     int blur_cm;                    // reach (k-steps) of the blur levels the next work list is for; 0 = unknown
-    int item_cap;
     const pano_patch *prepared_table, *flags_table;
     int prepared_n, flags_n;
-    // whose work list item_buf holds (stays when a blur has consumed `prepared_table`; an option
+    // whose work list BUF_ITEM_LIST holds (stays when a blur has consumed `prepared_table`; an option
     // switch or a re-allocation clears it): what a kept-geometry repeat may re-use
     const pano_patch *list_table;
     int list_n;
@@ -144,14 +186,9 @@ struct pano_ctx {
     hipEvent_t ev_regions, ev_upload, ev_fork, ev_join, ev_copy;
     hipStream_t side;               // second stream of pano_stitch_multiband
     bool upload_pending;
-    // pano_stitch_multiband without its host round trip (stitch.hip): the device-side layout's
-    // summary (device / pinned host), device copies of the patch rectangles and resident flags
-    // (and the host values they were made from), and what the previous stitch's layout needed:
-    // the next one's launch bounds
-    LayoutSummary *lay_sum_host;    // pinned: the layout kernel writes it, the host reads it
-    int32_t *lay_rects_dev;
-    uint8_t *lay_have_dev;
-    int lay_cap_n;
+    // pano_stitch_multiband without its host round trip (stitch.hip): the host values the device
+    // copies of the patch rectangles and resident flags were made from, and what the previous
+    // stitch's layout needed: the next one's launch bounds
     std::vector<int32_t> lay_rects_host;
     std::vector<uint8_t> lay_have_host;
     pano_layout lay_prev;
@@ -165,27 +202,9 @@ struct pano_ctx {
     bool geom_valid, in_stitch;
     const void *geom_bufs[GEOM_BUFS];
     int lay_count[2];               // stitches that went through on the device layout / fell back
-    // pano_sift_extrema: the list of scale-space extrema between its two kernels (+ its counter)
-    uint32_t *sift_raw;
-    size_t sift_raw_cap;
     bool sift_capturing;            // pano_sift_detect is capturing a launch sequence (detect.hip)
     // pano_sift_detect: the captured launch sequences, one per set of buffers (detect.hip)
     std::vector<PanoSiftGraph> sift_graphs;
-    // pano_jpeg_encode (jpeg_enc.hip): the raw stream and its stuffing scan, the stuffed stream,
-    // and its pinned host copy (what the call returns)
-    uint8_t *enc_dev, *enc_out, *enc_host;
-    size_t enc_dev_cap, enc_out_cap, enc_host_cap;
-    // pano_poisson_blend (poisson.hip): the solver's vectors, partial sums and per-channel
-    // scalars, and the pinned host copy of those scalars (the convergence readback)
-    uint8_t *poisson_dev, *poisson_host;
-    size_t poisson_cap;
-    // pano_seam_flood (graphcut.hip), tiled path: the class being flooded and its "changed" word
-    // (device), and the pinned host word the batches' "done" is read into
-    uint8_t *seam_dev, *seam_host;
-    // pano_deflate (png_enc.hip): the zeroed stream the emission ORs into, and its pinned host
-    // copy (what the call returns)
-    uint8_t *png_dev, *png_host;
-    size_t png_dev_cap, png_host_cap;
 };
 
 int pano_ctx_enter(pano_ctx *ctx);
@@ -241,7 +260,18 @@ int pano_deflate_opt_in(void);                     // png_enc.hip
 static inline bool pano_blur_uses_mfma(const pano_ctx *ctx) {
     return ctx->opt[PANO_OPT_BLUR_KERNEL] == PANO_BLUR_MFMA;
 }
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ---- integer helpers ---------------------------------------------------------
+// (in the wider of the two types: int for ints, int64_t as soon as one operand is)
+template <class A, class B>
+static inline auto ceil_div(A a, B b) -> decltype(a + b) { return (a + b - 1) / b; }
+// the next multiple of 256 bytes: where a part of a work buffer starts
+template <class T>
+static inline T align_up(T bytes) { return (bytes + 255) / 256 * 256; }
+// the grid of a kernel that loops beyond `cap` workgroups
+static inline dim3 capped_grid(int64_t groups, int64_t cap) {
+    return dim3((unsigned)(groups < cap ? groups : cap));
+}
 
 // ---- device helpers --------------------------------------------------------
 // Scalar-cache view of read-only global memory: loads through this pointer are

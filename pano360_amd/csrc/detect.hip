@@ -43,9 +43,9 @@ static uint64_t detect_key(const pano_ctx *ctx, const pano_sift_args *a, const u
     const float fl[3] = {a->contrast_thr, a->edge_thr, a->sigma};
     h = fnv(h, fl, sizeof(fl));
     const void *ptrs[10] = {frame, a->work, a->gauss_dev, a->dims_dev, a->cands, a->kpts, a->counts,
-                            a->sort_work, a->desc, a->detect ? ctx->sift_raw : nullptr};
+                            a->sort_work, a->desc, a->detect ? ctx->buf[BUF_SIFT_RAW].p : nullptr};
     h = fnv(h, ptrs, sizeof(ptrs));
-    const size_t raw_cap = a->detect ? ctx->sift_raw_cap : 0;
+    const size_t raw_cap = a->detect ? ctx->buf[BUF_SIFT_RAW].cap : 0;
     h = fnv(h, &raw_cap, sizeof(raw_cap));
     h = fnv(h, a->gauss, (size_t)a->n_octaves * sizeof(float *));
     h = fnv(h, a->dog, (size_t)a->n_octaves * sizeof(float *));

@@ -11,6 +11,7 @@
 // the exact mean than the float32 pairwise sum of np.mean the reference runs
 // (the two differ by ~1e-7 relative; the pixel count is exact).
 #include "geom.h"
+#include "wave.h"
 
 static constexpr int OV_TW = 64, OV_TH = 16;     // pixels per workgroup (4 rows per thread)
 
@@ -32,12 +33,6 @@ struct PairMap {
         Y = (long long)rint(fmax(-2147483648.0, fmin(2147483647.0, fY)));
     }
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void overlap_stats_kernel(
     const pano_camera *__restrict__ cams, const pano_pair *__restrict__ pairs, int h, int w,

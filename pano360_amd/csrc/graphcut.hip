@@ -416,11 +416,10 @@ extern "C" int pano_seam_flood(pano_ctx *ctx, const int16_t *level, int rows, in
         PANO_LAUNCH_CHECK("seam_resident_kernel");
         return PANO_OK;
     }
-    if (!ctx->seam_dev) PANO_HIP(hipMalloc((void **)&ctx->seam_dev, sizeof(SeamState)));
-    if (!ctx->seam_host)
-        PANO_HIP(hipHostMalloc((void **)&ctx->seam_host, sizeof(int32_t), hipHostMallocDefault));
-    SeamState *state = (SeamState *)ctx->seam_dev;
-    volatile int32_t *done = (volatile int32_t *)ctx->seam_host;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_SEAM_DEV], sizeof(SeamState), false)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_SEAM_HOST], sizeof(int32_t), true)) return rc;
+    SeamState *state = (SeamState *)ctx->buf[BUF_SEAM_DEV].p;
+    volatile int32_t *done = (volatile int32_t *)ctx->buf[BUF_SEAM_HOST].p;
     const int n = rows * cols;
     PANO_HIP(hipMemsetAsync(state, 0, sizeof(SeamState), s));
     hipLaunchKernelGGL(seam_init_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, level, cols, n,

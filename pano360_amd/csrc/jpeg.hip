@@ -8,6 +8,7 @@
 // of that kind.  The rows are checked against the buffer sizes on the host before anything is
 // queued.
 #include "common.h"
+#include "wave.h"
 
 #define JF PANO_JPEG_FIELDS
 #define JPEG_TAB_BYTES (8 * PANO_JPEG_HUFF_BYTES + 4 * 64 * 2)
@@ -118,21 +119,14 @@ __global__ __launch_bounds__(JPEG_BLOCK) void jpeg_destuff_kernel(JpegBatch B) {
 __global__ __launch_bounds__(SCAN_BLOCK) void jpeg_scan_kernel(const int32_t *__restrict__ in,
                                                                int stride, uint32_t mask, int n,
                                                                int32_t *__restrict__ out) {
-    __shared__ int32_t part[SCAN_BLOCK];
+    __shared__ int32_t waves[SCAN_BLOCK / 64];
     const int t = threadIdx.x;
     const int per = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
     const int a = min(t * per, n), e = min(a + per, n);
     int32_t sum = 0;
     for (int k = a; k < e; ++k) sum += (int32_t)((uint32_t)in[(size_t)k * stride] & mask);
-    part[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < SCAN_BLOCK; off <<= 1) {
-        const int32_t v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int32_t run = part[t] - sum;
+    int32_t total;
+    int32_t run = block_scan_exclusive<SCAN_BLOCK>(sum, waves, total);
     for (int k = a; k < e; ++k) {
         const int32_t v = (int32_t)((uint32_t)in[(size_t)k * stride] & mask);
         out[k] = run;
@@ -616,7 +610,6 @@ __global__ __launch_bounds__(JPEG_BLOCK) void jpeg_pixels_kernel(JpegBatch B) {
 }
 
 // ---- the entry point -------------------------------------------------------------------------------
-static inline int64_t jceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // the rows against the buffers: every offset and size the kernels use, before anything is queued
 static int jpeg_check(const int64_t *desc, int n, int64_t packed_bytes, int64_t work_bytes,
@@ -639,10 +632,10 @@ static int jpeg_check(const int64_t *desc, int n, int64_t packed_bytes, int64_t 
                      (long long)h, (long long)nc);
         const int64_t hm = r[PANO_JD_HMAX], vm = r[PANO_JD_VMAX];
         PANO_REQUIRE(hm >= 1 && hm <= 2 && vm >= 1 && vm <= 2 &&
-                         r[PANO_JD_MCUX] == jceil(w, 8 * hm) && r[PANO_JD_MCUY] == jceil(h, 8 * vm),
+                         r[PANO_JD_MCUX] == ceil_div(w, 8 * hm) && r[PANO_JD_MCUY] == ceil_div(h, 8 * vm),
                      "pano_jpeg_decode: image %d: MCU grid", i);
         const int64_t nmcu = r[PANO_JD_MCUX] * r[PANO_JD_MCUY], ri = r[PANO_JD_RI];
-        PANO_REQUIRE(ri >= 0 && r[PANO_JD_NINT] == (ri ? jceil(nmcu, ri) : 1),
+        PANO_REQUIRE(ri >= 0 && r[PANO_JD_NINT] == (ri ? ceil_div(nmcu, ri) : 1),
                      "pano_jpeg_decode: image %d: restart intervals", i);
         const int64_t bpm = r[PANO_JD_BPM];
         PANO_REQUIRE(bpm >= 1 && bpm <= 16, "pano_jpeg_decode: image %d: %lld blocks per MCU", i,
@@ -674,7 +667,7 @@ static int jpeg_check(const int64_t *desc, int n, int64_t packed_bytes, int64_t 
                          r[PANO_JD_SUB0] == subs && r[PANO_JD_BLK0] == blocks &&
                          r[PANO_JD_PIX0] == pixels,
                      "pano_jpeg_decode: image %d: first indices", i);
-        chunks += len > 0 ? jceil(len, PANO_JPEG_CHUNK) : 1;
+        chunks += len > 0 ? ceil_div(len, PANO_JPEG_CHUNK) : 1;
         ints += r[PANO_JD_NINT];
         subs += len * 8 / PANO_JPEG_SUBSEQ + r[PANO_JD_NINT] + 1;
         blocks += nmcu * bpm;
@@ -706,7 +699,7 @@ static int jpeg_scan(pano_ctx *ctx, hipStream_t s, const int32_t *in, int stride
     return PANO_OK;
 }
 
-static inline dim3 jgrid(int64_t threads) { return dim3((unsigned)jceil(threads, JPEG_BLOCK)); }
+static inline dim3 jgrid(int64_t threads) { return dim3((unsigned)ceil_div(threads, JPEG_BLOCK)); }
 
 extern "C" int pano_jpeg_decode(pano_ctx *ctx, const int64_t *desc, int n, const uint8_t *packed,
                                 int64_t packed_bytes, void *work, int64_t work_bytes,

@@ -7,6 +7,7 @@
 // Blocks are numbered in scan order: MCU by MCU, and inside an MCU the luma blocks row by row,
 // then Cb, then Cr.  The coefficients are kept as int16 [64] per block in zigzag order.
 #include "common.h"
+#include "wave.h"
 
 #define ENC_BLOCK 256
 #define ENC_TILE 32                 // blocks per workgroup of the block kernel (8 threads each)
@@ -280,11 +281,6 @@ __device__ __forceinline__ EncCode enc_lane_code(const EncImage &E, const int16_
     return c;
 }
 
-__device__ __forceinline__ int enc_wave_sum(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- 2. bit counts: one wave per block ------------------------------------------------------------
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_count_kernel(EncImage E,
                                                                    const int16_t *__restrict__ coef,
@@ -292,39 +288,16 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_count_kernel(EncImage E,
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int64_t b = (int64_t)blockIdx.x * ENC_WAVES + wave; b < E.nblocks;
          b += (int64_t)gridDim.x * ENC_WAVES) {
-        const int n = enc_wave_sum(enc_lane_code(E, coef, (int)b, lane).n);
+        const int n = wave_sum(enc_lane_code(E, coef, (int)b, lane).n);
         if (lane == 0) counts[b] = (uint32_t)n;
     }
 }
 
 // ---- 3. exclusive scan of uint32 values into int64 offsets ------------------------------------------
 // local: each workgroup scans a tile of ENC_SCAN_TILE values (its offsets relative to the tile) and
-// writes the tile's sum to part[tile]; parts: one workgroup scans part[0 .. nparts) in place and
-// writes the total to part[nparts].  The offset of value i is out[i] + part[i / ENC_SCAN_TILE].
-__device__ __forceinline__ int64_t enc_block_scan(int64_t v, int64_t *lds_waves, int64_t &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int64_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds_waves[wave] = x;
-    __syncthreads();
-    if (wave == 0) {
-        int64_t s = lane < ENC_SCAN / 64 ? lds_waves[lane] : 0;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y = __shfl_up(s, o, 64);
-            if (lane >= o) s += y;
-        }
-        if (lane < ENC_SCAN / 64) lds_waves[lane] = s;
-    }
-    __syncthreads();
-    total = lds_waves[ENC_SCAN / 64 - 1];
-    const int64_t excl = x - v + (wave ? lds_waves[wave - 1] : 0);
-    __syncthreads();
-    return excl;
-}
-
+// writes the tile's sum to part[tile]; parts: one workgroup (wave.h: scan_exclusive_kernel) scans
+// part[0 .. nparts) in place and writes the total to part[nparts].  The offset of value i is
+// out[i] + part[i / ENC_SCAN_TILE].
 __global__ __launch_bounds__(ENC_SCAN) void jpeg_enc_scan_local_kernel(
     const uint32_t *__restrict__ in, int64_t n, int64_t *__restrict__ out, int64_t *__restrict__ part) {
     __shared__ int64_t waves[ENC_SCAN / 64];
@@ -336,27 +309,12 @@ __global__ __launch_bounds__(ENC_SCAN) void jpeg_enc_scan_local_kernel(
         sum += v[k];
     }
     int64_t total;
-    int64_t run = enc_block_scan(sum, waves, total);
+    int64_t run = block_scan_exclusive<ENC_SCAN>(sum, waves, total);
     for (int k = 0; k < ENC_SCAN_ITEMS; ++k) {
         if (i0 + k < n) out[i0 + k] = run;
         run += v[k];
     }
     if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(ENC_SCAN) void jpeg_enc_scan_parts_kernel(int64_t *__restrict__ part,
-                                                                       int64_t nparts) {
-    __shared__ int64_t waves[ENC_SCAN / 64];
-    int64_t carry = 0;
-    for (int64_t base = 0; base < nparts; base += ENC_SCAN) {
-        const int64_t i = base + threadIdx.x;
-        const int64_t v = i < nparts ? part[i] : 0;
-        int64_t total;
-        const int64_t excl = enc_block_scan(v, waves, total);
-        if (i < nparts) part[i] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) part[nparts] = carry;
 }
 
 __device__ __forceinline__ int64_t enc_offset(const int64_t *off, const int64_t *part, int64_t i) {
@@ -395,11 +353,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_emit_kernel(
         int nbits = 0;
         if (live) {
             const EncCode c = enc_lane_code(E, coef, (int)b, lane);
-            int x = c.n;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(x, o, 64);
-                if (lane >= o) x += y;
-            }
+            const int x = wave_scan_inclusive(c.n);
             b0 = enc_offset(off, part, b);
             nbits = (int)counts[b];
             const int p = (int)(b0 & 31) + x - c.n;
@@ -458,9 +412,6 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_write_kernel(
 }
 
 // ---- the entry points ------------------------------------------------------------------------------
-static inline int64_t eceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t ealign(int64_t a) { return (a + 255) / 256 * 256; }
-
 // the scratch of pano_jpeg_encode: coefficients, bit counts, bit offsets, scan parts
 struct EncWork {
     int64_t coef, counts, offs, parts, bytes;
@@ -468,10 +419,10 @@ struct EncWork {
 static EncWork enc_work(int64_t nblocks) {
     EncWork w;
     w.coef = 0;
-    w.counts = ealign(128 * nblocks);
-    w.offs = w.counts + ealign(4 * nblocks);
-    w.parts = w.offs + ealign(8 * nblocks);
-    w.bytes = w.parts + ealign(8 * (eceil(nblocks, ENC_SCAN_TILE) + 1));
+    w.counts = align_up(128 * nblocks);
+    w.offs = w.counts + align_up(4 * nblocks);
+    w.parts = w.offs + align_up(8 * nblocks);
+    w.bytes = w.parts + align_up(8 * (ceil_div(nblocks, ENC_SCAN_TILE) + 1));
     return w;
 }
 
@@ -483,13 +434,13 @@ static bool enc_geometry(int h, int w, int subsampling, EncImage &E) {
     E.h = h;
     E.hm = subsampling == 0 ? 1 : 2;
     E.vm = subsampling == 2 ? 2 : 1;
-    E.mx = (int)eceil(w, 8 * E.hm);
-    E.my = (int)eceil(h, 8 * E.vm);
+    E.mx = ceil_div(w, 8 * E.hm);
+    E.my = ceil_div(h, 8 * E.vm);
     E.bpm = E.hm * E.vm + 2;
-    E.wib[0] = (int)eceil(w, 8);
-    E.hib[0] = (int)eceil(h, 8);
-    E.wib[1] = (int)eceil(eceil(w, E.hm), 8);
-    E.hib[1] = (int)eceil(eceil(h, E.vm), 8);
+    E.wib[0] = ceil_div(w, 8);
+    E.hib[0] = ceil_div(h, 8);
+    E.wib[1] = ceil_div(ceil_div(w, E.hm), 8);
+    E.hib[1] = ceil_div(ceil_div(h, E.vm), 8);
     E.nblocks = E.mx * E.my * E.bpm;
     return true;
 }
@@ -500,39 +451,22 @@ extern "C" size_t pano_jpeg_encode_work_bytes(int h, int w, int subsampling) {
     return (size_t)enc_work(E.nblocks).bytes;
 }
 
-// grow a context buffer (device or pinned host) to at least `need` bytes; the stream is idle
-static int enc_reserve(uint8_t **buf, size_t *cap, size_t need, bool host) {
-    if (need <= *cap) return PANO_OK;
-    if (*buf) {
-        if (host) PANO_HIP(hipHostFree(*buf));
-        else PANO_HIP(hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-    }
-    need += need / 4;
-    if (host) PANO_HIP(hipHostMalloc((void **)buf, need, hipHostMallocDefault));
-    else PANO_HIP(hipMalloc((void **)buf, need));
-    *cap = need;
-    return PANO_OK;
-}
-
 static int enc_scan(pano_ctx *ctx, hipStream_t s, const uint32_t *in, int64_t n, int64_t *out,
                     int64_t *part) {
-    const int64_t nparts = eceil(n, ENC_SCAN_TILE);
+    const int64_t nparts = ceil_div(n, ENC_SCAN_TILE);
     PANO_TIMED(PK_JPEG_ENC_SCAN, s,
                hipLaunchKernelGGL(jpeg_enc_scan_local_kernel, dim3((unsigned)nparts),
                                   dim3(ENC_SCAN), 0, s, in, n, out, part));
     PANO_LAUNCH_CHECK("jpeg_enc_scan_local_kernel");
     PANO_TIMED(PK_JPEG_ENC_SCAN, s,
-               hipLaunchKernelGGL(jpeg_enc_scan_parts_kernel, dim3(1), dim3(ENC_SCAN), 0, s, part,
-                                  nparts));
-    PANO_LAUNCH_CHECK("jpeg_enc_scan_parts_kernel");
+               hipLaunchKernelGGL((scan_exclusive_kernel<ENC_SCAN, int64_t>), dim3(1), dim3(ENC_SCAN),
+                                  0, s, (const int64_t *)part, nparts, part));
+    PANO_LAUNCH_CHECK("scan_exclusive_kernel");
     return PANO_OK;
 }
 
 static inline dim3 enc_groups(int64_t n, int per) {
-    const int64_t g = eceil(n, per);
-    return dim3((unsigned)(g < ENC_MAX_GROUPS ? g : ENC_MAX_GROUPS));
+    return capped_grid(ceil_div(n, per), ENC_MAX_GROUPS);
 }
 
 extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch,
@@ -563,7 +497,7 @@ extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w,
     int16_t *coef = (int16_t *)(w8 + L.coef);
     uint32_t *counts = (uint32_t *)(w8 + L.counts);
     int64_t *offs = (int64_t *)(w8 + L.offs), *parts = (int64_t *)(w8 + L.parts);
-    const int64_t nb = E.nblocks, nbparts = eceil(nb, ENC_SCAN_TILE);
+    const int64_t nb = E.nblocks, nbparts = ceil_div(nb, ENC_SCAN_TILE);
 
     // 1. blocks, 2. bit counts, 3. their scan; wait for the total
     PANO_TIMED(PK_JPEG_ENC_BLOCKS, s,
@@ -582,14 +516,16 @@ extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w,
                  "pano_jpeg_encode: %lld bits", (long long)total_bits);
 
     // the stream buffer: raw words (whole chunks, zeroed), the chunks' 0xFF counts and offsets
-    const int64_t nbytes = eceil(total_bits, 8), nchunks = eceil(nbytes, ENC_CHUNK);
-    const int64_t raw_bytes = ealign(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
-                  off_at = cnt_at + ealign(4 * nchunks), part_at = off_at + ealign(8 * nchunks),
-                  dev_bytes = part_at + ealign(8 * (eceil(nchunks, ENC_SCAN_TILE) + 1));
-    if (int rc = enc_reserve(&ctx->enc_dev, &ctx->enc_dev_cap, (size_t)dev_bytes, false)) return rc;
-    uint32_t *raw = (uint32_t *)ctx->enc_dev;
-    uint32_t *ccount = (uint32_t *)(ctx->enc_dev + cnt_at);
-    int64_t *coff = (int64_t *)(ctx->enc_dev + off_at), *cpart = (int64_t *)(ctx->enc_dev + part_at);
+    const int64_t nbytes = ceil_div(total_bits, 8), nchunks = ceil_div(nbytes, ENC_CHUNK);
+    const int64_t raw_bytes = align_up(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
+                  off_at = cnt_at + align_up(4 * nchunks), part_at = off_at + align_up(8 * nchunks),
+                  dev_bytes = part_at + align_up(8 * (ceil_div(nchunks, ENC_SCAN_TILE) + 1));
+    // (the context's buffers grow with a quarter to spare; the stream is idle, nothing reads them)
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_DEV], dev_bytes, false, dev_bytes / 4)) return rc;
+    uint8_t *const dev = (uint8_t *)ctx->buf[BUF_ENC_DEV].p;
+    uint32_t *raw = (uint32_t *)dev;
+    uint32_t *ccount = (uint32_t *)(dev + cnt_at);
+    int64_t *coff = (int64_t *)(dev + off_at), *cpart = (int64_t *)(dev + part_at);
     PANO_HIP(hipMemsetAsync(raw, 0, raw_bytes, s));
 
     // 4. emission, 5. stuffing counts and their scan; wait for the stuffed size
@@ -599,27 +535,29 @@ extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w,
                                   (const int64_t *)offs, (const int64_t *)parts, raw));
     PANO_LAUNCH_CHECK("jpeg_enc_emit_kernel");
     PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_stuff_count_kernel, dim3((unsigned)eceil(nchunks, ENC_BLOCK)),
+               hipLaunchKernelGGL(jpeg_enc_stuff_count_kernel, dim3((unsigned)ceil_div(nchunks, ENC_BLOCK)),
                                   dim3(ENC_BLOCK), 0, s, (const uint32_t *)raw, nchunks, ccount));
     PANO_LAUNCH_CHECK("jpeg_enc_stuff_count_kernel");
     if (int rc = enc_scan(ctx, s, ccount, nchunks, coff, cpart)) return rc;
     int64_t ffs = 0;
-    PANO_HIP(hipMemcpyAsync(&ffs, cpart + eceil(nchunks, ENC_SCAN_TILE), 8, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipMemcpyAsync(&ffs, cpart + ceil_div(nchunks, ENC_SCAN_TILE), 8, hipMemcpyDeviceToHost, s));
     PANO_HIP(hipStreamSynchronize(s));
     PANO_REQUIRE(ffs >= 0 && ffs <= nbytes, "pano_jpeg_encode: %lld 0xFF bytes", (long long)ffs);
     const int64_t out_bytes = nbytes + ffs;
-    if (int rc = enc_reserve(&ctx->enc_out, &ctx->enc_out_cap, (size_t)out_bytes, false)) return rc;
-    if (int rc = enc_reserve(&ctx->enc_host, &ctx->enc_host_cap, (size_t)out_bytes, true)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_OUT], out_bytes, false, out_bytes / 4)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], out_bytes, true, out_bytes / 4)) return rc;
+    uint8_t *const out = (uint8_t *)ctx->buf[BUF_ENC_OUT].p;
+    uint8_t *const host = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
     PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_stuff_write_kernel, dim3((unsigned)eceil(nchunks, ENC_BLOCK)),
+               hipLaunchKernelGGL(jpeg_enc_stuff_write_kernel, dim3((unsigned)ceil_div(nchunks, ENC_BLOCK)),
                                   dim3(ENC_BLOCK), 0, s, (const uint8_t *)raw, nbytes, nchunks,
-                                  (const int64_t *)coff, (const int64_t *)cpart, ctx->enc_out));
+                                  (const int64_t *)coff, (const int64_t *)cpart, out));
     PANO_LAUNCH_CHECK("jpeg_enc_stuff_write_kernel");
 
     // the download
-    PANO_HIP(hipMemcpyAsync(ctx->enc_host, ctx->enc_out, out_bytes, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipMemcpyAsync(host, out, out_bytes, hipMemcpyDeviceToHost, s));
     PANO_HIP(hipStreamSynchronize(s));
-    *stream_out = ctx->enc_host;
+    *stream_out = host;
     *stream_bytes = out_bytes;
     return PANO_OK;
 }

@@ -18,6 +18,7 @@
 // candidate list is private to a lane) and streams the train tiles through LDS, shared by the 4 waves
 // of the workgroup and double-buffered.
 #include "common.h"
+#include "wave.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -75,8 +76,7 @@ __global__ __launch_bounds__(256) void knn_norm_kernel(const float *__restrict__
             const float v = src[(size_t)row * d + k] * scale;
             acc = __builtin_fmaf(v, v, acc);
         }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if (lane == 0) {
         norms[row] = row < n ? acc : __builtin_inff();
         if (row < n && maxnorm) atomicMax(maxnorm, __float_as_uint(acc));
@@ -201,9 +201,7 @@ __device__ __forceinline__ float knn_exact(const float *__restrict__ q, const fl
         const float df = q[k] - t[k];
         acc = __builtin_fmaf(df, df, acc);
     }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) acc += __shfl_xor(acc, off);
-    return acc;
+    return wave_sum(acc);
 }
 
 // One wave per query: exact distances of its three candidates, the proof that nothing else
@@ -311,8 +309,6 @@ __global__ __launch_bounds__(256) void knn2_finish_kernel(
     }
 }
 
-static size_t knn_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct KnnWork {
     size_t pq, pt, nq, ntn, cidx, cval, scal, rlist, rkeys, total;
 };
@@ -323,23 +319,23 @@ static KnnWork knn_layout(int nq, int nt, int d) {
     KnnWork w;
     size_t off = 0;
     w.pq = off;
-    off += knn_align(tq * ks * 2 * 64 * sizeof(half8));
+    off += align_up(tq * ks * 2 * 64 * sizeof(half8));
     w.pt = off;
-    off += knn_align(tt * ks * 2 * 64 * sizeof(half8));
+    off += align_up(tt * ks * 2 * 64 * sizeof(half8));
     w.nq = off;
-    off += knn_align(tq * 32 * sizeof(float));
+    off += align_up(tq * 32 * sizeof(float));
     w.ntn = off;
-    off += knn_align(tt * 32 * sizeof(float));
+    off += align_up(tt * 32 * sizeof(float));
     w.cidx = off;
-    off += knn_align((size_t)nq * KNN_KEEP * sizeof(int32_t));
+    off += align_up((size_t)nq * KNN_KEEP * sizeof(int32_t));
     w.cval = off;
-    off += knn_align((size_t)nq * KNN_KEEP * sizeof(float));
+    off += align_up((size_t)nq * KNN_KEEP * sizeof(float));
     w.scal = off;
     off += 256;
     w.rlist = off;
-    off += knn_align((size_t)nq * sizeof(int32_t));
+    off += align_up((size_t)nq * sizeof(int32_t));
     w.rkeys = off;
-    off += knn_align((size_t)nq * 2 * sizeof(unsigned long long));
+    off += align_up((size_t)nq * 2 * sizeof(unsigned long long));
     w.total = off;
     return w;
 }

@@ -192,8 +192,6 @@ __global__ __launch_bounds__(256) void cut_tail_kernel(const uint32_t *__restric
     pts[2 * i + 1] = (int32_t)(p % (uint32_t)w);
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct CandLayout {
     size_t temp_bytes, flags, slot, total;
 };
@@ -203,10 +201,10 @@ CandLayout cand_layout(size_t n) {
     int *iu = nullptr;
     size_t scan_bytes = 0;
     (void)rocprim::exclusive_scan(nullptr, scan_bytes, iu, iu, 0, n, rocprim::plus<int>());
-    L.temp_bytes = align256(scan_bytes);
+    L.temp_bytes = align_up(scan_bytes);
     L.flags = L.temp_bytes;
-    L.slot = L.flags + align256(n * 4);
-    L.total = L.slot + align256(n * 4);
+    L.slot = L.flags + align_up(n * 4);
+    L.total = L.slot + align_up(n * 4);
     return L;
 }
 
@@ -219,10 +217,10 @@ CutLayout cut_layout(size_t n) {
     uint32_t *ku = nullptr;
     size_t sort_bytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, ku, ku, ku, ku, n, 0u, 32u);
-    L.temp_bytes = align256(sort_bytes);
+    L.temp_bytes = align_up(sort_bytes);
     L.keys = L.temp_bytes;
-    L.pos = L.keys + align256(n * 4);
-    L.total = L.pos + align256(n * 4);
+    L.pos = L.keys + align_up(n * 4);
+    L.total = L.pos + align_up(n * 4);
     return L;
 }
 
@@ -295,6 +293,7 @@ __global__ __launch_bounds__(64) void ssc_probe_kernel(const int32_t *__restrict
 
 // NumPy's pairwise sum of 64 contiguous float32 held one per lane (lane = index): 8 strided
 // accumulators r[j] = t[j] + t[8 + j] + ... in order, then ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)).
+// (Not wave.h's wave_sum, whose butterfly adds in another order.)
 __device__ __forceinline__ float sum64(float t, int lane) {
     const int u = lane & 7;
     float acc = __shfl(t, u);
@@ -447,7 +446,7 @@ static size_t ssc_words(int n_cell_rows, int n_cell_cols) {
 
 extern "C" size_t pano_ssc_probe_work_bytes(int n_cell_rows, int n_cell_cols) {
     if (n_cell_rows < 0 || n_cell_cols < 0) return 0;
-    return align256(ssc_words(n_cell_rows, n_cell_cols) * 4);
+    return align_up(ssc_words(n_cell_rows, n_cell_cols) * 4);
 }
 
 extern "C" int pano_ssc_probe(pano_ctx *ctx, const int32_t *points, int n, double cgr,

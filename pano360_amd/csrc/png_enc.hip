@@ -6,6 +6,7 @@
 // wrapper, the chunks of the PNG container) is pano360_amd/png.py and a NumPy restatement of the
 // filter rule and of the run tokeniser is tests/png_model.py.
 #include "common.h"
+#include "wave.h"
 
 #define FILT_BLOCK 256
 #define FILT_MAX_GROUPS (1 << 20)   // grid cap of the filter kernel (it loops beyond it)
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(FILT_BLOCK) void png_filter_kernel(PngImage P,
             }
         }
         for (int m = 0; m < 5; ++m) {
-            for (int o = 32; o > 0; o >>= 1) s[m] += __shfl_xor(s[m], o, 64);
+            s[m] = wave_sum(s[m]);
             if (lane == 0) sums[wave][m] = s[m];
         }
         __syncthreads();
@@ -542,32 +543,7 @@ __global__ __launch_bounds__(DEF_BLOCK) void deflate_code_kernel(
 }
 
 // ---- 5. exclusive scan of the chunks' bit counts into int64 offsets; offs[n] = the total -------------
-__global__ __launch_bounds__(DEF_BLOCK) void deflate_scan_kernel(const uint32_t *__restrict__ bits,
-                                                                 int64_t n, int64_t *__restrict__ offs) {
-    __shared__ int64_t waves[DEF_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t carry = 0;
-    for (int64_t base = 0; base < n; base += DEF_BLOCK) {
-        const int64_t i = base + threadIdx.x;
-        const int64_t v = i < n ? bits[i] : 0;
-        int64_t x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int64_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) waves[wave] = x;
-        __syncthreads();
-        int64_t before = 0, total = 0;
-        for (int k = 0; k < DEF_BLOCK / 64; ++k) {
-            if (k < wave) before += waves[k];
-            total += waves[k];
-        }
-        if (i < n) offs[i] = carry + before + x - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offs[n] = carry;
-}
+// (wave.h: scan_exclusive_kernel)
 
 // ---- 6. emission ------------------------------------------------------------------------------------
 // A thread's bits go into the zeroed stream LSB first: the words wholly inside its bit range are
@@ -639,11 +615,7 @@ __global__ __launch_bounds__(DEF_BLOCK) void deflate_emit_kernel(
                 count += lens[sym] + nextra + dist_len;
             });
         if (tid == DEF_BLOCK - 1) count += lens[256];
-        int x = count;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
+        const int x = wave_scan_inclusive(count);
         if (lane == 63) wave_bits[wave] = x;
         __syncthreads();                            // (also publishes code[])
         int before = 0;
@@ -684,9 +656,6 @@ __global__ __launch_bounds__(DEF_BLOCK) void deflate_emit_kernel(
 }
 
 // ---- the entry points ------------------------------------------------------------------------------
-static inline int64_t pceil(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t palign(int64_t a) { return (a + 255) / 256 * 256; }
-
 extern "C" int pano_png_filter(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch,
                                int flags, uint8_t *filtered) {
     PANO_ENTER(ctx, "pano_png_filter");
@@ -701,10 +670,9 @@ extern "C" int pano_png_filter(pano_ctx *ctx, const uint8_t *img, int h, int w, 
     P.w = w;
     P.bgr = flags & PANO_PNG_BGR;
     const hipStream_t s = (hipStream_t)stream;
-    const unsigned groups = (unsigned)(h < FILT_MAX_GROUPS ? h : FILT_MAX_GROUPS);
     PANO_TIMED(PK_PNG_FILTER, s,
-               hipLaunchKernelGGL(png_filter_kernel, dim3(groups), dim3(FILT_BLOCK), 0, s, P,
-                                  filtered));
+               hipLaunchKernelGGL(png_filter_kernel, capped_grid(h, FILT_MAX_GROUPS),
+                                  dim3(FILT_BLOCK), 0, s, P, filtered));
     PANO_LAUNCH_CHECK("png_filter_kernel");
     return PANO_OK;
 }
@@ -740,34 +708,18 @@ struct DefWork {
 };
 static DefWork def_work(int64_t n) {
     DefWork w;
-    w.nchunks = n > 0 ? pceil(n, DEFLATE_CHUNK) : 1;
+    w.nchunks = n > 0 ? ceil_div(n, DEFLATE_CHUNK) : 1;
     w.recs = 0;
     w.bits = (int64_t)sizeof(DefRecord) * w.nchunks;
-    w.offs = w.bits + palign(4 * w.nchunks);
-    w.adler = w.offs + palign(8 * (w.nchunks + 1));
-    w.bytes = w.adler + palign(8 * w.nchunks);
+    w.offs = w.bits + align_up(4 * w.nchunks);
+    w.adler = w.offs + align_up(8 * (w.nchunks + 1));
+    w.bytes = w.adler + align_up(8 * w.nchunks);
     return w;
 }
 
 extern "C" size_t pano_deflate_work_bytes(int64_t n) {
     if (n < 0 || n >= PANO_DEFLATE_MAX_BYTES) return 0;
     return (size_t)def_work(n).bytes;
-}
-
-// grow a context buffer (device or pinned host) to at least `need` bytes; the stream is idle
-static int png_reserve(uint8_t **buf, size_t *cap, size_t need, bool host) {
-    if (need <= *cap) return PANO_OK;
-    if (*buf) {
-        if (host) PANO_HIP(hipHostFree(*buf));
-        else PANO_HIP(hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-    }
-    need += need / 4;
-    if (host) PANO_HIP(hipHostMalloc((void **)buf, need, hipHostMallocDefault));
-    else PANO_HIP(hipMalloc((void **)buf, need));
-    *cap = need;
-    return PANO_OK;
 }
 
 extern "C" int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void *work,
@@ -790,7 +742,7 @@ extern "C" int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void 
     uint32_t *bits = (uint32_t *)(w8 + L.bits), *adler = (uint32_t *)(w8 + L.adler);
     int64_t *offs = (int64_t *)(w8 + L.offs);
     const int64_t nc = L.nchunks;
-    const dim3 groups((unsigned)(nc < DEF_MAX_GROUPS ? nc : DEF_MAX_GROUPS));
+    const dim3 groups = capped_grid(nc, DEF_MAX_GROUPS);
 
     // 4. the chunks' codes and bit counts, 5. their scan; wait for the total and the Adler partials
     PANO_TIMED(PK_DEFLATE_CODE, s,
@@ -798,9 +750,9 @@ extern "C" int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void 
                                   recs, bits, adler));
     PANO_LAUNCH_CHECK("deflate_code_kernel");
     PANO_TIMED(PK_DEFLATE_SCAN, s,
-               hipLaunchKernelGGL(deflate_scan_kernel, dim3(1), dim3(DEF_BLOCK), 0, s,
-                                  (const uint32_t *)bits, nc, offs));
-    PANO_LAUNCH_CHECK("deflate_scan_kernel");
+               hipLaunchKernelGGL((scan_exclusive_kernel<DEF_BLOCK, uint32_t>), dim3(1), dim3(DEF_BLOCK),
+                                  0, s, (const uint32_t *)bits, nc, offs));
+    PANO_LAUNCH_CHECK("scan_exclusive_kernel");
     int64_t total_bits = 0;
     std::vector<uint32_t> partial(2 * (size_t)nc);
     PANO_HIP(hipMemcpyAsync(&total_bits, offs + nc, 8, hipMemcpyDeviceToHost, s));
@@ -817,18 +769,21 @@ extern "C" int pano_deflate(pano_ctx *ctx, const uint8_t *data, int64_t n, void 
     *adler_out = (uint32_t)(b << 16 | a);
 
     // 6. emission into the zeroed stream, and the download
-    const int64_t nbytes = pceil(total_bits, 8), raw_bytes = palign(4 * (pceil(total_bits, 32) + 1));
-    if (int rc = png_reserve(&ctx->png_dev, &ctx->png_dev_cap, (size_t)raw_bytes, false)) return rc;
-    if (int rc = png_reserve(&ctx->png_host, &ctx->png_host_cap, (size_t)nbytes, true)) return rc;
-    PANO_HIP(hipMemsetAsync(ctx->png_dev, 0, raw_bytes, s));
+    const int64_t nbytes = ceil_div(total_bits, 8), raw_bytes = align_up(4 * (ceil_div(total_bits, 32) + 1));
+    // (the context's buffers grow with a quarter to spare; the stream is idle, nothing reads them)
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_PNG_DEV], raw_bytes, false, raw_bytes / 4)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_PNG_HOST], nbytes, true, nbytes / 4)) return rc;
+    uint32_t *const dev = (uint32_t *)ctx->buf[BUF_PNG_DEV].p;
+    uint8_t *const host = (uint8_t *)ctx->buf[BUF_PNG_HOST].p;
+    PANO_HIP(hipMemsetAsync(dev, 0, raw_bytes, s));
     PANO_TIMED(PK_DEFLATE_EMIT, s,
                hipLaunchKernelGGL(deflate_emit_kernel, groups, dim3(DEF_BLOCK), DEF_POOL_WORDS * 4, s, data, n, nc,
                                   (const DefRecord *)recs, (const int64_t *)offs,
-                                  (uint32_t *)ctx->png_dev, raw_bytes / 4));
+                                  dev, raw_bytes / 4));
     PANO_LAUNCH_CHECK("deflate_emit_kernel");
-    PANO_HIP(hipMemcpyAsync(ctx->png_host, ctx->png_dev, nbytes, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipMemcpyAsync(host, dev, nbytes, hipMemcpyDeviceToHost, s));
     PANO_HIP(hipStreamSynchronize(s));
-    *stream_out = ctx->png_host;
+    *stream_out = host;
     *stream_bytes = nbytes;
     return PANO_OK;
 }

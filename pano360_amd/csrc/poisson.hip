@@ -32,6 +32,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define PB_BLOCK 256
 #define PB_WAVES (PB_BLOCK / 64)
@@ -71,15 +72,9 @@ __device__ __forceinline__ PbLinks pb_links_P(int j, int xj, int w, int n) {
                    j + w < n && xj != w - 1};
 }
 
-__device__ __forceinline__ double pb_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // the block's sum of v in thread 0 (waves in order); lds: PB_WAVES doubles of its own
 __device__ __forceinline__ double pb_block_sum(double v, double *lds) {
-    v = pb_wave_sum(v);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = lds[0];
@@ -103,7 +98,7 @@ __device__ __forceinline__ void pb_block_totals(const double *__restrict__ part,
     }
 #pragma unroll
     for (int q = 0; q < K; ++q) {
-        acc[q] = pb_wave_sum(acc[q]);
+        acc[q] = wave_sum(acc[q]);
         if ((threadIdx.x & 63) == 0) lds[q][threadIdx.x >> 6] = acc[q];
     }
     __syncthreads();
@@ -411,19 +406,11 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_finish_kernel(const uint8_t *__re
 
 // ---- host ------------------------------------------------------------------------------------
 static int pb_reserve(pano_ctx *ctx, size_t bytes) {
-    if (!ctx->poisson_host)
-        PANO_HIP(hipHostMalloc((void **)&ctx->poisson_host, 4 * sizeof(PbChan), hipHostMallocDefault));
-    if (bytes <= ctx->poisson_cap) return PANO_OK;
-    if (ctx->poisson_dev) {
-        // the last blend's finish kernel may still read the old buffer
-        PANO_HIP(hipStreamSynchronize(ctx->stream));
-        PANO_HIP(hipFree(ctx->poisson_dev));
-        ctx->poisson_dev = nullptr;
-        ctx->poisson_cap = 0;
-    }
-    PANO_HIP(hipMalloc((void **)&ctx->poisson_dev, bytes));
-    ctx->poisson_cap = bytes;
-    return PANO_OK;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_POISSON_HOST], 4 * sizeof(PbChan), true)) return rc;
+    PanoBuf &dev = ctx->buf[BUF_POISSON_DEV];
+    // the last blend's finish kernel may still read the old buffer
+    if (dev.p && bytes > dev.cap) PANO_HIP(hipStreamSynchronize(ctx->stream));
+    return pano_buf_reserve(dev, bytes, false);
 }
 
 extern "C" int pano_poisson_blend(pano_ctx *ctx, const uint8_t *src, uint8_t *tgt,
@@ -442,11 +429,11 @@ extern "C" int pano_poisson_blend(pano_ctx *ctx, const uint8_t *src, uint8_t *tg
     const size_t vec = (size_t)c * stride * sizeof(double);
     const size_t part_bytes = (size_t)c * PB_PARTS * nblk * sizeof(double);
     if (int rc = pb_reserve(ctx, 6 * vec + part_bytes + 4 * sizeof(PbChan))) return rc;
-    uint8_t *base = ctx->poisson_dev;
+    uint8_t *base = (uint8_t *)ctx->buf[BUF_POISSON_DEV].p;
     double *x = (double *)base, *r = (double *)(base + vec), *rh = (double *)(base + 2 * vec);
     double *p = (double *)(base + 3 * vec), *v = (double *)(base + 4 * vec);
     double *t = (double *)(base + 5 * vec), *part = (double *)(base + 6 * vec);
-    PbChan *chan = (PbChan *)(base + 6 * vec + part_bytes), *host = (PbChan *)ctx->poisson_host;
+    PbChan *chan = (PbChan *)(base + 6 * vec + part_bytes), *host = (PbChan *)ctx->buf[BUF_POISSON_HOST].p;
 
     const dim3 grid(nblk, c), block(PB_BLOCK), one(c);
     hipLaunchKernelGGL(pb_setup_kernel, grid, block, 0, s, src, tgt, mask, w, n, c, stride, x, r,

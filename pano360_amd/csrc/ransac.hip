@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wave.h"
 
 #define RANSAC_BLOCK 256
 #define RANSAC_TILE 1024
@@ -184,9 +185,7 @@ __device__ __forceinline__ void ransac_block_sum(double (&v)[K], double *red, do
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        double s = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const double s = wave_sum(v[k]);
         if (lane == 0) red[wave * K + k] = s;
     }
     __syncthreads();

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wave.h"
 
 #define SIFT_BORDER 5
 #define SIFT_MAX_STEPS 5
@@ -625,15 +626,11 @@ __global__ __launch_bounds__(64 * SIFT_WAVES) void sift_describe_kernel(
             if (kk < 2) sum += bin(nb + kk);
             v[e] = (float)sum * from_fixed;
         }
-        float nrm2 = v[0] * v[0] + v[1] * v[1];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nrm2 += __shfl_xor(nrm2, off, 64);
+        float nrm2 = wave_sum(v[0] * v[0] + v[1] * v[1]);
         const float thr = sqrtf(nrm2) * 0.2f;
         v[0] = fminf(v[0], thr);
         v[1] = fminf(v[1], thr);
-        nrm2 = v[0] * v[0] + v[1] * v[1];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nrm2 += __shfl_xor(nrm2, off, 64);
+        nrm2 = wave_sum(v[0] * v[0] + v[1] * v[1]);
         const float s = __fdiv_rn(512.0f, fmaxf(sqrtf(nrm2), 1.1920929e-07f));
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -651,19 +648,14 @@ __global__ __launch_bounds__(64 * SIFT_WAVES) void sift_describe_kernel(
 // the graph's key, so a graph made before a growth never matches again).
 int pano_sift_raw_reserve(pano_ctx *ctx, int rows, int cols) {
     const size_t need = (size_t)rows * cols / 4 > (1u << 20) ? (size_t)rows * cols / 4 : (1u << 20);
-    if (need <= ctx->sift_raw_cap) return PANO_OK;
+    PanoBuf &raw = ctx->buf[BUF_SIFT_RAW];
+    const size_t bytes = (need + 1) * sizeof(uint32_t);          // (+ the list's counter)
+    if (bytes <= raw.cap) return PANO_OK;
     PANO_REQUIRE(!ctx->sift_capturing,
                  "pano_sift_raw_reserve: the extrema list would grow inside a capture");
-    if (ctx->sift_raw) {
-        // kernels on ANY stream this context has targeted - a replay included - may still use it
-        PANO_HIP(hipDeviceSynchronize());
-        PANO_HIP(hipFree(ctx->sift_raw));
-        ctx->sift_raw = nullptr;
-        ctx->sift_raw_cap = 0;
-    }
-    PANO_HIP(hipMalloc((void **)&ctx->sift_raw, (need + 1) * sizeof(uint32_t)));
-    ctx->sift_raw_cap = need;
-    return PANO_OK;
+    // kernels on ANY stream this context has targeted - a replay included - may still use it
+    if (raw.p) PANO_HIP(hipDeviceSynchronize());
+    return pano_buf_reserve(raw, bytes, false);
 }
 
 extern "C" int pano_sift_extrema(pano_ctx *ctx, const float *dog, int rows, int cols, int octave,
@@ -679,7 +671,9 @@ extern "C" int pano_sift_extrema(pano_ctx *ctx, const float *dog, int rows, int 
         // the streaming search + the refinement of the listed extrema
         const hipStream_t s = (hipStream_t)stream;
         if (int rc = pano_sift_raw_reserve(ctx, rows, cols)) return rc;
-        int *raw_count = (int *)(ctx->sift_raw + ctx->sift_raw_cap);
+        uint32_t *const raw = (uint32_t *)ctx->buf[BUF_SIFT_RAW].p;
+        const int raw_cap = (int)(ctx->buf[BUF_SIFT_RAW].cap / sizeof(uint32_t) - 1);
+        int *raw_count = (int *)(raw + raw_cap);
         if (int rc = pano_zero_i32(s, raw_count, 1)) return rc;   // (a kernel: graph-safe, detect.hip)
         int seg_rows = 96;
         while (seg_rows > 12 && (long)ceil_div(cols - 2 * SIFT_BORDER, 62) *
@@ -689,11 +683,10 @@ extern "C" int pano_sift_extrema(pano_ctx *ctx, const float *dog, int rows, int 
                                 ceil_div(rows - 2 * SIFT_BORDER, 4 * seg_rows));
         PANO_TIMED(PK_SIFT_EXTREMA, s, {
             hipLaunchKernelGGL(sift_scan_kernel<5>, grid, block, 0, s, dog, rows, cols,
-                               (float)threshold, seg_rows, ctx->sift_raw, raw_count,
-                               (int)ctx->sift_raw_cap);
+                               (float)threshold, seg_rows, raw, raw_count, raw_cap);
             hipLaunchKernelGGL(sift_refine_kernel, dim3(512), dim3(256), 0, s, dog, rows, cols, octave,
-                               n_layers, contrast_thr, edge_thr, sigma, ctx->sift_raw, raw_count,
-                               (int)ctx->sift_raw_cap, cands, count, max_cands);
+                               n_layers, contrast_thr, edge_thr, sigma, raw, raw_count, raw_cap,
+                               cands, count, max_cands);
         });
         PANO_LAUNCH_CHECK("sift_scan_kernel / sift_refine_kernel");
         return PANO_OK;

@@ -132,8 +132,8 @@ SortLayout sort_layout(int n) {
     int *iu = nullptr;
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, k64, k64, ku, ku, (size_t)n, 0u, 64u);   // size queries
     (void)rocprim::exclusive_scan(nullptr, scan_bytes, iu, iu, 0, (size_t)n, rocprim::plus<int>());
-    L.temp_bytes = ((sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 255) & ~(size_t)255;
-    const size_t arr = ((size_t)n * 4 + 255) & ~(size_t)255;
+    L.temp_bytes = align_up(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+    const size_t arr = align_up((size_t)n * 4);
     L.keys_a = L.temp_bytes;                            // 64-bit keys: two arrays' worth each
     L.keys_b = L.keys_a + 2 * arr;
     L.idx_a = L.keys_b + 2 * arr;

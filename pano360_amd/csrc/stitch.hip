@@ -155,27 +155,29 @@ __global__ __launch_bounds__(LAY_THREADS) void layout_windows_kernel(
 }
 
 static int ensure_layout_buffers(pano_ctx *ctx, int n) {
-    if (!ctx->lay_sum_host) {
+    PanoBuf &sum = ctx->buf[BUF_LAY_SUM_HOST];
+    if (!sum.p) {
         // (the summary, then the sticky mismatch word of the trusted stitches)
-        PANO_HIP(hipHostMalloc((void **)&ctx->lay_sum_host, sizeof(LayoutSummary) + 64, hipHostMallocDefault));
-        memset(ctx->lay_sum_host, 0, sizeof(LayoutSummary) + 64);
+        if (int rc = pano_buf_reserve(sum, sizeof(LayoutSummary) + 64, true)) return rc;
+        memset(sum.p, 0, sizeof(LayoutSummary) + 64);
     }
-    if (n > ctx->lay_cap_n) {
+    PanoBuf &rects = ctx->buf[BUF_LAY_RECTS], &have = ctx->buf[BUF_LAY_HAVE];
+    const size_t rect_bytes = (size_t)n * 4 * sizeof(int32_t);
+    // (each buffer answers for itself: after a failed allocation the next stitch comes here again)
+    if (rect_bytes > rects.cap || (size_t)n > have.cap) {
         PANO_HIP(hipStreamSynchronize(ctx->stream));            // a queued kernel may still read them
-        if (ctx->lay_rects_dev) PANO_HIP(hipFree(ctx->lay_rects_dev));
-        if (ctx->lay_have_dev) PANO_HIP(hipFree(ctx->lay_have_dev));
-        ctx->lay_rects_dev = nullptr;
-        ctx->lay_have_dev = nullptr;
-        PANO_HIP(hipMalloc((void **)&ctx->lay_rects_dev, (size_t)n * 4 * sizeof(int32_t)));
-        PANO_HIP(hipMalloc((void **)&ctx->lay_have_dev, (size_t)n));
-        ctx->lay_cap_n = n;
-        ctx->lay_rects_host.clear();
+        ctx->lay_rects_host.clear();                            // (what the old buffers held)
         ctx->lay_have_host.clear();
+        if (int rc = pano_buf_reserve(rects, rect_bytes, false)) return rc;
+        if (int rc = pano_buf_reserve(have, (size_t)n, false)) return rc;
     }
     return PANO_OK;
 }
 
 // The verified layout as the layout kernel compares it, and the sticky word behind the summary.
+static LayoutSummary *lay_sum_host(pano_ctx *ctx) {
+    return (LayoutSummary *)ctx->buf[BUF_LAY_SUM_HOST].p;
+}
 static LayoutSummary layout_expectation(const pano_layout &v) {
     LayoutSummary e = {};
     e.planes_floats = v.planes_floats, e.blurred_floats = v.blurred_floats;
@@ -185,7 +187,7 @@ static LayoutSummary layout_expectation(const pano_layout &v) {
     return e;
 }
 static int *layout_sticky(pano_ctx *ctx) {
-    return (int *)((unsigned char *)ctx->lay_sum_host + sizeof(LayoutSummary));
+    return (int *)((unsigned char *)lay_sum_host(ctx) + sizeof(LayoutSummary));
 }
 
 static void stitch_signature(const pano_stitch_args *a, int tile_grid, int *sig) {
@@ -394,7 +396,7 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
         // the context's buffers is the one the previous stitch built for this very table: an
         // option switch voids it, pano_ctx_set_option)
         const bool list_kept = n_blur == 0 || ctx->lay_prev.n_records == 0 ||
-                               (ctx->item_buf && ctx->list_table == a->table &&
+                               (ctx->buf[BUF_ITEM_LIST].p && ctx->list_table == a->table &&
                                 ctx->list_n == ctx->lay_prev.n_records);
         if (want_keep && trusted && geom_was_valid && tile_grid == 32 && list_kept) {
             // Kept geometry: the owner map, the valid mask, the interior map, the record table, the
@@ -423,14 +425,14 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
             if (ctx->lay_rects_host.size() != nrect ||
                 memcmp(ctx->lay_rects_host.data(), a->rects, nrect * sizeof(int32_t)) != 0) {
                 ctx->lay_rects_host.assign(a->rects, a->rects + nrect);
-                PANO_HIP(hipMemcpyAsync(ctx->lay_rects_dev, ctx->lay_rects_host.data(),
+                PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_RECTS].p, ctx->lay_rects_host.data(),
                                         nrect * sizeof(int32_t), hipMemcpyHostToDevice, s));
             }
             std::vector<uint8_t> have(a->n, 1);
             if (a->have) have.assign(a->have, a->have + a->n);
             if (ctx->lay_have_host != have) {
                 ctx->lay_have_host = have;
-                PANO_HIP(hipMemcpyAsync(ctx->lay_have_dev, ctx->lay_have_host.data(), (size_t)a->n,
+                PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_HAVE].p, ctx->lay_have_host.data(), (size_t)a->n,
                                         hipMemcpyHostToDevice, s));
             }
             // launch bounds: what the previous layout needed, with slack for cameras that move
@@ -474,12 +476,13 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
             uintptr_t bbase = (uintptr_t)a->blurred;             // as pano_layout_place aligns it
             bbase += (uintptr_t)(-(intptr_t)bbase) % 128;
             hipLaunchKernelGGL(layout_windows_kernel, dim3(1), dim3(LAY_THREADS), 0, s, a->regions,
-                               ctx->lay_rects_dev, ctx->lay_have_dev, a->n, a->max_spans, a->radius,
+                               (const int32_t *)ctx->buf[BUF_LAY_RECTS].p,
+                               (const uint8_t *)ctx->buf[BUF_LAY_HAVE].p, a->n, a->max_spans, a->radius,
                                a->xs0, a->xs1, n_blur, 1, a->planes, (float *)bbase, a->scratch,
                                (long)a->planes_floats, (long)a->blurred_floats,
                                (long)a->scratch_floats, a->cap_tiles, 1, bound.n_records,
                                bound.max_vw, bound.max_vh, bound.max_aw, bound.max_ah, a->table,
-                               ctx->lay_sum_host, layout_expectation(ctx->lay_prev), trusted ? 1 : 0,
+                               lay_sum_host(ctx), layout_expectation(ctx->lay_prev), trusted ? 1 : 0,
                                layout_sticky(ctx));
             PANO_LAUNCH_CHECK("layout_windows_kernel");
             // the summary goes straight into pinned host memory; the caller's copy of the records
@@ -516,7 +519,7 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
             }
             PANO_HIP(hipEventSynchronize(ctx->ev_regions));      // the GPU is in the warp by now
             PANO_HIP(hipEventSynchronize(ctx->ev_copy));
-            const LayoutSummary sum = *ctx->lay_sum_host;
+            const LayoutSummary sum = *lay_sum_host(ctx);
             a->layout.planes_floats = sum.planes_floats;
             a->layout.blurred_floats = sum.blurred_floats;
             a->layout.scratch_floats = sum.scratch_floats;
@@ -586,7 +589,7 @@ extern "C" int pano_stitch_verify(pano_ctx *ctx) {
     PANO_HIP(hipSetDevice(ctx->device));                 // (writes no buffer: kept geometry stays)
     PANO_HIP(hipEventSynchronize(ctx->ev_regions));
     ctx->trusted_pending = false;
-    const LayoutSummary sum = *ctx->lay_sum_host;
+    const LayoutSummary sum = *lay_sum_host(ctx);
     const pano_layout &v = ctx->lay_prev;
     // (the last trusted stitch's summary, and the sticky word every trusted stitch before it left)
     const int sticky = __atomic_exchange_n(layout_sticky(ctx), 0, __ATOMIC_SEQ_CST);

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Patch
+from ._lib import Patch, _ptr
 
 BORDER_SAMPLES = 100        # stitcher.py:109
 MULTIBAND_PAD = 10          # stitcher.py:296-297
@@ -329,10 +329,6 @@ def gain_tables(gains):
 def _torch():
     import torch
     return torch
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 # numpy mirrors of the C records (include/pano360.h), for building tables in bulk

@@ -99,6 +99,38 @@ def test_two_runs_give_identical_bytes(eng):
     assert a == b
 
 
+def test_growth_then_reuse_on_one_fresh_engine(eng):
+    """The stream buffers are the context's and only grow: after a large image the small one is
+    emitted (ORed) into a buffer longer than its stream that held the large one's bits."""
+    from pano360_amd import engine
+    from pano360_amd import jpeg as J
+    fresh = engine.Engine(eng.device)
+    small, large = content("frame", 16, 16), content("noise", 640, 480)
+    first = J.encode_device(small, 75, -1, "rgb", fresh)
+    assert first == pillow(small, 75, -1)
+    assert J.encode_device(large, 95, -1, "rgb", fresh) == pillow(large, 95, -1)
+    again = J.encode_device(small, 75, -1, "rgb", fresh)
+    assert again == pillow(small, 75, -1) and again == first
+
+
+def test_scan_tile_borders_equal_pillow(eng):
+    """A scan workgroup takes 4096 values.  At 4:2:2, 512 x 256 is exactly 4096 blocks (one full
+    tile) and 656 x 200 is 4100 (a second tile of four); 1024 x 512 noise at quality 95 has a
+    stuffed stream of more than 2 x 4096 chunks of 64 bytes, so the stuffing scan crosses a tile
+    as well."""
+    from pano360_amd import jpeg as J
+    for w, h, blocks in ((512, 256, 4096), (656, 200, 4100)):
+        mcus = -(-w // 16) * -(-h // 8)
+        assert 4 * mcus == blocks
+        rgb = content("noise", w, h)
+        assert J.encode_device(rgb, 75, 1, "rgb", eng) == pillow(rgb, 75, 1), (w, h)
+    rgb = content("noise", 1024, 512)
+    want = pillow(rgb, 95, -1)
+    hdr = J.parse(want)
+    assert hdr.data_end - hdr.data_start > 2 * 4096 * 64
+    assert J.encode_device(rgb, 95, -1, "rgb", eng) == want
+
+
 def test_write_routes_out_of_scope_to_pillow(eng, tmp_path):
     from pano360_amd import jpeg as J
     rgb = content("frame", 40, 30)

@@ -406,6 +406,34 @@ def test_stitch_with_the_layout_on_the_device_equals_the_host_layout(eng, scene)
             assert a[0].shape == b[0].shape and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
+def test_layout_buffers_grow_and_are_reused_on_one_engine():
+    """The device copies of the rectangles and resident flags are the context's and only grow: a
+    2-frame rig, a 5-frame rig (the buffers grow) and the 2-frame rig again (in buffers that held
+    the five), each stitched twice so that the second stitch goes through the device layout.
+    The 2-frame results are bit-identical and nothing falls back to the host layout."""
+    import torch
+    from pano360_amd import _lib, engine, synth
+    w, h = 160, 96
+    use = engine.Engine("cuda:0")
+    use.set_option(_lib.OPT_STITCH_ASYNC, 1)
+    got = []
+    for n in (2, 5, 2):
+        rots, intrs = synth.make_cameras(n, w, h, step_deg=15.0, jitter=0.004, seed=n)
+        frames = use.upload_frames([synth.make_frame(i, w, h, "A") for i in range(n)])
+        before = use.stitch_counts()
+        for _ in range(2):                      # (the first of a shape is laid out on the host)
+            plan = use.upload_plan(engine.Plan([(h, w)] * n, rots, intrs, True, 10 ** 9))
+            mosaic, _, valid, _ = use.multiband_fused(frames, plan, 5)
+            torch.cuda.synchronize()
+        after = use.stitch_counts()
+        assert (after[0] - before[0], after[1] - before[1]) == (1, 0), (n, before, after)
+        got.append((mosaic.clone(), valid.clone(), use.crop_rect(valid)))
+    assert use.stitch_counts() == (3, 0)
+    assert got[0][0].any() and got[0][1].any()
+    assert torch.equal(got[0][0], got[2][0]) and torch.equal(got[0][1], got[2][1])
+    assert got[0][2] == got[2][2]
+
+
 @pytest.mark.parametrize("strip_case", [False, True])
 def test_trusted_stitches_equal_waiting_ones_and_a_broken_promise_is_caught(strip_case):
     """Engine.trust_layouts: a stitch that repeats the previous one's Plan object (a PlanMemo hit)

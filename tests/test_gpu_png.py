@@ -178,6 +178,17 @@ def test_deflate_round_trips_the_edge_cases(eng):
             assert len(z) < 1000                    # runs, not literals, across the chunk borders
 
 
+def test_deflate_growth_then_reuse_on_one_engine(eng):
+    """The stream buffers are the context's and only grow: after 3 chunks + 5 bytes of noise the
+    one byte is emitted (ORed) into a buffer that held the long stream's bits."""
+    from pano360_amd import engine, png
+    fresh = engine.Engine(eng.device)
+    noise = np.random.default_rng(29).integers(0, 256, 3 * png.CHUNK + 5, dtype=np.uint8).tobytes()
+    first = _check_deflate(png, fresh, b"q", "one byte")
+    _check_deflate(png, fresh, noise, "noise")
+    assert _check_deflate(png, fresh, b"q", "one byte again") == first
+
+
 def test_deflate_past_2_31_stream_bits(eng):
     """280 MB of device-generated noise: the bit offsets pass 2^31 (the only large case)."""
     import torch
