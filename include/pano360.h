@@ -1112,6 +1112,67 @@ int pano_msop_describe(pano_ctx *ctx, const float *gx, const float *gy, const fl
                        int h, int w, const int32_t *points, const int32_t *sel, int n, int scale,
                        double *points_out, float *theta, float *tiles, float *desc);
 
+/* Views of a finished mosaic        (the reference ends with cv2.imshow, stitcher.py:449-451:
+ * a person looks at the mosaic; here a renderer does, csrc/view.hip)
+ * A mosaic of H x W pixels samples the sphere at theta = low[0] + x res[0], phi = low[1] + y res[1]
+ * (Plan.__init__, SphProj.hom2proj: theta = atan2(x, z), phi = atan2(y, hypot(x, z)); the frame is
+ * x right, y down, z forward).  It is CLOSED when |W res[0] - 2 pi| < res[0] / 2: column W is
+ * column 0 again.
+ *
+ * pano_mip_u8: the mip chain of a uint8 [h][w][3] image whose rows are `pitch` bytes apart.
+ *     Level 0 is the image, level l + 1 is ((h_l + 1) / 2, (w_l + 1) / 2), a pixel
+ *     (a + b + c + d + 2) >> 2 over its 2 x 2 block with the odd index clamped to the last row or
+ *     column; the levels stop at 1 x 1 or at PANO_VIEW_MAX_LEVELS.  mips: dev, level l dense at
+ *     mips + offsets[l]; offsets: HOST int64 [n_levels + 1], ascending, offsets[l + 1] >=
+ *     offsets[l] + 3 h_l w_l (the last entry is the buffer's size); n_levels must be the chain's
+ *     length.  One copy and n_levels - 1 launches, asynchronous on the stream.
+ * pano_view_render: ONE launch renders n views (at most PANO_VIEW_MAX_VIEWS, of any sizes and
+ *     kinds) of the chain.  View i writes image uint8 [h][w][3] and mask uint8 [h][w] (1 = the
+ *     mosaic covers the pixel's direction; an uncovered pixel is 0 in both).  mosaic, views: HOST
+ *     records in float64, converted to float32 by the call; everything on the device is float32,
+ *     one rounding per operation.  Output pixel (u, v) gets a direction d by the view's kind:
+ *       PANO_VIEW_RECTILINEAR    d = m (u, v, 1), m = R K^-1 formed by the caller
+ *       PANO_VIEW_EQUIRECT       theta' = p[0] + u p[1], phi' = p[2] + v p[3],
+ *                                d = m (cos phi' sin theta', sin phi', cos phi' cos theta'), m = R
+ *       PANO_VIEW_STEREOGRAPHIC  X = (u - p[0]) / p[2], Y = (v - p[1]) / p[2],
+ *                                d = m (4 X, 4 Y, 4 - (X X + Y Y)), m = R
+ *     then, for every kind:
+ *       theta = atan2(dx, dz), phi = atan2(dy, hypot(dx, dz));
+ *       fx = (theta - low[0]) / res[0] brought into [0, 2 pi / res[0]) and, on a closed mosaic,
+ *       multiplied by W / (2 pi / res[0]) so that its period is W; fy = (phi - low[1]) / res[1];
+ *       covered: 0 <= fy <= H - 1 and, on an open mosaic, fx <= W - 1;
+ *       rho = the larger length of the forward differences of (fx, fy) towards (u + 1, v) and
+ *       (u, v + 1), which the thread evaluates itself (the theta difference wrapped into
+ *       (-pi, pi]); lod = clamp(log2 rho, 0, n_levels - 1);
+ *       the sample is trilinear: bilinear in the levels floor(lod) and floor(lod) + 1 at the level
+ *       coordinate (f - (2^l - 1) / 2) / 2^l, rows clamped, columns clamped (open) or taken modulo
+ *       the level's width (closed), mixed by lod - floor(lod); floor(x + 0.5) clamped to 0 .. 255.
+ *     On a closed mosaic whose W is not a multiple of 2^l the seam is slightly stretched at level
+ *     l (its width times 2^l is not W). */
+#define PANO_VIEW_MAX_LEVELS 16
+#define PANO_VIEW_MAX_VIEWS 32
+#define PANO_VIEW_MAX_SIDE 32768   /* of a mosaic and of a view                    */
+#define PANO_VIEW_RECTILINEAR 0
+#define PANO_VIEW_EQUIRECT 1
+#define PANO_VIEW_STEREOGRAPHIC 2
+typedef struct pano_view {
+    double m[9];               /* row-major: R K^-1 (rectilinear), else R        */
+    double p[4];               /* equirect: a0, sa, b0, sb; stereographic: cx, cy, f */
+    uint8_t *image;            /* dev uint8 [h][w][3]                            */
+    uint8_t *mask;             /* dev uint8 [h][w]                               */
+    int32_t kind, w, h, reserved;
+} pano_view;
+typedef struct pano_view_mosaic {
+    double low[2], res[2];     /* (theta, phi) of pixel (0, 0); rad/px along x, y */
+    int32_t h, w;
+    int32_t closed;            /* 1 = the columns wrap (checked against w res[0]) */
+    int32_t reserved;
+} pano_view_mosaic;
+int pano_mip_u8(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch, uint8_t *mips,
+                const int64_t *offsets, int n_levels);
+int pano_view_render(pano_ctx *ctx, const uint8_t *mips, const int64_t *offsets, int n_levels,
+                     const pano_view_mosaic *mosaic, const pano_view *views, int n);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

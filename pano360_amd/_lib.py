@@ -87,6 +87,23 @@ SEAM_RESIDENT_CELLS = 81408
 SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
 SSC_ONCHIP_CELLS = 524288
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
+# pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
+VIEW_MAX_LEVELS = 16
+VIEW_MAX_VIEWS = 32
+
+
+class View(C.Structure):
+    """``pano_view`` of include/pano360.h (136 bytes)."""
+    _fields_ = [("m", C.c_double * 9), ("p", C.c_double * 4),
+                ("image", C.c_void_p), ("mask", C.c_void_p),
+                ("kind", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ViewMosaic(C.Structure):
+    """``pano_view_mosaic`` of include/pano360.h (48 bytes)."""
+    _fields_ = [("low", C.c_double * 2), ("res", C.c_double * 2),
+                ("h", C.c_int32), ("w", C.c_int32), ("closed", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class Pair(C.Structure):
@@ -206,6 +223,9 @@ _SIGNATURES = {
     "pano_ssc_probe": (_i, [_vp, _vp, _i, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pano_msop_describe": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,
                                 _vp]),
+    "pano_mip_u8": (_i, [_vp, _vp, _i, _i, C.c_int64, _vp, C.POINTER(C.c_int64), _i]),
+    "pano_view_render": (_i, [_vp, _vp, C.POINTER(C.c_int64), _i, C.POINTER(ViewMosaic),
+                              C.POINTER(View), _i]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

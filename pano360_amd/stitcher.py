@@ -231,6 +231,14 @@ def _stitch_device(regions, blender, equalize, crop):
     """``stitch`` up to the download: (mosaic, crop rectangle).  The mosaic is the uint8 BGR
     device tensor of the fused blenders (a host array for any other blender); the rectangle is
     (y0, x0, h, w) with ``crop``, else None."""
+    return _stitch_device_geometry(regions, blender, equalize, crop)[:2]
+
+
+def _stitch_device_geometry(regions, blender, equalize, crop):
+    """``_stitch_device`` and, third, the ``view.MosaicGeometry`` of the whole mosaic (where its
+    pixels lie on the sphere: the plan's ``low``, ``resolution`` and ``shape``); the cropped
+    mosaic's is ``geometry.cropped(rect)``."""
+    from . import view as _view
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
     padded = blender == multiband_blend                     # stitcher.py:295
@@ -269,7 +277,7 @@ def _stitch_device(regions, blender, equalize, crop):
         rect = eng.crop_rect(valid)
         if rect is None:
             raise UnboundLocalError("local variable 'last' referenced before assignment")
-    return mosaic, rect
+    return mosaic, rect, _view.MosaicGeometry.of_plan(plan)
 
 
 def _download_cropped(mosaic, rect):
@@ -352,8 +360,30 @@ def _register(path, name, frames, badjust, detector="sift"):
     return regions
 
 
-def main(argv=None):
-    """Same command line as the reference (stitcher.py:390-451)."""
+def _view_spec(text):
+    """``YAW,PITCH,FOV[,WxH]`` of --view, degrees: (yaw, pitch, fov, (w, h))."""
+    parts = text.split(",")
+    try:
+        if len(parts) not in (3, 4):
+            raise ValueError(text)
+        yaw, pitch, fov = (float(v) for v in parts[:3])
+        w, h = (int(v) for v in parts[3].lower().split("x")) if len(parts) == 4 else (1920, 1080)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: YAW,PITCH,FOV[,WxH]") from None
+    if not 0 < fov < 180 or w < 1 or h < 1:
+        raise argparse.ArgumentTypeError(f"{text!r}: 0 < FOV < 180 degrees, sides >= 1")
+    return yaw, pitch, fov, (w, h)
+
+
+def _positive(text):
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"{text}: >= 1")
+    return value
+
+
+def parse_args(argv=None):
+    """The reference's command line (stitcher.py:390-409) and this port's additions."""
     parser = argparse.ArgumentParser(description="Stitch images.")
     parser.add_argument("path", type=str, help="directory with the images to process.")
     parser.add_argument("-s", "--shrink", type=float, default=2,
@@ -372,7 +402,26 @@ def main(argv=None):
     parser.add_argument("--detector", default="sift", choices=["sift", "msop"],
                         help="feature detector of --register (msop: the caches are named "
                              "matches_<name>_msop.npz and ba_<name>_msop.pkl).")
+    parser.add_argument("--view", action="append", type=_view_spec, default=[],
+                        metavar="YAW,PITCH,FOV[,WxH]",
+                        help="also save a pinhole look at the mosaic (degrees; default 1920x1080) "
+                             "as <out>_view<k>; repeatable; a negative yaw is written --view=-30,0,90.")
+    parser.add_argument("--equirect", type=_positive, metavar="WIDTH",
+                        help="also save the full-sphere 2:1 equirectangular image as "
+                             "<out>_equirect.")
+    parser.add_argument("--cube", type=_positive, metavar="SIDE",
+                        help="also save the six cube faces as <out>_cube_<face>.")
     args = parser.parse_args(argv)
+    if (args.view or args.equirect or args.cube) and not args.out:
+        parser.error("--view, --equirect and --cube need -o")
+    if args.equirect and args.equirect % 2:
+        parser.error("--equirect: an even width")
+    return args
+
+
+def main(argv=None):
+    """Same command line as the reference (stitcher.py:390-451)."""
+    args = parse_args(argv)
 
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
     if args.detector == "msop":
@@ -411,19 +460,55 @@ def main(argv=None):
                 reg.img = frame
 
     start = time.time()
-    dev_mosaic, rect = _stitch_device(regions, BLENDERS[args.blend], args.equalize, args.crop)
+    dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend], args.equalize,
+                                                     args.crop)
     mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
         _save(args.out, dev_mosaic, rect, mosaic)
+        _save_views(args, dev_mosaic, rect, geom)
     return mosaic
+
+
+def view_outputs(args):
+    """[(file name, view)] of --view, --equirect and --cube: ``<stem>_view<k><ext>``,
+    ``<stem>_equirect<ext>``, ``<stem>_cube_<face><ext>`` beside ``args.out``."""
+    from . import view as _view
+    stem, ext = os.path.splitext(args.out)
+    rad = np.pi / 180
+    out = [(f"{stem}_view{k}{ext}", _view.perspective(yaw * rad, pitch * rad, 0.0, fov * rad, size))
+           for k, (yaw, pitch, fov, size) in enumerate(args.view)]
+    if args.equirect:
+        out.append((f"{stem}_equirect{ext}", _view.equirect(args.equirect)))
+    if args.cube:
+        out += [(f"{stem}_cube_{face}{ext}", v)
+                for face, v in zip(_view.CUBE_FACES, _view.cube_faces(args.cube))]
+    return out
+
+
+def _save_views(args, dev_mosaic, rect, geom):
+    """Renders the views the command line asks for from the mosaic (the cropped one with --crop;
+    a custom blender's host mosaic is uploaded) in one launch, and writes them like the mosaic."""
+    from . import view as _view
+    outputs = view_outputs(args)
+    if not outputs:
+        return
+    start = time.time()
+    if rect is not None:
+        y0, x0, h, w = rect
+        dev_mosaic, geom = dev_mosaic[y0:y0 + h, x0:x0 + w, :], geom.cropped(rect)
+    images, _ = _view.render_device(dev_mosaic, geom, [v for _, v in outputs])
+    for (path, _), image in zip(outputs, images):
+        _save(path, image, None, None)
+    logging.info(f"Rendered {len(outputs)} views, time: {time.time() - start}")
 
 
 def _save(path, dev_mosaic, rect, mosaic):
     """Write the mosaic as Pillow's ``save(path)`` would.  A JPEG of a device mosaic is
     encoded on the device at Pillow's defaults (``jpeg.encode_device``: the same bytes), a PNG
     of one by ``png.encode_device`` (the same pixels, not zlib's bytes); every other format,
-    and the host mosaic of a custom blender, goes through Pillow."""
+    and the host mosaic of a custom blender, goes through Pillow (``mosaic`` None: the device
+    image is downloaded for it)."""
     from . import jpeg as _jpeg
     from . import png as _png
     lower = path.lower()
@@ -440,6 +525,8 @@ def _save(path, dev_mosaic, rect, mosaic):
                 fid.write(data)
             return
     from PIL import Image as PilImage
+    if mosaic is None:
+        mosaic = dev_mosaic.cpu().numpy()
     PilImage.fromarray(np.ascontiguousarray(mosaic[..., ::-1])).save(path)
 
 
