@@ -993,6 +993,53 @@ int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pi
                      int subsampling, const uint8_t *qt, void *work, int64_t work_bytes,
                      const uint8_t **stream, int64_t *stream_bytes);
 
+/* Baseline JPEG encode of a batch                          the tiles of pano360_amd/tiles.py
+ * n images of any sizes in one call; for every image on its own the contract of pano_jpeg_encode
+ * holds (its stream is the bytes that call returns for it).  The sampling, the channel order and
+ * the quantisers are the batch's.
+ *   images       host pano_jpeg_image [n]: img (dev), pitch, h, w as in pano_jpeg_encode; an
+ *                image may be a crop view of a larger one (a tile is not copied).  The call
+ *                uploads the table.
+ *   n            1 .. PANO_JPEG_BATCH_MAX; all images together at most
+ *                PANO_JPEG_BATCH_MAX_BLOCKS blocks (dummy blocks included)
+ *   work         dev scratch of pano_jpeg_encode_batch_work_bytes(blocks, n) bytes (0: bad
+ *                size), blocks the sum over the images of MCUs x blocks per MCU.  It starts with
+ *                the quantised blocks of all images, image after image, as in pano_jpeg_encode.
+ *   *streams     out: the n entropy-coded segments (stuffed, padded) one after the other
+ *   *offsets     out: int64 [n + 1], image i's segment is (*streams)[(*offsets)[i] ..
+ *                (*offsets)[i + 1]).  Both in pinned host memory the context owns, valid until
+ *                its next pano_jpeg_encode or pano_jpeg_encode_batch or its destruction.
+ * The five stages of pano_jpeg_encode run over the batch as a whole, the blocks of all images
+ * numbered one after the other:
+ *   - a block finds its image by bisecting the table of the images' first blocks (int32 [n + 1],
+ *     uploaded with the descriptors), once per block and stage; workgroups straddle images.  Edge
+ *     replication, dummy blocks and the DC prediction (zero at an image's first MCU) are the
+ *     image's own.
+ *   - one scan of all blocks' bit counts; an image's bits are the difference of the offsets at
+ *     its ends.  A kernel over the images turns them into bytes (padded with 1-bits to a whole
+ *     byte, by the image's last block) and 64-byte stuffing chunks, and a second, small scan
+ *     gives every image its first chunk: an image's raw bits start on a chunk of its own, never
+ *     byte-packed behind its neighbour, so no word, pad bit or 0xFF of one image is seen with
+ *     another's.  The call waits for the chunk total (wait 1).
+ *   - stuffing: a chunk's count is its stream bytes plus its 0xFF bytes, so the scan of the
+ *     counts is the position in the output, where the streams are packed byte after byte; an
+ *     image's first chunk also writes offsets[i].  The call waits for the stuffed size (wait 2).
+ * Then the offsets and the streams are copied to the host in one copy and the call waits for
+ * that: two waits and one download whatever n is.  Not capturable.  The same input gives the same
+ * bytes on every run.  n, sizes, pitches, flags, quantisers, the block total and the scratch
+ * size are checked before anything is queued. */
+#define PANO_JPEG_BATCH_MAX 16384
+#define PANO_JPEG_BATCH_MAX_BLOCKS (1 << 28)
+typedef struct pano_jpeg_image {
+    const uint8_t *img;
+    int64_t pitch;
+    int32_t h, w;
+} pano_jpeg_image;
+size_t pano_jpeg_encode_batch_work_bytes(int64_t blocks, int n);
+int pano_jpeg_encode_batch(pano_ctx *ctx, const pano_jpeg_image *images, int n, int flags,
+                           int subsampling, const uint8_t *qt, void *work, int64_t work_bytes,
+                           const uint8_t **streams, const int64_t **offsets);
+
 /* PNG output: the scanline filters and a deflate coder            stitcher.py:446-447 (cv2.imwrite)
  * A PNG cannot be zlib's bytes (its match search is serial); the contract is: the file decodes
  * to exactly the image's pixels, the same input gives the same bytes on every run, and the file

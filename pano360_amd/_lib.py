@@ -90,6 +90,14 @@ EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says
 # pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
 VIEW_MAX_LEVELS = 16
 VIEW_MAX_VIEWS = 32
+# pano_jpeg_encode_batch: PANO_JPEG_BATCH_MAX, PANO_JPEG_BATCH_MAX_BLOCKS
+JPEG_BATCH_MAX = 16384
+JPEG_BATCH_MAX_BLOCKS = 1 << 28
+
+
+class JpegImage(C.Structure):
+    """``pano_jpeg_image`` of include/pano360.h (24 bytes)."""
+    _fields_ = [("img", C.c_void_p), ("pitch", C.c_int64), ("h", C.c_int32), ("w", C.c_int32)]
 
 
 class View(C.Structure):
@@ -207,6 +215,9 @@ _SIGNATURES = {
     "pano_jpeg_encode_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_jpeg_encode": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _vp, _vp, C.c_int64,
                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "pano_jpeg_encode_batch_work_bytes": (C.c_size_t, [C.c_int64, _i]),
+    "pano_jpeg_encode_batch": (_i, [_vp, C.POINTER(JpegImage), _i, _i, _i, _vp, _vp, C.c_int64,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pano_png_filter": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _vp]),
     "pano_deflate_work_bytes": (C.c_size_t, [C.c_int64]),
     "pano_deflate": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_void_p),

@@ -1,7 +1,9 @@
-// Baseline JPEG encode of one image (pano_jpeg_encode): colour conversion, downsampling, the
-// ISLOW FDCT and quantisation per block, per-block Huffman bit counts, an int64 scan of them, the
-// bit emission and the byte stuffing.  The contract (what is bit-exact with what, the scratch
-// layout, the waits) is in include/pano360.h; the host side (quantisation tables, the header) is
+// Baseline JPEG encode of one image (pano_jpeg_encode) or of a batch of images of any sizes
+// (pano_jpeg_encode_batch): colour conversion, downsampling, the ISLOW FDCT and quantisation per
+// block, per-block Huffman bit counts, an int64 scan of them, the bit emission and the byte
+// stuffing.  The batch runs the same stages over all images' blocks at once; what differs is at
+// "the batch" below.  The contract (what is bit-exact with what, the scratch layout, the waits) is
+// in include/pano360.h; the host side (quantisation tables, the header) is
 // pano360_amd/jpeg.py and a NumPy restatement of every stage is tests/jpeg_encode_model.py.
 //
 // Blocks are numbered in scan order: MCU by MCU, and inside an MCU the luma blocks row by row,
@@ -75,7 +77,7 @@ __constant__ uint8_t kEncZigzag[64] = {
     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- the image and its block grid ----------------------------------------------------------------
-struct EncImage {
+struct EncGeom {
     const uint8_t *img;             // pixel (x, y) at img[y * pitch + 3 x], RGB or BGR
     int64_t pitch;
     int w, h, bgr;
@@ -83,6 +85,8 @@ struct EncImage {
     int mx, my, bpm;                // MCUs across / down, blocks per MCU
     int wib[2], hib[2];             // blocks across / down of the luma and of a chroma component
     int nblocks;
+};
+struct EncImage : EncGeom {
     uint8_t q[2][64];               // quantisers, natural order
 };
 
@@ -94,7 +98,7 @@ struct EncPlace {
     int comp, bx, by;
     bool dummy;
 };
-__device__ __forceinline__ EncPlace enc_place(const EncImage &E, int b) {
+__device__ __forceinline__ EncPlace enc_place(const EncGeom &E, int b) {
     const int mcu = b / E.bpm, k = b - mcu * E.bpm, ny = E.hm * E.vm;
     const int ux = mcu % E.mx, uy = mcu / E.mx;
     EncPlace p;
@@ -118,7 +122,7 @@ __device__ __forceinline__ EncPlace enc_place(const EncImage &E, int b) {
     return p;
 }
 
-__device__ __forceinline__ void enc_rgb(const EncImage &E, int x, int y, int &r, int &g, int &b) {
+__device__ __forceinline__ void enc_rgb(const EncGeom &E, int x, int y, int &r, int &g, int &b) {
     const uint8_t *p = E.img + (int64_t)y * E.pitch + 3 * (int64_t)x;
     const int c0 = p[0], c1 = p[1], c2 = p[2];
     r = E.bgr ? c2 : c0;
@@ -127,7 +131,7 @@ __device__ __forceinline__ void enc_rgb(const EncImage &E, int x, int y, int &r,
 }
 
 // jccolor.c's rgb_ycc_convert (SCALEBITS 16; ONE_HALF - 1 on Cb and Cr)
-__device__ __forceinline__ int enc_ycc(const EncImage &E, int comp, int x, int y) {
+__device__ __forceinline__ int enc_ycc(const EncGeom &E, int comp, int x, int y) {
     int r, g, b;
     enc_rgb(E, x, y, r, g, b);
     if (comp == 0) return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
@@ -138,7 +142,7 @@ __device__ __forceinline__ int enc_ycc(const EncImage &E, int comp, int x, int y
 // The sample of component `comp` at (sx, sy) as libjpeg's preprocessing makes it: the last
 // column and row replicated; chroma downsampled h2v1 (bias 0, 1, ...) or h2v2 (bias 1, 2, ...)
 // over the replicated pixels; below the last downsampled h2v2 row, that row again.
-__device__ __forceinline__ int enc_sample(const EncImage &E, int comp, int sx, int sy) {
+__device__ __forceinline__ int enc_sample(const EncGeom &E, int comp, int sx, int sy) {
     const int W1 = E.w - 1, H1 = E.h - 1;
     if (comp == 0 || E.hm == 1) return enc_ycc(E, comp, min(sx, W1), min(sy, H1));
     const int x0 = min(2 * sx, W1), x1 = min(2 * sx + 1, W1);
@@ -180,48 +184,53 @@ __device__ __forceinline__ void enc_fdct8(const int *d, int *o) {
 // ---- 1. blocks: samples, FDCT, quantisation, zigzag ------------------------------------------------
 // ENC_TILE blocks per workgroup, 8 threads per block: thread r makes the samples of row r and its
 // row pass, then column r's pass through LDS, then quantises zigzag positions 8r .. 8r + 7 and
-// stores them as one 16-byte word.
+// stores them as one 16-byte word.  enc_block is one such step of the whole workgroup: block b of
+// image E (live: there is one) goes to dst[0 .. 64); q are the quantisers.
+__device__ __forceinline__ void enc_block(const EncGeom &E, const uint8_t (*q)[64], int b, bool live,
+                                          int (*tile)[8][9], int16_t *__restrict__ dst) {
+    const int j = threadIdx.x >> 3, r = threadIdx.x & 7;
+    EncPlace p{0, 0, 0, false};
+    if (live) {
+        p = enc_place(E, b);
+        int d[8], o[8];
+        for (int c = 0; c < 8; ++c) d[c] = enc_sample(E, p.comp, 8 * p.bx + c, 8 * p.by + r) - 128;
+        enc_fdct8<true>(d, o);
+        for (int c = 0; c < 8; ++c) tile[j][r][c] = o[c];
+    }
+    __syncthreads();
+    if (live) {
+        int d[8], o[8];
+        for (int k = 0; k < 8; ++k) d[k] = tile[j][k][r];
+        enc_fdct8<false>(d, o);
+        for (int k = 0; k < 8; ++k) tile[j][k][r] = o[k];
+    }
+    __syncthreads();
+    if (live) {
+        const uint8_t *qc = q[p.comp ? 1 : 0];
+        int16_t v[8];
+        for (int i = 0; i < 8; ++i) {
+            const int k = 8 * r + i, n = kEncZigzag[k];
+            const int x = tile[j][n >> 3][n & 7], dq = 8 * qc[n];
+            const int a = ((x < 0 ? -x : x) + (dq >> 1)) / dq;
+            v[i] = (int16_t)(p.dummy && k ? 0 : x < 0 ? -a : a);
+        }
+        uint4 packed;
+        packed.x = (uint16_t)v[0] | (uint32_t)(uint16_t)v[1] << 16;
+        packed.y = (uint16_t)v[2] | (uint32_t)(uint16_t)v[3] << 16;
+        packed.z = (uint16_t)v[4] | (uint32_t)(uint16_t)v[5] << 16;
+        packed.w = (uint16_t)v[6] | (uint32_t)(uint16_t)v[7] << 16;
+        *(uint4 *)(dst + 8 * r) = packed;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_blocks_kernel(EncImage E,
                                                                     int16_t *__restrict__ coef) {
     __shared__ int tile[ENC_TILE][8][9];
-    const int j = threadIdx.x >> 3, r = threadIdx.x & 7;
     for (int64_t base = (int64_t)blockIdx.x * ENC_TILE; base < E.nblocks;
          base += (int64_t)gridDim.x * ENC_TILE) {
-        const int b = (int)base + j;
-        const bool live = b < E.nblocks;
-        EncPlace p{0, 0, 0, false};
-        if (live) {
-            p = enc_place(E, b);
-            int d[8], o[8];
-            for (int c = 0; c < 8; ++c) d[c] = enc_sample(E, p.comp, 8 * p.bx + c, 8 * p.by + r) - 128;
-            enc_fdct8<true>(d, o);
-            for (int c = 0; c < 8; ++c) tile[j][r][c] = o[c];
-        }
-        __syncthreads();
-        if (live) {
-            int d[8], o[8];
-            for (int k = 0; k < 8; ++k) d[k] = tile[j][k][r];
-            enc_fdct8<false>(d, o);
-            for (int k = 0; k < 8; ++k) tile[j][k][r] = o[k];
-        }
-        __syncthreads();
-        if (live) {
-            const uint8_t *q = E.q[p.comp ? 1 : 0];
-            int16_t v[8];
-            for (int i = 0; i < 8; ++i) {
-                const int k = 8 * r + i, n = kEncZigzag[k];
-                const int x = tile[j][n >> 3][n & 7], dq = 8 * q[n];
-                const int a = ((x < 0 ? -x : x) + (dq >> 1)) / dq;
-                v[i] = (int16_t)(p.dummy && k ? 0 : x < 0 ? -a : a);
-            }
-            uint4 packed;
-            packed.x = (uint16_t)v[0] | (uint32_t)(uint16_t)v[1] << 16;
-            packed.y = (uint16_t)v[2] | (uint32_t)(uint16_t)v[3] << 16;
-            packed.z = (uint16_t)v[4] | (uint32_t)(uint16_t)v[5] << 16;
-            packed.w = (uint16_t)v[6] | (uint32_t)(uint16_t)v[7] << 16;
-            *(uint4 *)(coef + 64 * (int64_t)b + 8 * r) = packed;
-        }
-        __syncthreads();
+        const int b = (int)base + (threadIdx.x >> 3);
+        enc_block(E, E.q, b, b < E.nblocks, tile, coef + 64 * (int64_t)b);
     }
 }
 
@@ -247,7 +256,7 @@ __device__ __forceinline__ void enc_put_value(EncCode &c, int v, int nb) {
 __device__ __forceinline__ int enc_nbits(int v) { return v ? 32 - __clz(v < 0 ? -v : v) : 0; }
 
 // the DC of the block before b of the same component in scan order (0 for its first block)
-__device__ __forceinline__ int enc_pred_dc(const EncImage &E, const int16_t *coef, int b) {
+__device__ __forceinline__ int enc_pred_dc(const EncGeom &E, const int16_t *coef, int b) {
     const int mcu = b / E.bpm, k = b - mcu * E.bpm, ny = E.hm * E.vm;
     int prev;
     if (k > 0 && k < ny) prev = b - 1;
@@ -256,7 +265,7 @@ __device__ __forceinline__ int enc_pred_dc(const EncImage &E, const int16_t *coe
     return coef[64 * (int64_t)prev];
 }
 
-__device__ __forceinline__ EncCode enc_lane_code(const EncImage &E, const int16_t *coef, int b,
+__device__ __forceinline__ EncCode enc_lane_code(const EncGeom &E, const int16_t *coef, int b,
                                                  int lane) {
     const int mcu = b / E.bpm, k = b - mcu * E.bpm;
     const int t = k < E.hm * E.vm ? 0 : 2;
@@ -337,44 +346,50 @@ __device__ __forceinline__ void enc_or_bits(uint32_t *lw, int p, uint64_t bits, 
     }
 }
 
+// enc_emit_block is one such step of the whole workgroup: the wave's block b of image E (live:
+// there is one; coef: the image's first block) has `nbits` bits and starts at bit b0 of raw; the
+// image's last block pads.  lw: the wave's ENC_WORDS words of LDS.
+__device__ __forceinline__ void enc_emit_block(const EncGeom &E, const int16_t *__restrict__ coef,
+                                               int b, bool live, int64_t b0, int nbits, bool last,
+                                               uint32_t *lw, uint32_t *__restrict__ raw) {
+    const int lane = threadIdx.x & 63;
+    lw[lane] = 0;
+    __syncthreads();
+    if (live) {
+        const EncCode c = enc_lane_code(E, coef, b, lane);
+        const int x = wave_scan_inclusive(c.n);
+        const int p = (int)(b0 & 31) + x - c.n;
+        enc_or_bits(lw, p, c.bits, c.n);
+        if (last) {
+            const int pad = (int)(-(b0 + nbits) & 7);
+            if (lane == 63 && pad) enc_or_bits(lw, (int)(b0 & 31) + nbits, (1u << pad) - 1, pad);
+            nbits += pad;
+        }
+    }
+    __syncthreads();
+    if (live) {
+        const int nwords = (int)(((b0 & 31) + nbits + 31) >> 5);
+        uint32_t *dst = raw + (b0 >> 5);
+        for (int i = lane; i < nwords; i += 64) {
+            const uint32_t v = __builtin_bswap32(lw[i]);
+            if (i == 0 || i == nwords - 1) atomicOr(&dst[i], v);
+            else dst[i] = v;
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_emit_kernel(
     EncImage E, const int16_t *__restrict__ coef, const uint32_t *__restrict__ counts,
     const int64_t *__restrict__ off, const int64_t *__restrict__ part, uint32_t *__restrict__ raw) {
     __shared__ uint32_t words[ENC_WAVES][ENC_WORDS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    uint32_t *lw = words[wave];
+    const int wave = threadIdx.x >> 6;
     for (int64_t base = (int64_t)blockIdx.x * ENC_WAVES; base < E.nblocks;
          base += (int64_t)gridDim.x * ENC_WAVES) {
         const int64_t b = base + wave;
         const bool live = b < E.nblocks;
-        lw[lane] = 0;
-        __syncthreads();
-        int64_t b0 = 0;
-        int nbits = 0;
-        if (live) {
-            const EncCode c = enc_lane_code(E, coef, (int)b, lane);
-            const int x = wave_scan_inclusive(c.n);
-            b0 = enc_offset(off, part, b);
-            nbits = (int)counts[b];
-            const int p = (int)(b0 & 31) + x - c.n;
-            enc_or_bits(lw, p, c.bits, c.n);
-            if (b == E.nblocks - 1) {
-                const int pad = (int)(-(b0 + nbits) & 7);
-                if (lane == 63 && pad) enc_or_bits(lw, (int)(b0 & 31) + nbits, (1u << pad) - 1, pad);
-                nbits += pad;
-            }
-        }
-        __syncthreads();
-        if (live) {
-            const int nwords = (int)(((b0 & 31) + nbits + 31) >> 5);
-            uint32_t *dst = raw + (b0 >> 5);
-            for (int i = lane; i < nwords; i += 64) {
-                const uint32_t v = __builtin_bswap32(lw[i]);
-                if (i == 0 || i == nwords - 1) atomicOr(&dst[i], v);
-                else dst[i] = v;
-            }
-        }
-        __syncthreads();
+        enc_emit_block(E, coef, (int)b, live, live ? enc_offset(off, part, b) : 0,
+                       live ? (int)counts[b] : 0, b == E.nblocks - 1, words[wave], raw);
     }
 }
 
@@ -382,10 +397,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_emit_kernel(
 // count: the 0xFF bytes of each ENC_CHUNK-byte chunk (the buffer is zero past the stream, and a
 // zero is never counted); write (after the scan): each chunk's bytes at its shifted place, a 0x00
 // after every 0xFF.
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_count_kernel(
-    const uint32_t *__restrict__ raw, int64_t nchunks, uint32_t *__restrict__ counts) {
-    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
-    if (c >= nchunks) return;
+__device__ __forceinline__ uint32_t enc_chunk_ffs(const uint32_t *__restrict__ raw, int64_t c) {
     const uint4 *p = (const uint4 *)(raw + c * (ENC_CHUNK / 4));
     uint32_t n = 0;
     for (int i = 0; i < ENC_CHUNK / 16; ++i) {
@@ -394,7 +406,25 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_count_kernel(
         for (int k = 0; k < 4; ++k)
             for (int s = 0; s < 32; s += 8) n += ((w[k] >> s) & 0xFF) == 0xFF;
     }
-    counts[c] = n;
+    return n;
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_count_kernel(
+    const uint32_t *__restrict__ raw, int64_t nchunks, uint32_t *__restrict__ counts) {
+    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
+    if (c >= nchunks) return;
+    counts[c] = enc_chunk_ffs(raw, c);
+}
+
+// bytes [a, e) of raw to out[o ...], a 0x00 after every 0xFF; returns where the next byte goes
+__device__ __forceinline__ int64_t enc_stuff_bytes(const uint8_t *__restrict__ raw, int64_t a,
+                                                   int64_t e, uint8_t *__restrict__ out, int64_t o) {
+    for (int64_t i = a; i < e; ++i) {
+        const uint8_t v = raw[i];
+        out[o++] = v;
+        if (v == 0xFF) out[o++] = 0;
+    }
+    return o;
 }
 
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_write_kernel(
@@ -403,12 +433,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_write_kernel(
     const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
     if (c >= nchunks) return;
     const int64_t a = c * ENC_CHUNK, e = a + ENC_CHUNK < nbytes ? a + ENC_CHUNK : nbytes;
-    int64_t o = a + enc_offset(off, part, c);
-    for (int64_t i = a; i < e; ++i) {
-        const uint8_t v = raw[i];
-        out[o++] = v;
-        if (v == 0xFF) out[o++] = 0;
-    }
+    enc_stuff_bytes(raw, a, e, out, a + enc_offset(off, part, c));
 }
 
 // ---- the entry points ------------------------------------------------------------------------------
@@ -559,5 +584,311 @@ extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w,
     PANO_HIP(hipStreamSynchronize(s));
     *stream_out = host;
     *stream_bytes = out_bytes;
+    return PANO_OK;
+}
+
+// ---- the batch (pano_jpeg_encode_batch) ------------------------------------------------------------
+// The blocks of all images are numbered one after the other, image by image; first[i] is image
+// i's first block (first[n]: the total) and a workgroup finds a block's image by bisecting that
+// table, so the block-wise kernels above run unchanged on (image, block in the image) and their
+// workgroups straddle images freely.  The counts of all blocks are scanned together; an image's
+// bits are the difference of the offsets at its two ends.  Every image's raw bits start on a whole
+// stuffing chunk (chunk0[i], from a scan of the images' chunk counts), so no word, pad byte or 0xFF
+// of one image touches another's, and the stuffed streams are packed byte after byte: a chunk's
+// count is its stream bytes plus its 0xFF bytes, and the scan of those is the output position.
+struct EncDesc {
+    const uint8_t *img;
+    int64_t pitch;
+    int w, h, mx, my;
+    int wib[2], hib[2];
+};
+
+// the largest i in [0, n) with t[i] <= v (t ascending, t[0] <= v)
+template <class T>
+__device__ __forceinline__ int enc_find(const T *__restrict__ t, int n, T v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// image i's geometry: S holds what the batch shares (sampling, channel order)
+__device__ __forceinline__ EncGeom enc_batch_geom(const EncImage &S, const EncDesc *__restrict__ desc,
+                                                  const int *__restrict__ first, int i) {
+    const EncDesc d = desc[i];
+    EncGeom E = S;
+    E.img = d.img;
+    E.pitch = d.pitch;
+    E.w = d.w;
+    E.h = d.h;
+    E.mx = d.mx;
+    E.my = d.my;
+    E.wib[0] = d.wib[0];
+    E.wib[1] = d.wib[1];
+    E.hib[0] = d.hib[0];
+    E.hib[1] = d.hib[1];
+    E.nblocks = first[i + 1] - first[i];
+    return E;
+}
+
+// S.nblocks is the batch's total
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_blocks_kernel(
+    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
+    int16_t *__restrict__ coef) {
+    __shared__ int tile[ENC_TILE][8][9];
+    for (int64_t base = (int64_t)blockIdx.x * ENC_TILE; base < S.nblocks;
+         base += (int64_t)gridDim.x * ENC_TILE) {
+        const int g = (int)base + (threadIdx.x >> 3);
+        const bool live = g < S.nblocks;
+        const int i = live ? enc_find(first, n, g) : 0;
+        const EncGeom E = enc_batch_geom(S, desc, first, i);
+        enc_block(E, S.q, g - first[i], live, tile, coef + 64 * (int64_t)g);
+    }
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_count_kernel(
+    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
+    const int16_t *__restrict__ coef, uint32_t *__restrict__ counts) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int64_t g = (int64_t)blockIdx.x * ENC_WAVES + wave; g < S.nblocks;
+         g += (int64_t)gridDim.x * ENC_WAVES) {
+        const int i = enc_find(first, n, (int)g);
+        const EncGeom E = enc_batch_geom(S, desc, first, i);
+        const int16_t *ci = coef + 64 * (int64_t)first[i];
+        const int bits = wave_sum(enc_lane_code(E, ci, (int)g - first[i], lane).n);
+        if (lane == 0) counts[g] = (uint32_t)bits;
+    }
+}
+
+// per image: its stream's bytes before stuffing (the bits of its blocks, padded to a byte) and its
+// chunks.  nparts: the parts of the blocks' scan, part[nparts] their total.
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_images_kernel(
+    const int *__restrict__ first, int n, const int64_t *__restrict__ off,
+    const int64_t *__restrict__ part, int64_t nparts, int64_t *__restrict__ ibytes,
+    int64_t *__restrict__ ichunks) {
+    const int i = blockIdx.x * ENC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t a = enc_offset(off, part, first[i]);
+    const int64_t e = i + 1 < n ? enc_offset(off, part, first[i + 1]) : part[nparts];
+    const int64_t bytes = (e - a + 7) >> 3;
+    ibytes[i] = bytes;
+    ichunks[i] = (bytes + ENC_CHUNK - 1) / ENC_CHUNK;
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_emit_kernel(
+    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
+    const int16_t *__restrict__ coef, const uint32_t *__restrict__ counts,
+    const int64_t *__restrict__ off, const int64_t *__restrict__ part,
+    const int64_t *__restrict__ chunk0, uint32_t *__restrict__ raw) {
+    __shared__ uint32_t words[ENC_WAVES][ENC_WORDS];
+    const int wave = threadIdx.x >> 6;
+    for (int64_t base = (int64_t)blockIdx.x * ENC_WAVES; base < S.nblocks;
+         base += (int64_t)gridDim.x * ENC_WAVES) {
+        const int64_t g = base + wave;
+        const bool live = g < S.nblocks;
+        const int i = live ? enc_find(first, n, (int)g) : 0;
+        const EncGeom E = enc_batch_geom(S, desc, first, i);
+        const int f = first[i];
+        const int64_t b0 = live ? chunk0[i] * (8 * ENC_CHUNK) + enc_offset(off, part, g) -
+                                      enc_offset(off, part, f)
+                                : 0;
+        enc_emit_block(E, coef + 64 * (int64_t)f, (int)g - f, live, b0, live ? (int)counts[g] : 0,
+                       g == first[i + 1] - 1, words[wave], raw);
+    }
+}
+
+// the stream bytes of chunk c, which is image i's
+__device__ __forceinline__ int enc_chunk_bytes(const int64_t *__restrict__ chunk0,
+                                               const int64_t *__restrict__ ibytes, int i, int64_t c) {
+    const int64_t left = ibytes[i] - (c - chunk0[i]) * ENC_CHUNK;
+    return (int)(left < ENC_CHUNK ? left : ENC_CHUNK);
+}
+
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_stuff_count_kernel(
+    const uint32_t *__restrict__ raw, int64_t nchunks, const int64_t *__restrict__ chunk0,
+    const int64_t *__restrict__ ibytes, int n, uint32_t *__restrict__ counts) {
+    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
+    if (c >= nchunks) return;
+    const int i = enc_find(chunk0, n, c);
+    counts[c] = (uint32_t)enc_chunk_bytes(chunk0, ibytes, i, c) + enc_chunk_ffs(raw, c);
+}
+
+// out: int64 offsets[n + 1] of the images' streams, then (at out + head) the streams
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_stuff_write_kernel(
+    const uint8_t *__restrict__ raw, int64_t nchunks, const int64_t *__restrict__ chunk0,
+    const int64_t *__restrict__ ibytes, int n, const int64_t *__restrict__ off,
+    const int64_t *__restrict__ part, uint8_t *__restrict__ out, int64_t head) {
+    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
+    if (c >= nchunks) return;
+    const int i = enc_find(chunk0, n, c);
+    const int64_t a = c * ENC_CHUNK, o = enc_offset(off, part, c);
+    const int64_t end = enc_stuff_bytes(raw, a, a + enc_chunk_bytes(chunk0, ibytes, i, c), out + head, o);
+    int64_t *offsets = (int64_t *)out;
+    if (c == chunk0[i]) offsets[i] = o;
+    if (c == nchunks - 1) offsets[n] = end;
+}
+
+// the scratch of pano_jpeg_encode_batch: EncWork, then the first-block table, the descriptors (the
+// two are uploaded as one), the images' bytes and their chunks (scanned in place)
+struct EncBatchWork {
+    EncWork w;
+    int64_t first, desc, ibytes, ichunks, bytes;
+    int64_t table_bytes;            // first and desc
+};
+static EncBatchWork enc_batch_work(int64_t nblocks, int64_t n) {
+    EncBatchWork b;
+    b.w = enc_work(nblocks);
+    b.first = b.w.bytes;
+    b.desc = b.first + align_up(4 * (n + 1));
+    b.ibytes = b.desc + align_up((int64_t)sizeof(EncDesc) * n);
+    b.table_bytes = b.ibytes - b.first;
+    b.ichunks = b.ibytes + align_up(8 * n);
+    b.bytes = b.ichunks + align_up(8 * (n + 1));
+    return b;
+}
+
+extern "C" size_t pano_jpeg_encode_batch_work_bytes(int64_t blocks, int n) {
+    if (blocks < 1 || blocks > PANO_JPEG_BATCH_MAX_BLOCKS || n < 1 || n > PANO_JPEG_BATCH_MAX) return 0;
+    return (size_t)enc_batch_work(blocks, n).bytes;
+}
+
+extern "C" int pano_jpeg_encode_batch(pano_ctx *ctx, const pano_jpeg_image *images, int n, int flags,
+                                      int subsampling, const uint8_t *qt, void *work,
+                                      int64_t work_bytes, const uint8_t **streams,
+                                      const int64_t **offsets) {
+    PANO_ENTER(ctx, "pano_jpeg_encode_batch");
+    PANO_REQUIRE(images && qt && work && streams && offsets, "pano_jpeg_encode_batch: null pointer");
+    *streams = nullptr;
+    *offsets = nullptr;
+    PANO_REQUIRE(n >= 1 && n <= PANO_JPEG_BATCH_MAX, "pano_jpeg_encode_batch: %d images (1..%d)", n,
+                 PANO_JPEG_BATCH_MAX);
+    PANO_REQUIRE((flags & ~PANO_JPEG_BGR) == 0, "pano_jpeg_encode_batch: flags %d", flags);
+    for (int i = 0; i < 128; ++i)
+        PANO_REQUIRE(qt[i] >= 1, "pano_jpeg_encode_batch: quantiser %d is 0", i);
+    EncImage S{};
+    int64_t nb = 0;
+    for (int i = 0; i < n; ++i) {
+        const pano_jpeg_image &m = images[i];
+        PANO_REQUIRE(m.img && enc_geometry(m.h, m.w, subsampling, S),
+                     "pano_jpeg_encode_batch: image %d: %d x %d at %p, subsampling %d (1..%d per "
+                     "side, 0..2)", i, m.w, m.h, (const void *)m.img, subsampling, PANO_JPEG_MAX_SIDE);
+        PANO_REQUIRE(m.pitch >= 3 * (int64_t)m.w, "pano_jpeg_encode_batch: image %d: pitch %lld for "
+                     "%d pixels", i, (long long)m.pitch, m.w);
+        nb += S.nblocks;
+        PANO_REQUIRE(nb <= PANO_JPEG_BATCH_MAX_BLOCKS, "pano_jpeg_encode_batch: more than %d blocks",
+                     PANO_JPEG_BATCH_MAX_BLOCKS);
+    }
+    const EncBatchWork L = enc_batch_work(nb, n);
+    PANO_REQUIRE(work_bytes >= L.bytes, "pano_jpeg_encode_batch: work of %lld bytes, %lld needed",
+                 (long long)work_bytes, (long long)L.bytes);
+
+    // the tables, staged in the pinned buffer (the last call's streams end here)
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], L.table_bytes, true)) return rc;
+    uint8_t *const stage = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
+    int *const hfirst = (int *)stage;
+    EncDesc *const hdesc = (EncDesc *)(stage + (L.desc - L.first));
+    nb = 0;
+    for (int i = 0; i < n; ++i) {
+        const pano_jpeg_image &m = images[i];
+        enc_geometry(m.h, m.w, subsampling, S);
+        hfirst[i] = (int)nb;
+        hdesc[i] = EncDesc{m.img, m.pitch, S.w, S.h, S.mx, S.my, {S.wib[0], S.wib[1]},
+                           {S.hib[0], S.hib[1]}};
+        nb += S.nblocks;
+    }
+    hfirst[n] = (int)nb;
+    S.img = nullptr;
+    S.pitch = 0;
+    S.nblocks = (int)nb;
+    S.bgr = flags & PANO_JPEG_BGR;
+    for (int i = 0; i < 128; ++i) S.q[i >> 6][i & 63] = qt[i];
+    const hipStream_t s = (hipStream_t)stream;
+    uint8_t *w8 = (uint8_t *)work;
+    int16_t *coef = (int16_t *)(w8 + L.w.coef);
+    uint32_t *counts = (uint32_t *)(w8 + L.w.counts);
+    int64_t *offs = (int64_t *)(w8 + L.w.offs), *parts = (int64_t *)(w8 + L.w.parts);
+    const int *first = (const int *)(w8 + L.first);
+    const EncDesc *desc = (const EncDesc *)(w8 + L.desc);
+    int64_t *ibytes = (int64_t *)(w8 + L.ibytes), *chunk0 = (int64_t *)(w8 + L.ichunks);
+    const int64_t nbparts = ceil_div(nb, ENC_SCAN_TILE);
+    PANO_HIP(hipMemcpyAsync(w8 + L.first, stage, L.table_bytes, hipMemcpyHostToDevice, s));
+
+    // 1. blocks, 2. bit counts, 3. their scan, the images' bytes and chunks; wait for the chunks
+    PANO_TIMED(PK_JPEG_ENC_BLOCKS, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_blocks_kernel, enc_groups(nb, ENC_TILE),
+                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, coef));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_blocks_kernel");
+    PANO_TIMED(PK_JPEG_ENC_COUNT, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_count_kernel, enc_groups(nb, ENC_WAVES),
+                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, (const int16_t *)coef,
+                                  counts));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_count_kernel");
+    if (int rc = enc_scan(ctx, s, counts, nb, offs, parts)) return rc;
+    PANO_TIMED(PK_JPEG_ENC_SCAN, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_images_kernel, dim3(ceil_div(n, ENC_BLOCK)),
+                                  dim3(ENC_BLOCK), 0, s, first, n, (const int64_t *)offs,
+                                  (const int64_t *)parts, nbparts, ibytes, chunk0));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_images_kernel");
+    PANO_TIMED(PK_JPEG_ENC_SCAN, s,
+               hipLaunchKernelGGL((scan_exclusive_kernel<ENC_SCAN, int64_t>), dim3(1), dim3(ENC_SCAN),
+                                  0, s, (const int64_t *)chunk0, (int64_t)n, chunk0));
+    PANO_LAUNCH_CHECK("scan_exclusive_kernel");
+    int64_t nchunks = 0;
+    PANO_HIP(hipMemcpyAsync(&nchunks, chunk0 + n, 8, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipStreamSynchronize(s));
+    PANO_REQUIRE(nchunks >= n && nchunks < ((int64_t)1 << 34), "pano_jpeg_encode_batch: %lld chunks",
+                 (long long)nchunks);
+
+    // the stream buffer: raw words (whole chunks, zeroed), the chunks' counts and offsets
+    const int64_t raw_bytes = align_up(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
+                  off_at = cnt_at + align_up(4 * nchunks), part_at = off_at + align_up(8 * nchunks),
+                  ncparts = ceil_div(nchunks, ENC_SCAN_TILE),
+                  dev_bytes = part_at + align_up(8 * (ncparts + 1));
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_DEV], dev_bytes, false, dev_bytes / 4)) return rc;
+    uint8_t *const dev = (uint8_t *)ctx->buf[BUF_ENC_DEV].p;
+    uint32_t *raw = (uint32_t *)dev;
+    uint32_t *ccount = (uint32_t *)(dev + cnt_at);
+    int64_t *coff = (int64_t *)(dev + off_at), *cpart = (int64_t *)(dev + part_at);
+    PANO_HIP(hipMemsetAsync(raw, 0, raw_bytes, s));
+
+    // 4. emission, 5. the chunks' output bytes and their scan; wait for the stuffed size
+    PANO_TIMED(PK_JPEG_ENC_EMIT, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_emit_kernel, enc_groups(nb, ENC_WAVES),
+                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, (const int16_t *)coef,
+                                  (const uint32_t *)counts, (const int64_t *)offs,
+                                  (const int64_t *)parts, (const int64_t *)chunk0, raw));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_emit_kernel");
+    const dim3 cgrid((unsigned)ceil_div(nchunks, ENC_BLOCK));
+    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_stuff_count_kernel, cgrid, dim3(ENC_BLOCK), 0, s,
+                                  (const uint32_t *)raw, nchunks, (const int64_t *)chunk0,
+                                  (const int64_t *)ibytes, n, ccount));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_stuff_count_kernel");
+    if (int rc = enc_scan(ctx, s, ccount, nchunks, coff, cpart)) return rc;
+    int64_t out_bytes = 0;
+    PANO_HIP(hipMemcpyAsync(&out_bytes, cpart + ncparts, 8, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipStreamSynchronize(s));
+    PANO_REQUIRE(out_bytes >= n && out_bytes <= 2 * nchunks * ENC_CHUNK,
+                 "pano_jpeg_encode_batch: %lld stuffed bytes", (long long)out_bytes);
+    const int64_t head = align_up(8 * ((int64_t)n + 1)), all_bytes = head + out_bytes;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_OUT], all_bytes, false, all_bytes / 4)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], all_bytes, true, all_bytes / 4)) return rc;
+    uint8_t *const out = (uint8_t *)ctx->buf[BUF_ENC_OUT].p;
+    uint8_t *const host = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
+    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
+               hipLaunchKernelGGL(jpeg_enc_batch_stuff_write_kernel, cgrid, dim3(ENC_BLOCK), 0, s,
+                                  (const uint8_t *)raw, nchunks, (const int64_t *)chunk0,
+                                  (const int64_t *)ibytes, n, (const int64_t *)coff,
+                                  (const int64_t *)cpart, out, head));
+    PANO_LAUNCH_CHECK("jpeg_enc_batch_stuff_write_kernel");
+
+    // the download: the offsets and the streams in one copy
+    PANO_HIP(hipMemcpyAsync(host, out, all_bytes, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipStreamSynchronize(s));
+    *offsets = (const int64_t *)host;
+    *streams = host + head;
     return PANO_OK;
 }

@@ -518,7 +518,7 @@ def read_images(paths, eng=None, max_packed=BATCH_PACKED, max_work=BATCH_WORK,
     return frames, route
 
 
-# ---- encode (``pano_jpeg_encode``, csrc/jpeg_enc.hip) -----------------------------------------
+# ---- encode (``pano_jpeg_encode``, ``pano_jpeg_encode_batch``, csrc/jpeg_enc.hip) -------------
 # Baseline, 8-bit, YCbCr from RGB, one interleaved scan, no restart markers, the Annex K tables:
 # what Pillow's ``Image.save(f, "JPEG")`` writes (libjpeg-turbo's defaults), byte for byte.
 
@@ -655,6 +655,101 @@ def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_c
     coefs = torch.empty_like(zz)
     coefs[:, torch.from_numpy(ZIGZAG.astype(np.int64)).to(dev)] = zz
     return data, coefs
+
+
+def encode_blocks(h, w, subsampling=-1):
+    """Blocks of an h x w image's scan (dummy blocks included): MCUs x blocks per MCU."""
+    hm, vm = SUBSAMPLING[subsampling]
+    return -(-w // (8 * hm)) * -(-h // (8 * vm)) * (hm * vm + 2)
+
+
+def plan_encode_batches(blocks, max_work=BATCH_WORK, work_bytes=None):
+    """Split images, given their ``encode_blocks``, in order into native calls: lists of indices,
+    each within ``max_work`` scratch bytes (``work_bytes(blocks, n)``, by default
+    ``pano_jpeg_encode_batch_work_bytes``), ``JPEG_BATCH_MAX`` images and
+    ``JPEG_BATCH_MAX_BLOCKS`` blocks.  Raises ValueError for an image that fits no call alone."""
+    from . import _lib
+    if work_bytes is None:
+        native = _lib.lib().pano_jpeg_encode_batch_work_bytes
+        work_bytes = lambda b, n: int(native(C.c_int64(b), n))       # noqa: E731
+
+    def fits(b, n):
+        return n <= _lib.JPEG_BATCH_MAX and b <= _lib.JPEG_BATCH_MAX_BLOCKS \
+            and work_bytes(b, n) <= max_work
+
+    batches, cur, cur_blocks = [], [], 0
+    for i, b in enumerate(blocks):
+        if not fits(b, 1):
+            raise ValueError(f"image {i} of {b} blocks fits no batch of {max_work} scratch bytes")
+        if cur and not fits(cur_blocks + b, len(cur) + 1):
+            batches.append(cur)
+            cur, cur_blocks = [], 0
+        cur.append(i)
+        cur_blocks += b
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=None,
+                        max_work=BATCH_WORK):
+    """One JPEG file (``bytes``) per image of ``images``, a list of uint8 [h][w][3] device tensors
+    or views of any sizes (a host array is uploaded): each equals ``encode_device`` of that image.
+    A crop view whose rows' pixels are contiguous is coded in place.  The list is cut, in order,
+    into native calls (``plan_encode_batches``); ``pano_jpeg_encode_batch`` codes a call's images
+    together and waits on the stream twice and downloads once, however many they are.  An empty
+    list gives [].  Raises ValueError, before anything is queued, for an image ``encodable``
+    rejects."""
+    import torch
+    from . import _lib
+    from . import engine as _eng
+    images = list(images)
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
+    for i, img in enumerate(images):
+        if not hasattr(img, "shape") or not encodable(img, quality, subsampling):
+            raise ValueError(f"image {i}: {tuple(getattr(img, 'shape', ()))} "
+                             f"{getattr(img, 'dtype', type(img))} at quality {quality}, "
+                             f"subsampling {subsampling}: not a case the device encodes")
+    if not images:
+        return []
+    shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
+    blocks = [encode_blocks(h, w, subsampling) for h, w in shapes]
+    batches = plan_encode_batches(blocks, max_work)
+    eng = eng or _eng.engine()
+    dev = torch.device(eng.device)
+    lib = eng.lib
+    sub = 2 if subsampling == -1 else subsampling
+    qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
+    files = []
+    for batch in batches:
+        held = []                                       # uploads and copies live until the call ends
+        table = (_lib.JpegImage * len(batch))()
+        for rec, i in zip(table, batch):
+            img = images[i]
+            if not isinstance(img, torch.Tensor):
+                img = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+            elif img.device != dev:
+                img = img.to(dev)
+            h, w = shapes[i]
+            if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * w:
+                img = img.contiguous()
+            held.append(img)
+            rec.img, rec.pitch, rec.h, rec.w = img.data_ptr(), img.stride(0), h, w
+        total = sum(blocks[i] for i in batch)
+        work_bytes = int(lib.pano_jpeg_encode_batch_work_bytes(C.c_int64(total), len(batch)))
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        streams, offsets = C.c_void_p(), C.c_void_p()
+        _lib.check(lib.pano_jpeg_encode_batch(
+            eng.ctx(), table, len(batch), 1 if order == "bgr" else 0, sub,
+            qt.ctypes.data_as(C.c_void_p), _eng._ptr(work), C.c_int64(work_bytes),
+            C.byref(streams), C.byref(offsets)), "pano_jpeg_encode_batch")
+        offs = (C.c_int64 * (len(batch) + 1)).from_address(offsets.value)
+        for k, i in enumerate(batch):
+            h, w = shapes[i]
+            files.append(encode_header(w, h, quality, subsampling)
+                         + C.string_at(streams.value + offs[k], offs[k + 1] - offs[k]) + b"\xff\xd9")
+    return files
 
 
 def write(path, img, quality=75, subsampling=-1, order="bgr", eng=None):

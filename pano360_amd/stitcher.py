@@ -411,9 +411,21 @@ def parse_args(argv=None):
                              "<out>_equirect.")
     parser.add_argument("--cube", type=_positive, metavar="SIDE",
                         help="also save the six cube faces as <out>_cube_<face>.")
+    parser.add_argument("--deepzoom", action="store_true",
+                        help="also save the mosaic as a Deep Zoom tile pyramid: <out>.dzi and "
+                             "<out>_files/.")
+    parser.add_argument("--multires", type=_positive, metavar="SIDE",
+                        help="also save the sphere as a multiresolution cube of at most this "
+                             "side, with its config.json, in <out>_multires/.")
+    parser.add_argument("--tile", type=_positive, default=512, metavar="N",
+                        help="tile side of --deepzoom and --multires (default 512).")
     args = parser.parse_args(argv)
     if (args.view or args.equirect or args.cube) and not args.out:
         parser.error("--view, --equirect and --cube need -o")
+    if (args.deepzoom or args.multires) and not args.out:
+        parser.error("--deepzoom and --multires need -o")
+    if args.multires and args.multires < args.tile:
+        parser.error("--multires: a side of at least --tile")
     if args.equirect and args.equirect % 2:
         parser.error("--equirect: an even width")
     return args
@@ -467,6 +479,7 @@ def main(argv=None):
     if args.out:
         _save(args.out, dev_mosaic, rect, mosaic)
         _save_views(args, dev_mosaic, rect, geom)
+        _save_tiles(args, dev_mosaic, rect, geom)
     return mosaic
 
 
@@ -501,6 +514,28 @@ def _save_views(args, dev_mosaic, rect, geom):
     for (path, _), image in zip(outputs, images):
         _save(path, image, None, None)
     logging.info(f"Rendered {len(outputs)} views, time: {time.time() - start}")
+
+
+def _save_tiles(args, dev_mosaic, rect, geom):
+    """The tile pyramids the command line asks for (``tiles.write_deepzoom``: ``<stem>.dzi`` and
+    ``<stem>_files/``; ``tiles.write_multires``: ``<stem>_multires/``), from the mosaic
+    ``_save_views`` uses, through one mip chain."""
+    if not (args.deepzoom or args.multires):
+        return
+    from . import tiles as _tiles
+    from . import view as _view
+    start = time.time()
+    if rect is not None:
+        y0, x0, h, w = rect
+        dev_mosaic, geom = dev_mosaic[y0:y0 + h, x0:x0 + w, :], geom.cropped(rect)
+    stem = os.path.splitext(args.out)[0]
+    mips = _view.mip_device(dev_mosaic)
+    written = []
+    if args.deepzoom:
+        written += _tiles.write_deepzoom(stem, mips, args.tile)
+    if args.multires:
+        written += _tiles.write_multires(f"{stem}_multires", mips, geom, args.multires, args.tile)
+    logging.info(f"Wrote {len(written)} tile files, time: {time.time() - start}")
 
 
 def _save(path, dev_mosaic, rect, mosaic):
