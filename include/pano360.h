@@ -1220,6 +1220,40 @@ int pano_mip_u8(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch, 
 int pano_view_render(pano_ctx *ctx, const uint8_t *mips, const int64_t *offsets, int n_levels,
                      const pano_view_mosaic *mosaic, const pano_view *views, int n);
 
+/* Filling what no frame covers          (the reference leaves it black or cuts it away with --crop,
+ * stitcher.py:340-369; csrc/fill.hip, float64 statement: tests/fill_model.py)
+ * pano_fill_u8: pull-push fill of the invalid pixels of a uint8 [h][w][3] image.  img, mask
+ *     (uint8 [h][w], nonzero = valid), out: dev, rows img_pitch / mask_pitch / out_pitch bytes apart;
+ *     out may be img (same pitch): then only the invalid pixels are written.  closed: column w is
+ *     column 0.  Sides 1 .. PANO_VIEW_MAX_SIDE.
+ *     Levels: S_0 = (h, w), S_{l+1} = ((h_l + 1) / 2, (w_l + 1) / 2) down to 1 x 1 (the chain of
+ *     pano_mip_u8); levels >= 1 are float32, one rounding per operation.
+ *     Pull: v_0 = mask != 0, c_0 = img.  Pixel (Y, X) of level l + 1 has the children
+ *     (2Y + dy, 2X + dx), dy, dx in {0, 1}, that lie inside S_l (no clamp, no wrap); it is valid if
+ *     any child is, and its colour is the sum of the valid children's colours, taken in the order
+ *     (0,0), (0,1), (1,0), (1,1), divided by their count (0 when there is none).
+ *     Push: f_top = c_top; from the top down a valid pixel keeps f_l = c_l and an invalid pixel
+ *     (y, x) takes 0.5625 f(Y, X) + 0.1875 f(Y, X') + 0.1875 f(Y', X) + 0.0625 f(Y', X') of level
+ *     l + 1, added left to right, with Y = y >> 1, X = x >> 1, Y' = Y + (y & 1 ? 1 : -1) clamped to
+ *     the level, X' = X + (x & 1 ? 1 : -1) clamped (open) or modulo w_{l+1} (closed).
+ *     Output: valid pixels are the input's bytes, invalid ones clamp(floor(f_0 + 0.5), 0, 255); an
+ *     image without a valid pixel comes back as it is.
+ *     One launch per pulled level of more than PANO_FILL_TAIL_PIXELS pixels, one workgroup that
+ *     takes the first level of at most that many down to 1 x 1 and back up in LDS, one launch per
+ *     pushed level above it.  The levels live in a buffer of the context, which grows on demand (the
+ *     call then waits for the stream first); otherwise asynchronous on the stream.  No atomics: the
+ *     same input gives the same bytes.
+ *     On a closed image whose width is odd at some level the modulo joins a slightly stretched
+ *     seam (as pano_view_render's).  The fill works in the image plane: on an equirectangular image
+ *     it is smooth near a pole, not isotropic.
+ * pano_select_u8: out = mask ? a : b per pixel of two dense uint8 [n_pixels][3] images; mask uint8
+ *     [n_pixels], nonzero = a.  out may be a or b.  One launch, asynchronous. */
+#define PANO_FILL_TAIL_PIXELS 4096
+int pano_fill_u8(pano_ctx *ctx, const uint8_t *img, int64_t img_pitch, const uint8_t *mask,
+                 int64_t mask_pitch, int h, int w, int closed, uint8_t *out, int64_t out_pitch);
+int pano_select_u8(pano_ctx *ctx, const uint8_t *a, const uint8_t *mask, const uint8_t *b,
+                   uint8_t *out, int64_t n_pixels);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -90,6 +90,8 @@ EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says
 # pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
 VIEW_MAX_LEVELS = 16
 VIEW_MAX_VIEWS = 32
+# pano_fill_u8: PANO_FILL_TAIL_PIXELS
+FILL_TAIL_PIXELS = 4096
 # pano_jpeg_encode_batch: PANO_JPEG_BATCH_MAX, PANO_JPEG_BATCH_MAX_BLOCKS
 JPEG_BATCH_MAX = 16384
 JPEG_BATCH_MAX_BLOCKS = 1 << 28
@@ -237,6 +239,8 @@ _SIGNATURES = {
     "pano_mip_u8": (_i, [_vp, _vp, _i, _i, C.c_int64, _vp, C.POINTER(C.c_int64), _i]),
     "pano_view_render": (_i, [_vp, _vp, C.POINTER(C.c_int64), _i, C.POINTER(ViewMosaic),
                               C.POINTER(View), _i]),
+    "pano_fill_u8": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64]),
+    "pano_select_u8": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

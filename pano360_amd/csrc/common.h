@@ -154,6 +154,8 @@ enum PanoBufId {
     // copy (what the call returns)
     BUF_PNG_DEV,
     BUF_PNG_HOST,
+    // pano_fill_u8 (fill.hip): the "any pixel valid" word and the float32 levels >= 1 (fill_layout.h)
+    BUF_FILL_DEV,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it

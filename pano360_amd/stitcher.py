@@ -238,6 +238,14 @@ def _stitch_device_geometry(regions, blender, equalize, crop):
     """``_stitch_device`` and, third, the ``view.MosaicGeometry`` of the whole mosaic (where its
     pixels lie on the sphere: the plan's ``low``, ``resolution`` and ``shape``); the cropped
     mosaic's is ``geometry.cropped(rect)``."""
+    return _stitch_device_valid(regions, blender, equalize, crop, False)[:3]
+
+
+def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True):
+    """``_stitch_device_geometry`` and, fourth, the valid mask the stitch computes (uint8 [H][W] on
+    the device, 1 = some frame covers the pixel): ``eng.stitch``'s third result, or
+    ``eng.ownership`` of the warped patches for a custom blender, as under ``crop``.  Without
+    ``want_valid`` a custom blender's mask is only computed for the crop (else None)."""
     from . import view as _view
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
@@ -269,15 +277,15 @@ def _stitch_device_geometry(regions, blender, equalize, crop):
         valid = None
         mosaic = blender(_download_patches(patches), plan.shape)
     rect = None
+    if valid is None and (crop or want_valid):
+        table = _eng.patch_table(patches, eng)
+        _, valid = eng.ownership(table, plan.shape)
     if crop:
         logging.debug("Cropping...")
-        if valid is None:
-            table = _eng.patch_table(patches, eng)
-            _, valid = eng.ownership(table, plan.shape)
         rect = eng.crop_rect(valid)
         if rect is None:
             raise UnboundLocalError("local variable 'last' referenced before assignment")
-    return mosaic, rect, _view.MosaicGeometry.of_plan(plan)
+    return mosaic, rect, _view.MosaicGeometry.of_plan(plan), valid
 
 
 def _download_cropped(mosaic, rect):
@@ -419,7 +427,13 @@ def parse_args(argv=None):
                              "side, with its config.json, in <out>_multires/.")
     parser.add_argument("--tile", type=_positive, default=512, metavar="N",
                         help="tile side of --deepzoom and --multires (default 512).")
+    parser.add_argument("--fill", action="store_true",
+                        help="fill what no frame covers from the pixels around it: the saved "
+                             "mosaic and --deepzoom show no ragged border, and --view, --equirect, "
+                             "--cube and --multires no black outside the mosaic (not with --crop).")
     args = parser.parse_args(argv)
+    if args.fill and args.crop:
+        parser.error("--fill and --crop exclude each other: a cropped mosaic has nothing to fill")
     if (args.view or args.equirect or args.cube) and not args.out:
         parser.error("--view, --equirect and --cube need -o")
     if (args.deepzoom or args.multires) and not args.out:
@@ -472,15 +486,37 @@ def main(argv=None):
                 reg.img = frame
 
     start = time.time()
-    dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend], args.equalize,
-                                                     args.crop)
+    background = None
+    if args.fill:
+        dev_mosaic, rect, geom, valid = _stitch_device_valid(regions, BLENDERS[args.blend],
+                                                             args.equalize, False)
+        dev_mosaic, background = _filled(args, dev_mosaic, geom, valid)
+    else:
+        dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend],
+                                                         args.equalize, args.crop)
     mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
         _save(args.out, dev_mosaic, rect, mosaic)
-        _save_views(args, dev_mosaic, rect, geom)
-        _save_tiles(args, dev_mosaic, rect, geom)
+        _save_views(args, dev_mosaic, rect, geom, background)
+        _save_tiles(args, dev_mosaic, rect, geom, background)
     return mosaic
+
+
+def _filled(args, dev_mosaic, geom, valid):
+    """--fill: the mosaic with its uncovered pixels filled (``fill.fill_device``; a custom
+    blender's host mosaic is uploaded) and, when a view of the sphere is asked for, the background
+    those views are composited over: (``view.Mips``, geometry) of ``fill.sphere_device``."""
+    from . import fill as _fill
+    from . import view as _view
+    start = time.time()
+    filled = _fill.fill_device(dev_mosaic, valid, geom.closed)
+    background = None
+    if args.out and (args.view or args.equirect or args.cube or args.multires):
+        sphere, sphere_geom = _fill.sphere_device(filled, geom)
+        background = (_view.mip_device(sphere), sphere_geom)
+    logging.info(f"Filled the mosaic, time: {time.time() - start}")
+    return filled, background
 
 
 def view_outputs(args):
@@ -499,9 +535,10 @@ def view_outputs(args):
     return out
 
 
-def _save_views(args, dev_mosaic, rect, geom):
+def _save_views(args, dev_mosaic, rect, geom, background=None):
     """Renders the views the command line asks for from the mosaic (the cropped one with --crop;
-    a custom blender's host mosaic is uploaded) in one launch, and writes them like the mosaic."""
+    a custom blender's host mosaic is uploaded) in one launch, and writes them like the mosaic.
+    ``background`` (--fill): what the mosaic does not cover comes from that sphere."""
     from . import view as _view
     outputs = view_outputs(args)
     if not outputs:
@@ -510,13 +547,17 @@ def _save_views(args, dev_mosaic, rect, geom):
     if rect is not None:
         y0, x0, h, w = rect
         dev_mosaic, geom = dev_mosaic[y0:y0 + h, x0:x0 + w, :], geom.cropped(rect)
-    images, _ = _view.render_device(dev_mosaic, geom, [v for _, v in outputs])
+    if background is None:
+        images, _ = _view.render_device(dev_mosaic, geom, [v for _, v in outputs])
+    else:
+        from . import fill as _fill
+        images, _ = _fill.render_filled_device(dev_mosaic, geom, [v for _, v in outputs], background)
     for (path, _), image in zip(outputs, images):
         _save(path, image, None, None)
     logging.info(f"Rendered {len(outputs)} views, time: {time.time() - start}")
 
 
-def _save_tiles(args, dev_mosaic, rect, geom):
+def _save_tiles(args, dev_mosaic, rect, geom, background=None):
     """The tile pyramids the command line asks for (``tiles.write_deepzoom``: ``<stem>.dzi`` and
     ``<stem>_files/``; ``tiles.write_multires``: ``<stem>_multires/``), from the mosaic
     ``_save_views`` uses, through one mip chain."""
@@ -534,7 +575,8 @@ def _save_tiles(args, dev_mosaic, rect, geom):
     if args.deepzoom:
         written += _tiles.write_deepzoom(stem, mips, args.tile)
     if args.multires:
-        written += _tiles.write_multires(f"{stem}_multires", mips, geom, args.multires, args.tile)
+        written += _tiles.write_multires(f"{stem}_multires", mips, geom, args.multires, args.tile,
+                                         background=background)
     logging.info(f"Wrote {len(written)} tile files, time: {time.time() - start}")
 
 

@@ -141,25 +141,37 @@ def multires_config(side, tile):
                          "cubeResolution": cube}}
 
 
-def multires_tiles(mips, geom, side, tile, eng=None):
+def multires_tiles(mips, geom, side, tile, eng=None, background=None):
     """(names, crop views) of ``multires_files``: the faces of a level are one
-    ``view.render_device`` launch from the mip chain; device tensors, no copies."""
+    ``view.render_device`` launch from the mip chain; device tensors, no copies.  ``background`` =
+    (``view.Mips`` or image, geometry) of ``fill.sphere_device``: the faces are rendered through
+    ``fill.render_filled_device``, which takes what the mosaic does not cover from that sphere."""
     rows = multires_files(side, tile)
-    faces = {l: _view.render_device(mips, geom, _view.cube_faces(int(tile) << (l - 1)), eng)[0]
+    if background is None:
+        def render(views):
+            return _view.render_device(mips, geom, views, eng)[0]
+    else:
+        from . import fill as _fill
+        background = (_mips(background[0], eng), background[1])
+
+        def render(views):
+            return _fill.render_filled_device(mips, geom, views, background, eng)[0]
+    faces = {l: render(_view.cube_faces(int(tile) << (l - 1)))
              for l in range(1, multires_levels(side, tile)[1] + 1)}
     return [r[0] for r in rows], [faces[l][face][y0:y0 + th, x0:x0 + tw]
                                   for _, l, face, y0, x0, th, tw in rows]
 
 
 def write_multires(directory, mosaic_or_mips, geom, side, tile=512, quality=75, eng=None,
-                   order="bgr"):
+                   order="bgr", background=None):
     """Writes the cube pyramid of a mosaic with geometry ``geom`` (``view.MosaicGeometry``) into
     ``directory``: ``config.json``, ``<l>/<s><row>_<col>.jpg`` and ``fallback/<s>.jpg``.  All
-    levels' tiles are coded together; tiles the mosaic does not cover are written too, black.
+    levels' tiles are coded together; tiles the mosaic does not cover are written too, black, or
+    from ``background`` (see ``multires_tiles``) when it is given.
     Returns the files written, the configuration first."""
     from . import jpeg as _jpeg
     config = multires_config(side, tile)                # (before anything is queued)
-    names, views = multires_tiles(_mips(mosaic_or_mips, eng), geom, side, tile, eng)
+    names, views = multires_tiles(_mips(mosaic_or_mips, eng), geom, side, tile, eng, background)
     blobs = _jpeg.encode_batch_device(views, quality, order=order, eng=eng)
     paths = [os.path.join(directory, "config.json")] + \
         [os.path.join(directory, *n.split("/")) for n in names]
