@@ -751,9 +751,13 @@ int pano_knn2(pano_ctx *ctx, const float *query, int nq, const float *train, int
  * order (a stable compaction) to pts (dev float [nq][4]: the query keypoint x, y, then its
  * nearest train keypoint's x, y) and match (dev int32 [nq][2]: q, idx[q][0]); their number goes
  * to *count (dev int32).  The capacity of pts / match is nq rows, so the caller sizes a pair's
- * region on the host with no wait.  idx, dist: dev [nq][2] of pano_knn2; kp_query, kp_train: dev
- * float [nq][2] / [nt][2] (centred keypoints); a train index outside [0, nt) never survives.
- * pts 16-byte aligned, dist and the keypoints 8-byte aligned.  One launch, nothing waited for. */
+ * region on the host with no wait; only the survivors' rows are written: rows *count .. nq - 1
+ * and everything behind them keep what they held, so pairs can be packed back to back in one
+ * buffer.  A NaN distance never survives (the comparison is false).  idx, dist: dev [nq][2] of
+ * pano_knn2 (idx[q][1] is not read); kp_query, kp_train: dev float [nq][2] / [nt][2] (centred
+ * keypoints); a train index outside [0, nt) never survives.  nq = 0: only *count = 0 is written
+ * and the other pointers may be null.  pts 16-byte aligned, dist and the keypoints 8-byte
+ * aligned.  One launch, nothing waited for; a refused call (PANO_EINVAL) writes nothing. */
 int pano_match_pack(pano_ctx *ctx, const int32_t *idx, const float *dist, int nq, double ratio,
                     const float *kp_query, const float *kp_train, int nt, float *pts,
                     int32_t *match, int32_t *count);

@@ -843,6 +843,17 @@ def _knn2_raw(des1, des2, eng, scale=None):
     return idx, dist, rescans
 
 
+def _ratio_test(dist, ratio):
+    """Queries that pass Lowe's ratio test, ascending: float64(dist[q, 0]) < ratio *
+    float64(dist[q, 1]), strict, as ``pano_match_pack`` compares and as the reference does on
+    Python floats (features.py:232).  dist: float32 [K][2].  Compared in float32, as NumPy would
+    on these arrays, ratio * dist[q, 1] is rounded once more and matches on the boundary are
+    lost."""
+    dist = np.asarray(dist).reshape(-1, 2).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.nonzero(dist[:, 0] < float(ratio) * dist[:, 1])[0]
+
+
 def flann_matching(des1, des2, ratio=0.7):
     """Given 2 lists of descriptors, match them (features.py:222-232): 2-NN + Lowe's
     ratio test.  Exact search instead of FLANN's approximate one."""
@@ -854,7 +865,7 @@ def flann_matching(des1, des2, ratio=0.7):
     d2 = torch.from_numpy(np.ascontiguousarray(des2, np.float32)).to(eng.device)
     idx, dist = knn2_device(d1, d2)
     idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
-    keep = np.nonzero(dist[:, 0] < ratio * dist[:, 1])[0]
+    keep = _ratio_test(dist, ratio)
     return [DMatch(q, idx[q, 0], dist[q, 0]) for q in keep]
 
 

@@ -6,7 +6,9 @@ The per-pair sums are formed as the contract states them (J from the ten tables 
 r at a second camera state, the pairs added in order); the per-camera algebra is the product's
 host helpers, which tests/test_bundle_host.py pins to the reference separately.  The CPU tests
 pin this model to tests/golden/ba_*.npz, so GPU tests at sizes too large for fixtures can
-compare against it.  Test helper only: the product never imports it."""
+compare against it.  A second restatement of the kernels (``ssq_ordered``, ``pair_sums_ordered``,
+``assemble_ordered``) follows the header's order of every addition and is compared with them bit
+for bit on ``forged_system``'s pair table.  Test helper only: the product never imports it."""
 import heapq
 from collections import defaultdict
 
@@ -317,3 +319,227 @@ def run_record(index, cams, adj):
             "m_opt_initial": np.array([h["initial"] for h in adj.history]),
             "m_opt_losses": np.array([x for h in adj.history for x in h["losses"]]),
             "m_rot": np.stack([c.rot for c in cams]), "m_intr": np.stack([c.intr for c in cams])}
+
+
+# ------------------------------------------------------------------ the contract's summation order
+# A second restatement of pano_ba_residuals and pano_ba_normal, this one in the header's order of
+# operations AND of additions, so that it can be compared with the kernels bit for bit.  Float64
+# arrays and elementwise operations only (each one IEEE operation per element, as the library's
+# build without contraction has it); no matrix product, no np.sum.
+BA_LANES = 256              # one block per pair
+BA_SUMS = 90                # 21 + 21 + 36 + 12 sums per pair
+
+
+def wave_sum_model(x):
+    """The xor butterfly over the last axis (64 lanes): x = x + x[lane ^ off] for off = 32, 16,
+    8, 4, 2, 1.  Every lane ends with the same bits; all 64 are returned."""
+    x = np.asarray(x, np.float64)
+    assert x.shape[-1] == 64
+    lane = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        x = x + x[..., lane ^ off]
+    return x
+
+
+def _mul_p(M, x, y):
+    """M p with p = (x, y, 1): (m0 x + m1 y) + m2 per row.  M: 9 values, row-major."""
+    return [(M[3 * r] * x + M[3 * r + 1] * y) + M[3 * r + 2] for r in range(3)]
+
+
+def _mul_v(M, v):
+    """M v: (m0 v0 + m1 v1) + m2 v2 per row."""
+    return [(M[3 * r] * v[0] + M[3 * r + 1] * v[1]) + M[3 * r + 2] * v[2] for r in range(3)]
+
+
+def _block_total(values):
+    """values [..., padded] with padded a multiple of 256 (idle lanes hold 0.0), chunk c in
+    [..., 256 c : 256 c + 256]: per chunk the butterfly per wave, added to the wave's running
+    total chunk by chunk; then the four totals in wave order."""
+    lead = values.shape[:-1]
+    chunks = values.reshape(lead + (-1, 4, 64))
+    total = np.zeros(lead + (4,))
+    for c in range(chunks.shape[-3]):
+        total = total + wave_sum_model(chunks[..., c, :, :])[..., 0]
+    s = total[..., 0]
+    for w in range(1, 4):
+        s = s + total[..., w]
+    return s
+
+
+def _padded(values, count):
+    """[..., count] -> [..., a multiple of 256 >= max(count, 256)], 0.0 in the idle lanes."""
+    size = max(-(-count // BA_LANES), 1) * BA_LANES
+    out = np.zeros(values.shape[:-1] + (size,))
+    out[..., :count] = values
+    return out
+
+
+def ssq_ordered(rows, pairs, hom):
+    """pano_ba_residuals in its summation order: lane t of 256 accumulates the pair's matches
+    t, t + 256, ... in order, each wave is summed by the butterfly, the four waves in order."""
+    rows, hom = np.asarray(rows, np.float64), np.asarray(hom, np.float64).reshape(-1, 9)
+    out = np.zeros(len(pairs))
+    with np.errstate(all="ignore"):
+        for p, (_, _, first, count) in enumerate(np.asarray(pairs).tolist()):
+            m = rows[first:first + count]
+            t = _mul_p(hom[p], m[:, 2], m[:, 3])
+            rx, ry = m[:, 0] - t[0] / t[2], m[:, 1] - t[1] / t[2]
+            val = _padded(rx * rx + ry * ry, count).reshape(-1, BA_LANES)
+            acc = np.zeros(BA_LANES)
+            for c in range(len(val)):
+                acc = acc + val[c]
+            waves = wave_sum_model(acc.reshape(4, 64))[:, 0]
+            s = waves[0]
+            for w in range(1, 4):
+                s = s + waves[w]
+            out[p] = s
+    return out
+
+
+def _columns(m, T, Hr):
+    """The 12 columns of J (jx, jy: [12][count]) and the residual (rx, ry) of one pair's matches
+    m [count][4], from the pair's ten tables T [90] and its residual homography Hr [9]."""
+    xb, yb, xa, ya = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    Hj, Sb, Sr, Kai = T[0:9], T[9:18], T[18:27], T[27:36]
+    N, Q = T[36:63], T[63:90]
+    zero = np.zeros_like(xa)
+    h = _mul_p(Hj, xa, ya)
+    iz = 1.0 / h[2]
+    d = (h[0] * iz * iz, h[1] * iz * iz, -iz)
+
+    def col(w):
+        return w[0] * d[2] + w[2] * d[0], w[1] * d[2] + w[2] * d[1]
+
+    s = _mul_p(Sb, xa, ya)
+    cols = [col((s[0], s[1], zero)), col((s[2], zero, zero)), col((zero, s[2], zero))]
+    t = _mul_p(Sr, xa, ya)
+    cols += [col(_mul_v(N[9 * k:9 * k + 9], t)) for k in range(3)]
+    q = _mul_p(Kai, xa, ya)
+    n = (-q[0], -q[1], -q[2])
+    cols.append(col([(Hj[3 * r] * n[0] + Hj[3 * r + 1] * n[1]) + 0.0 * n[2] for r in range(3)]))
+    cols.append(col([(0.0 * n[0] + 0.0 * n[1]) + Hj[3 * r] * n[2] for r in range(3)]))
+    cols.append(col([(0.0 * n[0] + 0.0 * n[1]) + Hj[3 * r + 1] * n[2] for r in range(3)]))
+    cols += [col(_mul_v(Q[9 * k:9 * k + 9], q)) for k in range(3)]
+    g = _mul_p(Hr, xa, ya)
+    rx, ry = xb - g[0] / g[2], yb - g[1] / g[2]
+    return np.stack([c[0] for c in cols]), np.stack([c[1] for c in cols]), rx, ry
+
+
+def pair_sums_ordered(rows, pairs, jtab, hom_r):
+    """ba_pair_kernel's work[n_pairs][90] in its summation order: [0..20] J_b^T J_b and [21..41]
+    J_a^T J_a (upper triangles, row-major), [42..77] J_b^T J_a, [78..89] J^T r."""
+    rows = np.asarray(rows, np.float64)
+    jtab = np.asarray(jtab, np.float64).reshape(-1, 90)
+    hom_r = np.asarray(hom_r, np.float64).reshape(-1, 9)
+    uv = [(u, v) for u in range(6) for v in range(u, 6)]
+    uv += [(u, v) for u in range(6, 12) for v in range(u, 12)]
+    uv += [(u, v) for u in range(6) for v in range(6, 12)]
+    out = np.zeros((len(pairs), BA_SUMS))
+    with np.errstate(all="ignore"):
+        for p, (_, _, first, count) in enumerate(np.asarray(pairs).tolist()):
+            jx, jy, rx, ry = _columns(rows[first:first + count], jtab[p], hom_r[p])
+            jx, jy, rx, ry = (_padded(v, count) for v in (jx, jy, rx, ry))
+            prod = [jx[u] * jx[v] + jy[u] * jy[v] for u, v in uv]
+            prod += [jx[c] * rx + jy[c] * ry for c in range(12)]
+            out[p] = _block_total(np.stack(prod))
+    return out
+
+
+def _tri(u, v):
+    u, v = min(u, v), max(u, v)
+    return u * 6 - u * (u - 1) // 2 + (v - u)
+
+
+def assemble_ordered(sums, pairs, slot, n_active, lam):
+    """ba_assemble_kernel: from 0.0, the pairs added in pair order (camera b's and camera a's
+    diagonal blocks, the cross block at (b, a) and its transpose at (a, b)), then lambda on the
+    diagonal.  Returns (jtj [6 n_active][6 n_active], jtr [6 n_active])."""
+    n = 6 * n_active
+    jtj, jtr = np.zeros((n, n)), np.zeros(n)
+    tri = np.array([[_tri(u, v) for v in range(6)] for u in range(6)])
+    for p, (a, b, _, _) in enumerate(np.asarray(pairs).tolist()):
+        S = np.asarray(sums[p], np.float64)
+        sa, sb = 6 * int(slot[a]), 6 * int(slot[b])
+        cross = S[42:78].reshape(6, 6)
+        jtj[sb:sb + 6, sb:sb + 6] += S[tri]
+        jtj[sa:sa + 6, sa:sa + 6] += S[21 + tri]
+        jtj[sb:sb + 6, sa:sa + 6] += cross
+        jtj[sa:sa + 6, sb:sb + 6] += cross.T
+        jtr[sb:sb + 6] += S[78:84]
+        jtr[sa:sa + 6] += S[84:90]
+    jtj[np.arange(n), np.arange(n)] += lam
+    return jtj, jtr
+
+
+# ------------------------------------------------------------------ a forged pair table
+FORGED_CAMERAS = 9
+FORGED_INACTIVE = (0, 4, 7)
+# (a, b, count): camera 5 takes part in six pairs (four times as a, twice as b); cameras 2 and 5
+# are paired twice, once in each order; the active cameras 2 and 6, and 3 and 8, share no pair
+FORGED_PAIRS = ((1, 2, 0), (5, 1, 1), (2, 5, 2), (3, 2, 63), (5, 3, 64), (6, 5, 65), (8, 6, 255),
+                (5, 8, 256), (5, 2, 257), (1, 3, 511), (8, 1, 513), (3, 6, 1000), (6, 1, 90),
+                (2, 8, 120))
+
+
+def forged_system(seed=20):
+    """The pair table the recorded runs never have: counts on both sides of the wave's 64 and the
+    block's 256 lanes, cameras left out and therefore slot[c] != c, a hub camera, a repeated pair,
+    regions stored in a shuffled order with rows of NaN before, between and after them (a read
+    outside a region poisons the result), and a residual state that differs from the Jacobian's.
+    Returns a dict: rows [m][4], pairs int32 [14][4], slot int32 [9], n_active, jtab [14][90],
+    hom_j / hom_r [14][9], and for the independent model cameras, res_cameras and matches."""
+    rng = np.random.default_rng(seed)
+    n = FORGED_CAMERAS
+    rots = ring_rotations(rng, 72)[:n]                      # 5 degrees apart: every pair overlaps
+    active = [c for c in range(n) if c not in FORGED_INACTIVE]
+    cams, res_cams = [None] * n, [None] * n
+    for c in active:
+        cams[c] = ba.Image(None, rots[c], ba.intrinsics(900.0 + rng.uniform(-50, 50),
+                                                        tuple(rng.normal(0, 5, 2))))
+        prm = ba.camera_to_params(cams[c])
+        res_cams[c] = ba.params_to_camera(prm + rng.normal(0, 1, 6) * [1, .5, .5, 1e-3, 1e-3, 1e-3])
+    slot = np.full(n, -1, np.int32)
+    slot[active] = np.arange(len(active))
+    a = np.array([p[0] for p in FORGED_PAIRS])
+    b = np.array([p[1] for p in FORGED_PAIRS])
+    counts = np.array([p[2] for p in FORGED_PAIRS])
+    matches = []
+    for pa, pb, count in FORGED_PAIRS:
+        H = _hom(cams[pb], cams[pa])
+        src = rng.uniform([-640, -360], [640, 360], (count, 2))
+        dst_h = np.c_[src, np.ones(count)] @ H.T
+        dst = dst_h[:, :2] / dst_h[:, 2:] + rng.normal(0, 0.5, (count, 2))
+        matches.append((pa, pb, np.c_[dst, np.ones(count), src, np.ones(count)]))
+    order = rng.permutation(len(FORGED_PAIRS))
+    gaps = rng.integers(3, 9, len(order) + 1)
+    first, blocks, at = np.zeros(len(order), np.int64), [], 0
+    for k, p in enumerate(order):
+        blocks.append(np.full((gaps[k], 4), np.nan))
+        at += gaps[k]
+        first[p] = at
+        blocks.append(matches[p][2][:, [0, 1, 3, 4]])
+        at += counts[p]
+    blocks.append(np.full((gaps[-1], 4), np.nan))
+    assert np.any(np.diff(first) < 0)
+    s_j, s_r = ba._State.of(cams), ba._State.of(res_cams)
+    jtab = ba._jacobian_tables(s_j.K, s_j.R, s_j.Kinv, ba._dr_dvis(s_j.R), a, b)
+    return {"rows": np.ascontiguousarray(np.concatenate(blocks)),
+            "pairs": np.stack([a, b, first, counts], axis=1).astype(np.int32),
+            "slot": slot, "n_active": len(active), "jtab": jtab,
+            "hom_j": ba._pair_homs(s_j.K, s_j.R, s_j.Kinv, a, b).reshape(-1, 9),
+            "hom_r": ba._pair_homs(s_r.K, s_r.R, s_r.Kinv, a, b).reshape(-1, 9),
+            "cameras": cams, "res_cameras": res_cams, "matches": matches}
+
+
+def scaled_deviations(jtj, jtr, ssq, want_jtj, want_jtr, want_ssq):
+    """The measures of tests/test_gpu_bundle.py's test_kernels_match_reference: entries of J^T J
+    over sqrt(d_i d_j), of J^T r over sqrt(d_i r.r) (d the wanted diagonal, r.r the wanted sum of
+    squared residuals of all pairs), the pairs' ssq relative (a pair without matches must give
+    exactly 0)."""
+    d = np.sqrt(np.diag(want_jtj))
+    dev = float(np.max(np.abs(jtj - want_jtj) / np.outer(d, d)))
+    dev_r = float(np.max(np.abs(jtr - want_jtr) / (d * np.sqrt(np.sum(want_ssq)))))
+    some = want_ssq != 0
+    assert np.all(ssq[~some] == 0)
+    dev_s = float(np.max(np.abs(ssq[some] / want_ssq[some] - 1)))
+    return dev, dev_r, dev_s

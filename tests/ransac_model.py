@@ -1,4 +1,5 @@
-"""NumPy model of ``pano_hom_ransac`` (include/pano360.h): the sampler, the degeneracy test, the
+"""NumPy model of ``pano_match_pack`` (the ratio test and the packing, ``pack``) and of
+``pano_hom_ransac`` (include/pano360.h): the sampler, the degeneracy test, the
 4-point solve, the score, the selection and the refit, written from the header's contract so that
 the kernel's scores can be checked bit for bit.  A test helper only: the product never imports it.
 
@@ -12,6 +13,48 @@ GAMMA = 0x9E3779B97F4A7C15
 MAX_ATTEMPTS = 64
 TRIPLES = ((0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3))
 _U64 = np.uint64
+
+
+def pack(idx, dist, ratio, kp_query, kp_train, nt):
+    """``pano_match_pack`` (include/pano360.h) for one pair: query q survives iff
+    float64(dist[q, 0]) < ratio * float64(dist[q, 1]) - strict, so a NaN on either side drops
+    it - and 0 <= idx[q, 0] < nt; the survivors come in ascending q.  idx int32 [nq][2] and
+    dist float32 [nq][2] as pano_knn2 leaves them, kp_query float32 [nq][2], kp_train float32
+    [nt][2].  Returns (pts float32 [k][4]: the query keypoint, then its nearest train keypoint;
+    match int32 [k][2]: q, idx[q, 0]; k)."""
+    idx = np.asarray(idx, np.int32).reshape(-1, 2)
+    dist = np.asarray(dist, np.float32).reshape(-1, 2).astype(np.float64)
+    kq = np.asarray(kp_query, np.float32).reshape(-1, 2)
+    kt = np.asarray(kp_train, np.float32).reshape(-1, 2)
+    t = idx[:, 0].astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        keep = (dist[:, 0] < np.float64(ratio) * dist[:, 1]) & (t >= 0) & (t < nt)
+    q = np.nonzero(keep)[0]
+    pts = np.concatenate([kq[q], kt[t[q]]], axis=1).astype(np.float32).reshape(-1, 4)
+    match = np.stack([q, t[q]], axis=1).astype(np.int32).reshape(-1, 2)
+    return pts, match, len(q)
+
+
+def boundary_distances(rng, n, ratio=0.7):
+    """Forged (d0, d1) float32 [n][2] on the boundary of the ratio test: d1 random in [0.1, 2),
+    d0 the float32 just below (even rows) or just above (odd rows) the float64 product
+    ratio * d1.  In float64 the even rows pass and the odd rows fail; a comparison in float32
+    rounds ratio * d1 once more and decides many of them the other way."""
+    d1 = rng.uniform(0.1, 2.0, n).astype(np.float32)
+    prod = np.float64(ratio) * d1.astype(np.float64)
+    near = prod.astype(np.float32)
+    below = np.where(near.astype(np.float64) < prod, near, np.nextafter(near, np.float32(-np.inf)))
+    above = np.where(near.astype(np.float64) > prod, near, np.nextafter(near, np.float32(np.inf)))
+    d0 = np.where(np.arange(n) % 2 == 0, below, above).astype(np.float32)
+    return np.stack([d0, d1], axis=1)
+
+
+def float32_ratio_test(dist, ratio):
+    """The comparison as NumPy evaluates it on float32 arrays (ratio * d1 rounded to float32):
+    NOT the contract; the tests count the rows on which it differs from the contract."""
+    dist = np.asarray(dist, np.float32)
+    with np.errstate(invalid="ignore"):
+        return dist[:, 0] < np.float32(ratio) * dist[:, 1]
 
 
 def splitmix64(x):

@@ -1,6 +1,9 @@
 """CPU: bundle adjustment's host helpers and the NumPy model of its kernel contract and LM loop
 (tests/ba_model.py) against the reference's outputs in tests/golden/ba_*.npz
-(tools/gen_ba_golden.py), ``stitcher.idx_to_keypoints`` and the new symbols' signatures.
+(tools/gen_ba_golden.py), ``stitcher.idx_to_keypoints`` and the new symbols' signatures; the
+model's second restatement, in the contract's order of additions (what
+tests/test_gpu_bundle_forged.py compares the kernels with bit for bit), against the first on a
+forged pair table.
 
 Tolerances.  Entries of J^T J and J^T r are compared relative to their Cauchy-Schwarz scale
 (sqrt(A_ii A_jj) and sqrt(A_ii r.r)): the entries range over six decades (focal columns against
@@ -154,6 +157,130 @@ def test_bundle_symbols_have_signatures():
     assert res is ctypes.c_int and len(args) == 12 and args[8] is ctypes.c_double
     assert len(_lib._SIGNATURES["pano_ba_residuals"][1]) == 6
     assert _lib._SIGNATURES["pano_ba_work_bytes"][0] is ctypes.c_size_t
+
+
+# ------------------------------------------------------------------ the ordered model
+@pytest.fixture(scope="module")
+def forged():
+    return bm.forged_system()
+
+
+def test_wave_sum_model_is_the_xor_butterfly():
+    x = 2.0 ** -np.arange(64.0)                     # the sum, 2 - 2^-63, is not a float64
+    want = x.copy()
+    for off in (32, 16, 8, 4, 2, 1):
+        want = np.array([want[k] + want[k ^ off] for k in range(64)])
+    got = bm.wave_sum_model(x)
+    assert np.array_equal(got, want) and np.all(got == got[0])
+    # 1 + 2^-53 + 2^-53: the butterfly pairs lane 0 with 32, so the two halves of an ulp meet
+    # the 1.0 one at a time and are lost; added to each other first they would survive
+    y = np.zeros(64)
+    y[0], y[32], y[16] = 1.0, 2.0 ** -53, 2.0 ** -53
+    assert bm.wave_sum_model(y)[0] == 1.0
+    y[32], y[48] = 0.0, 2.0 ** -53                  # lanes 16 and 48 meet first: an ulp survives
+    assert bm.wave_sum_model(y)[0] == 1.0 + 2.0 ** -52
+    assert bm.wave_sum_model(np.ones((3, 2, 64))).shape == (3, 2, 64)
+
+
+def test_forged_system_has_the_cases_the_recorded_runs_lack(forged):
+    pairs, slot = forged["pairs"], forged["slot"]
+    assert sorted(pairs[:, 3].tolist()) == sorted([0, 1, 2, 63, 64, 65, 255, 256, 257, 511, 513,
+                                                   1000, 90, 120])
+    assert (slot == -1).sum() == 3 and forged["n_active"] == 6
+    assert all(slot[c] != c for c in range(len(slot)))
+    assert np.all(slot[pairs[:, :2]] >= 0)
+    hub = np.sum(pairs[:, :2] == 5, axis=0)
+    assert hub.sum() == 6 and hub.min() >= 1                    # as a and as b
+    assert np.any(pairs[:, 0] < pairs[:, 1]) and np.any(pairs[:, 0] > pairs[:, 1])
+    keys = [tuple(p) for p in pairs[:, :2].tolist()]
+    assert any((b, a) in keys for a, b in keys)                 # one pair in both orders
+    assert np.any(np.diff(pairs[:, 2]) < 0)                     # `first` is not monotonic
+    rows = forged["rows"]
+    inside = np.zeros(len(rows), bool)
+    for _, _, first, count in pairs.tolist():
+        assert not inside[first:first + count].any()            # regions do not overlap
+        inside[first:first + count] = True
+    assert np.all(np.isfinite(rows[inside])) and np.all(np.isnan(rows[~inside]))
+    assert not inside[0] and not inside[-1]
+    edges = np.nonzero(np.diff(inside.astype(int)) == 1)[0]     # a gap before every region
+    assert len(edges) == np.sum(pairs[:, 3] > 0)
+    assert not np.array_equal(forged["hom_j"], forged["hom_r"])
+    assert np.array_equal(forged["jtab"][:, :9], forged["hom_j"])
+
+
+def test_ordered_model_agrees_with_the_independent_model(forged):
+    """The two restatements share no summation: ba_model.normal_equations and pair_ssq use matrix
+    products and np.sum, the ordered model the contract's lanes, butterflies and pair order.  In
+    the scaled measures of test_kernels_match_reference they agree on the forged input to
+    J^T J 1.4e-15, J^T r 1.1e-15, ssq 5.3e-15 (measured), against that test's 1e-12."""
+    f = forged
+    sums = bm.pair_sums_ordered(f["rows"], f["pairs"], f["jtab"], f["hom_r"])
+    jtj, jtr = bm.assemble_ordered(sums, f["pairs"], f["slot"], f["n_active"], bm.LAMBDA)
+    ssq = bm.ssq_ordered(f["rows"], f["pairs"], f["hom_r"])
+    want_jtj, want_jtr = bm.normal_equations(f["cameras"], f["res_cameras"], f["matches"])
+    want_ssq = bm.pair_ssq(f["res_cameras"], f["matches"])
+    assert np.all(np.isfinite(sums)) and np.all(np.isfinite(ssq))        # no NaN row was read
+    dev, dev_r, dev_s = bm.scaled_deviations(jtj, jtr, ssq, want_jtj, want_jtr, want_ssq)
+    print(f"ordered model against the independent one: J^T J {dev:.2e}, J^T r {dev_r:.2e}, "
+          f"ssq {dev_s:.2e}")
+    assert dev <= 1e-12 and dev_r <= 1e-12 and dev_s <= 1e-12
+    assert np.array_equal(jtj, jtj.T)
+    # the residual sums of the Jacobian's own state, through the other entry of the model
+    ssq_j = bm.ssq_ordered(f["rows"], f["pairs"], f["hom_j"])
+    want_j = bm.pair_ssq(f["cameras"], f["matches"])
+    some = want_j != 0
+    assert np.max(np.abs(ssq_j[some] / want_j[some] - 1)) <= 1e-12 and np.all(ssq_j[~some] == 0)
+
+
+def test_the_order_of_the_additions_shows_in_the_bits(forged):
+    """What a comparison bit for bit can see that 1e-12 cannot: the same terms of the residual
+    sums added one after the other, pairwise by np.sum, or with the butterfly's offsets taken
+    in ascending order, end in other bits than the contract's order on several of the pairs."""
+    f = forged
+    want = bm.ssq_ordered(f["rows"], f["pairs"], f["hom_r"])
+    serial, pairwise, upward = np.zeros(len(want)), np.zeros(len(want)), np.zeros(len(want))
+    lane = np.arange(64)
+    for p, (_, _, first, count) in enumerate(f["pairs"].tolist()):
+        m = f["rows"][first:first + count]
+        t = bm._mul_p(f["hom_r"][p], m[:, 2], m[:, 3])
+        rx, ry = m[:, 0] - t[0] / t[2], m[:, 1] - t[1] / t[2]
+        val = rx * rx + ry * ry
+        for v in val:
+            serial[p] = serial[p] + v
+        pairwise[p] = np.sum(val)
+        acc = bm._padded(val, count).reshape(-1, 4, 64).sum(axis=0)
+        for off in (1, 2, 4, 8, 16, 32):
+            acc = acc + acc[:, lane ^ off]
+        upward[p] = ((acc[0, 0] + acc[1, 0]) + acc[2, 0]) + acc[3, 0]
+    for other in (serial, pairwise, upward):
+        assert np.max(np.abs(other[1:] / want[1:] - 1)) <= 1e-12
+        assert np.sum(other != want) >= 3
+
+
+def test_ordered_model_structure(forged):
+    f = forged
+    pairs, slot = f["pairs"], f["slot"]
+    sums = bm.pair_sums_ordered(f["rows"], pairs, f["jtab"], f["hom_r"])
+    empty = int(np.nonzero(pairs[:, 3] == 0)[0][0])
+    assert not sums[empty].any()
+    jtj, jtr = bm.assemble_ordered(sums, pairs, slot, f["n_active"], 5.0)
+    shared = {(slot[a], slot[b]) for a, b in pairs[:, :2].tolist()}
+    lonely = [(r, c) for r in range(6) for c in range(6)
+              if r != c and (r, c) not in shared and (c, r) not in shared]
+    assert len(lonely) == 4                                     # (2, 6), (3, 8) and transposes
+    for r, c in lonely:
+        assert not jtj[6 * r:6 * r + 6, 6 * c:6 * c + 6].any()
+    # no pairs: lambda I and a zero right-hand side
+    none = np.zeros((0, 4), np.int32)
+    for n_active in (1, 3):
+        jtj0, jtr0 = bm.assemble_ordered(np.zeros((0, 90)), none, slot, n_active, 5.0)
+        assert np.array_equal(jtj0, 5.0 * np.eye(6 * n_active)) and not jtr0.any()
+    # a pair of fewer rows than a chunk is the plain butterfly of its products
+    one = int(np.nonzero(pairs[:, 3] == 1)[0][0])
+    jx, jy, rx, ry = bm._columns(f["rows"][pairs[one, 2]:pairs[one, 2] + 1], f["jtab"][one],
+                                 f["hom_r"][one])
+    assert sums[one][0] == (jx[0] * jx[0] + jy[0] * jy[0])[0]
+    assert sums[one][89] == (jx[11] * rx + jy[11] * ry)[0]
 
 
 def test_traverse_without_pairs_raises():

@@ -1,8 +1,10 @@
-"""GPU: pano_match_pack and pano_hom_ransac - the kernels against the NumPy model of their
-contract (tests/ransac_model.py: every hypothesis's score bit for bit), batch independence and
+"""GPU: pano_hom_ransac - the kernels against the NumPy model of their contract
+(tests/ransac_model.py: every hypothesis's score bit for bit), batch independence and
 determinism, a known answer through ``find_homography``, and ``matching`` end to end on a rig
-rendered from one panorama.  Every frame here is 1280 x 720, detected on an engine of this module's
-own: frame sizes never mix in one engine."""
+rendered from one panorama.  The tests of the kernels enter at ``find_homographies_device``, after
+the ratio test and the packing: pano_match_pack runs here only inside ``matching``, and is tested
+on its own, against the model of its contract, in tests/test_gpu_match_pack.py.  Every frame here
+is 1280 x 720, detected on an engine of this module's own: frame sizes never mix in one engine."""
 import os
 import sys
 

@@ -1,4 +1,5 @@
-"""CPU: the NumPy model of pano_hom_ransac (tests/ransac_model.py) on known answers, the
+"""CPU: the NumPy model of pano_match_pack and pano_hom_ransac (tests/ransac_model.py) on known
+answers, the host ratio test of ``flann_matching`` on forged boundary distances, the
 sampler's and the degeneracy test's contract, ``_reverse`` and the ``matches_<name>.npz`` layout
 the reference's stitcher loads (stitcher.py:423-428, ``idx_to_keypoints``).  No GPU."""
 import os
@@ -117,6 +118,86 @@ def test_too_few_or_degenerate_points_fail():
     line[:, 0] = line[:, 2] = np.arange(40)
     H, mask, n, best, sc = rm.ransac(line, max_iters=50)
     assert H is None and (sc == -1).all()
+
+
+# ------------------------------------------------------------------ the ratio test and the packing
+def test_pack_model_on_a_hand_written_example():
+    kq = np.array([[0.25, 0], [1.25, -1], [2.25, -2], [3.25, -3], [4.25, -4], [5.25, -5]], np.float32)
+    kt = np.array([[1000, 0.5], [1001, 1.5], [1002, 2.5], [1003, 3.5]], np.float32)
+    idx = np.array([[2, 9],          # 1 < 0.5 * 4: kept
+                    [0, -7],         # 2 < 0.5 * 4 is false: the comparison is strict
+                    [4, 0],          # passes, but train row 4 of 4 does not exist
+                    [3, 3],          # NaN
+                    [1, 1],          # 3 < 0.5 * inf: kept
+                    [0, 2]], np.int32)   # 1.5 < 0.5 * 3.5: kept
+    dist = np.array([[1, 4], [2, 4], [0.5, 4], [np.nan, 4], [3, np.inf], [1.5, 3.5]], np.float32)
+    pts, match, k = rm.pack(idx, dist, 0.5, kq, kt, 4)
+    assert k == 3
+    assert pts.dtype == np.float32 and match.dtype == np.int32
+    assert pts.tolist() == [[0.25, 0.0, 1002.0, 2.5], [4.25, -4.0, 1001.0, 1.5],
+                            [5.25, -5.0, 1000.0, 0.5]]
+    assert match.tolist() == [[0, 2], [4, 1], [5, 0]]
+    # one train row fewer: query 0's neighbour is out of range too
+    pts, match, k = rm.pack(idx, dist, 0.5, kq, kt[:2], 2)
+    assert k == 2 and match.tolist() == [[4, 1], [5, 0]]
+
+
+def test_pack_model_edges():
+    kq, kt = np.zeros((1, 2), np.float32), np.ones((3, 2), np.float32)
+
+    def kept(d0, d1, t=1, ratio=0.7, nt=3):
+        return rm.pack(np.array([[t, -5]], np.int32), np.array([[d0, d1]], np.float32), ratio,
+                       kq, kt, nt)[2] == 1
+
+    assert kept(0.6, 1.0) and not kept(0.8, 1.0)
+    assert not kept(0.5, 1.0, ratio=0.5)                    # d0 == ratio * d1 exactly
+    assert not kept(0.0, 0.0)
+    assert kept(5.0, np.inf) and not kept(np.inf, np.inf)
+    assert not kept(np.nan, 1.0) and not kept(0.1, np.nan) and not kept(np.nan, np.nan)
+    # float32(0.7) < 0.7: in float64 this d0 is below 0.7 * 1.0, in float32 it is equal to it
+    assert kept(np.float32(0.7), 1.0)
+    for t in (-1, 3, 4, 2 ** 31 - 1, -2 ** 31):
+        assert not kept(0.1, 1.0, t=t)
+    assert kept(0.1, 1.0, t=0) and kept(0.1, 1.0, t=2)
+    pts, match, k = rm.pack(np.zeros((0, 2), np.int32), np.zeros((0, 2), np.float32), 0.7,
+                            np.zeros((0, 2), np.float32), kt, 3)
+    assert k == 0 and pts.shape == (0, 4) and match.shape == (0, 2)
+
+
+def test_boundary_distances_sit_on_either_side_of_the_product():
+    dist = rm.boundary_distances(np.random.default_rng(5), 400)
+    d = dist.astype(np.float64)
+    assert dist.dtype == np.float32
+    assert np.all(d[0::2, 0] < 0.7 * d[0::2, 1]) and np.all(d[1::2, 0] > 0.7 * d[1::2, 1])
+    up = np.nextafter(dist[0::2, 0], np.float32(np.inf)).astype(np.float64)
+    down = np.nextafter(dist[1::2, 0], np.float32(-np.inf)).astype(np.float64)
+    assert np.all(up >= 0.7 * d[0::2, 1]) and np.all(down <= 0.7 * d[1::2, 1])
+
+
+def test_host_ratio_test_compares_in_float64():
+    """``features._ratio_test`` replaces ``dist[:, 0] < ratio * dist[:, 1]`` on the float32 arrays
+    of ``flann_matching``, which NumPy evaluates in float32 (ratio * d1 rounded again).  On 400
+    forged boundary rows that expression drops 131 matches the contract keeps (counted below; at
+    least 100 are required), so this test fails on it."""
+    from pano360_amd.features import _ratio_test
+    dist = rm.boundary_distances(np.random.default_rng(0), 400)
+    want = np.arange(0, 400, 2)                             # the rows just below the product
+    got = _ratio_test(dist, 0.7)
+    assert got.dtype.kind == "i" and np.array_equal(got, want)
+    _, match, k = rm.pack(np.zeros((400, 2), np.int32), dist, 0.7, np.zeros((400, 2), np.float32),
+                          np.zeros((1, 2), np.float32), 1)
+    assert np.array_equal(match[:, 0], got) and k == 200
+    replaced = np.nonzero(dist[:, 0] < 0.7 * dist[:, 1])[0]        # the parent's expression
+    differ = len(np.setxor1d(replaced, want))
+    print(f"{differ} of 400 boundary rows are decided differently in float32")
+    assert differ >= 100 and set(replaced) < set(want)
+    assert np.array_equal(np.nonzero(rm.float32_ratio_test(dist, 0.7))[0], replaced)
+    # the edges of the contract
+    edge = np.array([[0.5, 1.0], [0, 0], [3, np.inf], [np.nan, 1], [1, np.nan], [0.25, 1.0],
+                     [np.float32(0.7), 1.0]], np.float32)
+    assert _ratio_test(edge, 0.5).tolist() == [2, 5]
+    assert _ratio_test(edge, 0.7).tolist() == [0, 2, 5, 6]
+    assert _ratio_test(np.zeros((0, 2), np.float32), 0.7).tolist() == []
 
 
 def test_reverse():
