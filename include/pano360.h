@@ -66,6 +66,9 @@ extern "C" {
 #ifndef PANO_INTERIOR_BLOCK
 #define PANO_INTERIOR_BLOCK 4  /* side of the blocks of pano_interior_map  */
 #endif
+#ifndef PANO_MEDIAN_KEEP
+#define PANO_MEDIAN_KEEP 32    /* samples of a pixel the median blend votes on in one pass */
+#endif
 
 /* One warped patch as the blenders see it (reference: the tuples appended at
  * stitcher.py:318-319).  All pointers dev. */
@@ -435,6 +438,28 @@ int pano_blend_cameras(pano_ctx *ctx, const pano_camera *cams, int n, int H, int
                        int xs0, int xs1, int linear, const double *sin_t,
                        const double *cos_t, const double *tan_p, const float *lut,
                        int lut_stride, uint8_t *mosaic, uint8_t *valid);
+
+/* Ghost-rejecting median blend of the mosaic columns [xs0, xs1) straight from the
+ * frames (no reference counterpart; DESIGN.md section 5m is the contract).  The samples
+ * of a pixel are what pano_blend_cameras' linear blend combines, in index order: colour
+ * c_i, alpha a_i of every covering, unmasked camera.  With the integer weights
+ * w_i = trunc(clamp(a_i, 0, 1) 2^30), T = sum w_i and the keys k_i = (c_i[0] + c_i[1]) + c_i[2],
+ * the median sample j is the first, in ascending (k_i, i) order over the samples with
+ * w_i > 0, whose running weight S satisfies 2 S >= T; a sample is an inlier when
+ * |c_i[ch] - c_j[ch]| <= tol in all three channels (every sample when T = 0), and the pixel
+ * is the linear blend over the inliers in index order.  Where all samples agree that is
+ * pano_blend_cameras' linear mosaic bit for bit.  A pixel may have any number of samples:
+ * beyond PANO_MEDIAN_KEEP the sorted order is consumed in passes, never truncated.
+ * tol >= 0.  lut, lut_stride, valid: as for pano_blend_cameras. */
+int pano_median_cameras(pano_ctx *ctx, const pano_camera *cams, int n, int H, int W,
+                        int xs0, int xs1, float tol, const double *sin_t,
+                        const double *cos_t, const double *tan_p, const float *lut,
+                        int lut_stride, uint8_t *mosaic, uint8_t *valid);
+
+/* The same blend on warped patches (whole-patch planes, as pano_linear_blend): a patch
+ * contributes a sample where its mask is 0. */
+int pano_median_blend(pano_ctx *ctx, const pano_patch *patches, int n, int H, int W,
+                      float tol, uint8_t *mosaic);
 
 /* Overlap statistics of equalize_gains           stitcher.py:36-63
  * For each pair, every pixel (x, y) of frame i is looked up in frame j as

@@ -90,6 +90,8 @@ EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says
 # pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
 VIEW_MAX_LEVELS = 16
 VIEW_MAX_VIEWS = 32
+# pano_median_cameras / pano_median_blend: PANO_MEDIAN_KEEP
+MEDIAN_KEEP = 32
 # pano_fill_u8: PANO_FILL_TAIL_PIXELS
 FILL_TAIL_PIXELS = 4096
 # pano_jpeg_encode_batch: PANO_JPEG_BATCH_MAX, PANO_JPEG_BATCH_MAX_BLOCKS
@@ -177,6 +179,9 @@ _SIGNATURES = {
     "pano_overlap_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "pano_linear_blend": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "pano_no_blend": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "pano_median_cameras": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _i,
+                                 _vp, _vp]),
+    "pano_median_blend": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "pano_crop_rect": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "pano_blur_plane": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
     "pano_pyr_down": (_i, [_vp, _vp, _i, _i, _vp]),

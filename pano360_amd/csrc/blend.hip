@@ -1453,3 +1453,165 @@ extern "C" int pano_no_blend(pano_ctx *ctx, const pano_patch *patches, int n, in
     PANO_LAUNCH_CHECK("no_blend_kernel");
     return PANO_OK;
 }
+
+// ---- median blend: vote out what moved, blend the rest linearly (median.h) ------------------------
+#include "median.h"
+
+// The samples of blend_cameras_kernel's linear blend: same candidates, same map, taps, colour
+// table and alpha.  A walk runs under whatever lanes need it, all of them at the same list
+// position (they enter together and step together), so the listed index is still wave-uniform.
+template <bool PERCAM>
+struct CameraSampler {
+    const pano_camera *cams;
+    const int *list;             // NULL: all n cameras
+    int ncand, x, y;
+    double s, c, t;
+    const float *lut;            // PERCAM: [n][256] in global memory; else the table staged in LDS
+
+    template <class Visit>
+    __device__ __forceinline__ void walk(int lo, int hi, Visit visit) const {
+        int ord = 0;
+        for (int k = 0; k < ncand; ++k) {
+            const int i = list ? __builtin_amdgcn_readfirstlane(list[k]) : k;
+            const pano_camera *cam = cams + i;
+            const int px = x - cam->x0, py = y - cam->y0;
+            if ((unsigned)px >= (unsigned)cam->w || (unsigned)py >= (unsigned)cam->h) continue;
+            float fx, fy;
+            const int sw = cam->sw, sh_ = cam->sh;
+            if (map_pixel(cam->proj, s, c, t, sw, sh_, fx, fy)) continue;
+            const int at = ord++;
+            if (at < lo) continue;
+            const Taps tp = make_taps_unmasked(fx, fy, sw, sh_);
+            const TapBytes tb = load_taps(cam->frame, sw, tp);
+            const float *__restrict__ tab = PERCAM ? lut + (size_t)i * 256 : lut;
+            float rgb[3];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                rgb[ch] = lerp4(lut_at(tab, tb.v[0][ch]), lut_at(tab, tb.v[1][ch]),
+                                lut_at(tab, tb.v[2][ch]), lut_at(tab, tb.v[3][ch]), tp);
+            visit(at, rgb, alpha_at(cam->hat_x, cam->hat_y, tp));
+            if (at >= hi) break;
+        }
+    }
+};
+
+template <bool PERCAM>
+__global__ __launch_bounds__(256) void median_cameras_kernel(
+    const pano_camera *__restrict__ cams, int n, int H, int W, int xs0, int xs1, float tol,
+    const double *__restrict__ sin_t, const double *__restrict__ cos_t,
+    const double *__restrict__ tan_p, const float *__restrict__ lut,
+    uint8_t *__restrict__ mosaic, uint8_t *__restrict__ valid) {
+    __shared__ uint32_t s_mem[2 * MED_KEEP][256];
+    __shared__ CamList sh;
+    __shared__ float s_lut[256];
+    const int lane = threadIdx.x, wave = threadIdx.y, tid = wave * 64 + lane;
+    if (!PERCAM) s_lut[tid] = lut[tid];
+    const int bx0 = xs0 + blockIdx.x * 64, by0 = blockIdx.y * 4;
+    const int bx1 = min(bx0 + 64, xs1), by1 = min(by0 + 4, H);
+    const int listed = build_camera_list(sh, cams, n, bx0, bx1, by0, by1);   // has the barriers s_lut needs
+    int ncand = listed < 0 ? n : listed;
+    const int *list = listed < 0 ? nullptr : sh.list;
+    // blend_cameras_kernel's prune: of a long list, the cameras masked on the whole block go
+    __shared__ double s_rng[6];
+    __shared__ int s_keep[OWN_LIST];
+    __shared__ int s_kept[4];
+    if (listed > 16) {
+        if (wave == 0) {
+            const int xc = min(bx0 + lane, bx1 - 1);
+            double lo_s = sin_t[xc], hi_s = lo_s, lo_c = cos_t[xc], hi_c = lo_c;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                lo_s = fmin(lo_s, __shfl_xor(lo_s, off, 64));
+                hi_s = fmax(hi_s, __shfl_xor(hi_s, off, 64));
+                lo_c = fmin(lo_c, __shfl_xor(lo_c, off, 64));
+                hi_c = fmax(hi_c, __shfl_xor(hi_c, off, 64));
+            }
+            if (lane == 0) {
+                s_rng[0] = lo_s; s_rng[1] = hi_s; s_rng[4] = lo_c; s_rng[5] = hi_c;
+            }
+        } else if (wave == 1 && lane == 0) {
+            double lo_t = tan_p[by0], hi_t = lo_t;
+            for (int yy = by0 + 1; yy < by1; ++yy) {
+                lo_t = fmin(lo_t, tan_p[yy]);
+                hi_t = fmax(hi_t, tan_p[yy]);
+            }
+            s_rng[2] = lo_t; s_rng[3] = hi_t;
+        }
+        __syncthreads();
+        const bool keep = tid < listed && alpha_bound(cams + sh.list[tid], s_rng).hi >= 0.0f;
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_kept[wave] = __popcll(bal);
+        __syncthreads();
+        int off = 0;
+        for (int w = 0; w < wave; ++w) off += s_kept[w];
+        off += __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep) s_keep[off] = sh.list[tid];                 // index order preserved
+        ncand = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
+        list = s_keep;
+        __syncthreads();
+    }
+
+    const int x = bx0 + lane, y = by0 + wave;
+    if (x >= xs1 || y >= H) return;
+    const CameraSampler<PERCAM> sm = {cams, list, ncand, x, y, sin_t[x], cos_t[x], tan_p[y],
+                                      PERCAM ? lut : s_lut};
+    uint8_t px[3];
+    const bool any = median_pixel(sm, s_mem, tid, tol, px);
+    const size_t g = ((size_t)y * W + x) * 3;
+    mosaic[g] = px[0];
+    mosaic[g + 1] = px[1];
+    mosaic[g + 2] = px[2];
+    if (valid) valid[(size_t)y * W + x] = any ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void median_blend_kernel(
+    const pano_patch *__restrict__ patches, int n, int H, int W, float tol,
+    uint8_t *__restrict__ mosaic) {
+    __shared__ uint32_t s_mem[2 * MED_KEEP][256];
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= W || y >= H) return;
+    const PatchSampler sm = {patches, n, x, y};
+    uint8_t px[3];
+    median_pixel(sm, s_mem, threadIdx.y * 64 + threadIdx.x, tol, px);
+    const size_t g = ((size_t)y * W + x) * 3;
+    mosaic[g] = px[0];
+    mosaic[g + 1] = px[1];
+    mosaic[g + 2] = px[2];
+}
+
+extern "C" int pano_median_cameras(pano_ctx *ctx, const pano_camera *cams, int n, int H, int W,
+                                   int xs0, int xs1, float tol, const double *sin_t,
+                                   const double *cos_t, const double *tan_p, const float *lut,
+                                   int lut_stride, uint8_t *mosaic, uint8_t *valid) {
+    PANO_ENTER(ctx, "pano_median_cameras");
+    if (int rc = check_table(cams, n, H, W, "pano_median_cameras")) return rc;
+    PANO_REQUIRE(sin_t && cos_t && tan_p && lut && mosaic, "pano_median_cameras: null pointer");
+    PANO_REQUIRE(lut_stride == 0 || lut_stride == 256,
+                 "pano_median_cameras: lut_stride %d (0 = shared table, 256 = per camera)", lut_stride);
+    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_median_cameras: bad strip [%d, %d)", xs0, xs1);
+    PANO_REQUIRE(tol >= 0.0f, "pano_median_cameras: tol %g (>= 0)", (double)tol);
+    if (xs0 == xs1) return PANO_OK;
+    dim3 block(64, 4), grid(ceil_div(xs1 - xs0, 64), ceil_div(H, 4));
+    hipStream_t s = (hipStream_t)stream;
+    if (lut_stride)
+        hipLaunchKernelGGL(median_cameras_kernel<true>, grid, block, 0, s, cams, n, H, W, xs0, xs1,
+                           tol, sin_t, cos_t, tan_p, lut, mosaic, valid);
+    else
+        hipLaunchKernelGGL(median_cameras_kernel<false>, grid, block, 0, s, cams, n, H, W, xs0, xs1,
+                           tol, sin_t, cos_t, tan_p, lut, mosaic, valid);
+    PANO_LAUNCH_CHECK("median_cameras_kernel");
+    return PANO_OK;
+}
+
+extern "C" int pano_median_blend(pano_ctx *ctx, const pano_patch *patches, int n, int H, int W,
+                                 float tol, uint8_t *mosaic) {
+    PANO_ENTER(ctx, "pano_median_blend");
+    if (int rc = check_table(patches, n, H, W, "pano_median_blend")) return rc;
+    PANO_REQUIRE(mosaic, "pano_median_blend: null output");
+    PANO_REQUIRE(tol >= 0.0f, "pano_median_blend: tol %g (>= 0)", (double)tol);
+    MOSAIC_GRID;
+    hipLaunchKernelGGL(median_blend_kernel, grid, block, 0, (hipStream_t)stream, patches, n, H, W,
+                       tol, mosaic);
+    PANO_LAUNCH_CHECK("median_blend_kernel");
+    return PANO_OK;
+}

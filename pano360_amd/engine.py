@@ -1047,6 +1047,19 @@ class Engine:
                    "pano_linear_blend" if linear else "pano_no_blend")
         return mosaic
 
+    def median_blend(self, patches, shape, tol, table=None):
+        """The ghost-rejecting median blend of whole-patch device patches:
+        per pixel the weighted median sample, then the linear blend over the samples within
+        ``tol`` of it in every channel.  Returns the mosaic (u8)."""
+        torch = _torch()
+        H, W = shape
+        if table is None:
+            table = patch_table(patches, self)
+        mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.pano_median_blend(self.ctx(), table.ptr, table.n, H, W, float(tol),
+                                              _ptr(mosaic)), "pano_median_blend")
+        return mosaic
+
     def _lut_args(self, luts):
         """(lut, lut_stride) of include/pano360.h: one shared table, or one per camera."""
         if luts is None:
@@ -1448,6 +1461,22 @@ class Engine:
             _ptr(valid)), "pano_blend_cameras")
         return mosaic, valid
 
+    def median_fused(self, frames, plan, tol, luts=None, strip=None):
+        """The median blend of the mosaic columns ``strip`` straight from the frames (no patch
+        buffers), on the samples ``blend_fused``'s linear blend combines.  Returns (mosaic u8,
+        valid u8)."""
+        torch = _torch()
+        H, W = plan.shape
+        c0, c1 = strip if strip is not None else (0, W)
+        cams = self.camera_table(plan, dict(enumerate(frames)))
+        mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
+        valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.pano_median_cameras(
+            self.ctx(), _ptr(cams), plan.n, H, W, c0, c1, float(tol), _ptr(plan.dev[0]),
+            _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(mosaic),
+            _ptr(valid)), "pano_median_cameras")
+        return mosaic, valid
+
     # -- crop and filters -------------------------------------------------------------
     def crop_rect(self, valid):
         """Rectangle (y0, x0, h, w) of crop_mosaic, or None when nothing is valid."""
@@ -1500,12 +1529,19 @@ class Engine:
 
     # -- whole stitch -----------------------------------------------------------
     def stitch(self, frames, plan, blend="multiband", n_levels=5, want_float=False,
-               fused=True, shortcut=True, luts=None):
+               fused=True, shortcut=True, luts=None, tol=0.1):
         """uint8 frames on device -> (mosaic u8 on device, float mosaic, valid,
         patches).  ``fused=False`` runs multiband through whole-patch stage
-        buffers (what the blender protocol sees); both give the same mosaic."""
+        buffers (what the blender protocol sees); both give the same mosaic.
+        ``tol``: the inlier tolerance of blend="median"."""
         if not hasattr(plan, "dev"):
             self.upload_plan(plan)
+        if blend == "median":
+            if fused:
+                mosaic, valid = self.median_fused(frames, plan, tol, luts=luts)
+                return mosaic, None, valid, []
+            patches, _ = self.warp_all(frames, plan, 0, luts=luts)
+            return self.median_blend(patches, plan.shape, tol), None, None, patches
         if blend == "multiband" and fused:
             return self.multiband_fused(frames, plan, n_levels, want_float, shortcut=shortcut,
                                         luts=luts)

@@ -2,7 +2,8 @@
 
 Same names, argument order, defaults, return types and side effects as the
 reference: ``stitch``, ``no_blend`` / ``linear_blend`` /
-``multiband_blend`` (the ``blender(patches, shape)`` protocol), ``SphProj``,
+``multiband_blend`` (the ``blender(patches, shape)`` protocol; ``median_blend`` is this port's
+ghost-rejecting addition to them), ``SphProj``,
 ``CylProj``, ``_proj_img_range_border``, ``_proj_img_range_corners``,
 ``estimate_resolution``, ``_hat``, ``_add_weights``, ``_valid``,
 ``crop_mosaic``, ``find_gains``, ``equalize_gains``, ``BLENDERS``,
@@ -39,6 +40,11 @@ MAX_RESOLUTION = 1400       # read at call time, like the reference (stitcher.py
 # of the blur (<= 1e-6 per plane).  Integer results (valid mask, crop) are exact either way.
 EXACT = os.environ.get("PANO_EXACT", "0") not in ("", "0")
 _exact_engine = None
+# Inlier tolerance of ``median_blend`` per channel, colours in [0, 1] (read at call time;
+# ``--ghost-tol``).  Above the exposure and resampling differences between frames of a static
+# scene, below the contrast of something that moved; chosen by that reasoning, not tuned on
+# photographs.
+GHOST_TOL = 0.1
 
 
 def _engine_for_stitch():
@@ -166,12 +172,31 @@ def multiband_blend(patches, shape, n_levels=5):
     return mosaic.cpu().numpy()
 
 
+def median_blend(patches, shape, tol=None):
+    """Blend linearly over the samples that agree with the pixel's weighted median sample:
+    what moved through the scene in a minority of the frames is voted out, and where nothing
+    moved the result is ``linear_blend``'s (no reference counterpart).
+    ``tol``: largest difference to the median sample per channel, None = ``GHOST_TOL``."""
+    eng = _eng.engine()
+    dev = _upload_patches(eng, patches, 0)
+    return eng.median_blend(dev, tuple(shape), _ghost_tol(tol)).cpu().numpy()
+
+
+def _ghost_tol(tol=None):
+    tol = GHOST_TOL if tol is None else tol
+    if not tol >= 0:
+        raise ValueError(f"median_blend: tol {tol!r} (>= 0)")
+    return float(tol)
+
+
 BLENDERS = {
     "none": no_blend,
     "linear": linear_blend,
     "multiband": multiband_blend,
+    "median": median_blend,
 }
-_FUSED = {no_blend: "none", linear_blend: "linear", multiband_blend: "multiband"}
+_FUSED = {no_blend: "none", linear_blend: "linear", multiband_blend: "multiband",
+          median_blend: "median"}
 
 
 def _valid(patches, shape):
@@ -234,18 +259,19 @@ def _stitch_device(regions, blender, equalize, crop):
     return _stitch_device_geometry(regions, blender, equalize, crop)[:2]
 
 
-def _stitch_device_geometry(regions, blender, equalize, crop):
+def _stitch_device_geometry(regions, blender, equalize, crop, tol=None):
     """``_stitch_device`` and, third, the ``view.MosaicGeometry`` of the whole mosaic (where its
     pixels lie on the sphere: the plan's ``low``, ``resolution`` and ``shape``); the cropped
     mosaic's is ``geometry.cropped(rect)``."""
-    return _stitch_device_valid(regions, blender, equalize, crop, False)[:3]
+    return _stitch_device_valid(regions, blender, equalize, crop, False, tol)[:3]
 
 
-def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True):
+def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=None):
     """``_stitch_device_geometry`` and, fourth, the valid mask the stitch computes (uint8 [H][W] on
     the device, 1 = some frame covers the pixel): ``eng.stitch``'s third result, or
     ``eng.ownership`` of the warped patches for a custom blender, as under ``crop``.  Without
-    ``want_valid`` a custom blender's mask is only computed for the crop (else None)."""
+    ``want_valid`` a custom blender's mask is only computed for the crop (else None).  ``tol``:
+    ``median_blend``'s tolerance for this stitch (None = ``GHOST_TOL``); no other blender reads it."""
     from . import view as _view
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
@@ -270,8 +296,9 @@ def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True):
     kind = _FUSED.get(blender)
     if kind is not None:
         n_levels = multiband_blend.__defaults__[0]
+        extra = {"tol": _ghost_tol(tol)} if kind == "median" else {}
         mosaic, _, valid, patches = eng.stitch(frames, plan, kind, n_levels, luts=luts,
-                                               shortcut=not EXACT)
+                                               shortcut=not EXACT, **extra)
     else:
         patches, _ = eng.warp_all(frames, plan, luts=luts)
         valid = None
@@ -390,6 +417,13 @@ def _positive(text):
     return value
 
 
+def _tolerance(text):
+    value = float(text)
+    if not value >= 0:
+        raise argparse.ArgumentTypeError(f"{text}: >= 0")
+    return value
+
+
 def parse_args(argv=None):
     """The reference's command line (stitcher.py:390-409) and this port's additions."""
     parser = argparse.ArgumentParser(description="Stitch images.")
@@ -403,6 +437,10 @@ def parse_args(argv=None):
     parser.add_argument("--crop", "-c", action="store_true", help="remove the black borders.")
     parser.add_argument("--blend", "-b", default="multiband", choices=list(BLENDERS.keys()),
                         help="blending algorithm.")
+    parser.add_argument("--ghost-tol", type=_tolerance, metavar="FLOAT",
+                        help="-b median: a frame's sample counts where every channel is within "
+                             f"this of the pixel's median sample (colours in [0, 1]; default "
+                             f"{GHOST_TOL}).")
     parser.add_argument("-o", "--out", type=str, help="save result to this file")
     parser.add_argument("--register", action="store_true",
                         help="without a camera cache, match the images and run bundle "
@@ -432,6 +470,8 @@ def parse_args(argv=None):
                              "mosaic and --deepzoom show no ragged border, and --view, --equirect, "
                              "--cube and --multires no black outside the mosaic (not with --crop).")
     args = parser.parse_args(argv)
+    if args.ghost_tol is not None and args.blend != "median":
+        parser.error("--ghost-tol needs -b median")
     if args.fill and args.crop:
         parser.error("--fill and --crop exclude each other: a cropped mosaic has nothing to fill")
     if (args.view or args.equirect or args.cube) and not args.out:
@@ -489,11 +529,13 @@ def main(argv=None):
     background = None
     if args.fill:
         dev_mosaic, rect, geom, valid = _stitch_device_valid(regions, BLENDERS[args.blend],
-                                                             args.equalize, False)
+                                                             args.equalize, False,
+                                                             tol=args.ghost_tol)
         dev_mosaic, background = _filled(args, dev_mosaic, geom, valid)
     else:
         dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend],
-                                                         args.equalize, args.crop)
+                                                         args.equalize, args.crop,
+                                                         tol=args.ghost_tol)
     mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
