@@ -94,7 +94,7 @@ __device__ __forceinline__ int build_camera_list(CamList &sh, const pano_camera 
     return overflow ? -1 : sh.count;
 }
 
-// Pruning (exact).  Before any pixel is evaluated, one thread per listed camera bounds
+// Pruning (exact). Before any pixel is evaluated, one thread per listed camera bounds
 // that camera's alpha over the whole 64 x 16 tile: interval arithmetic, in double, on
 // the ray components (the ranges of sin / cos over the tile's columns and of tan over
 // its rows), through K R and the perspective divide, gives a box of source coordinates
@@ -212,6 +212,91 @@ __device__ __forceinline__ AlphaBound alpha_bound_of(const pano_camera *cam, con
     out.lo = inside ? fmaxf((float)(fmax(xlo, 0.0) * fmax(ylo, 0.0) * (1.0 - 1e-6)) - 1e-7f, 0.0f)
                     : 0.0f;
     return out;
+}
+
+// The cameras a 64 x 4 block of the fused blends walks: LDS of prune_masked_cameras.
+struct CamPrune {
+    double rng[6];               // alpha_bound's ranges of sin, tan, cos over the block
+    int keep[OWN_LIST];
+    int kept[4];
+};
+
+struct Candidates {
+    const int *list;             // ordered camera indices in LDS; NULL: all `count` = n cameras
+    int count;
+};
+
+// The block's candidates from its camera list (`listed` = build_camera_list's result, < 0: the
+// list overflowed).  Cameras masked on the whole block (the interval bound of alpha_bound: behind
+// the camera or outside the frame everywhere) contribute no sample and leave a long list.
+// On a closed sweep every pixel lies in the full-width rectangles of the ~20 frames across
+// the +-pi seam (stitcher.py:107-122 has no wrap handling), nearly all of them masked there:
+// 228 MP x 40 inverse maps made config 5's linear blend slower than its multiband blend.
+// Every thread of the 256-thread block calls it.
+__device__ __forceinline__ Candidates prune_masked_cameras(
+    CamPrune &pr, const CamList &sh, int listed, const pano_camera *__restrict__ cams, int n,
+    int bx0, int bx1, int by0, int by1, const double *__restrict__ sin_t,
+    const double *__restrict__ cos_t, const double *__restrict__ tan_p) {
+    if (listed < 0) return {nullptr, n};
+    if (listed <= 16) return {sh.list, listed};   // (a dozen cameras, config 3: the bounds cost more than they save)
+    const int lane = threadIdx.x, wave = threadIdx.y;
+    if (wave == 0) {
+        const int xc = min(bx0 + lane, bx1 - 1);
+        double lo_s = sin_t[xc], hi_s = lo_s, lo_c = cos_t[xc], hi_c = lo_c;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            lo_s = fmin(lo_s, __shfl_xor(lo_s, off, 64));
+            hi_s = fmax(hi_s, __shfl_xor(hi_s, off, 64));
+            lo_c = fmin(lo_c, __shfl_xor(lo_c, off, 64));
+            hi_c = fmax(hi_c, __shfl_xor(hi_c, off, 64));
+        }
+        if (lane == 0) {
+            pr.rng[0] = lo_s; pr.rng[1] = hi_s; pr.rng[4] = lo_c; pr.rng[5] = hi_c;
+        }
+    } else if (wave == 1 && lane == 0) {
+        double lo_t = tan_p[by0], hi_t = lo_t;
+        for (int yy = by0 + 1; yy < by1; ++yy) {
+            lo_t = fmin(lo_t, tan_p[yy]);
+            hi_t = fmax(hi_t, tan_p[yy]);
+        }
+        pr.rng[2] = lo_t; pr.rng[3] = hi_t;
+    }
+    __syncthreads();
+    const int tid = wave * 64 + lane;
+    const bool keep = tid < listed && alpha_bound(cams + sh.list[tid], pr.rng).hi >= 0.0f;
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) pr.kept[wave] = __popcll(bal);
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += pr.kept[w];
+    off += __popcll(bal & ((1ull << lane) - 1ull));
+    if (keep) pr.keep[off] = sh.list[tid];                    // index order preserved
+    const int count = pr.kept[0] + pr.kept[1] + pr.kept[2] + pr.kept[3];
+    __syncthreads();
+    return {pr.keep, count};
+}
+
+// Does mosaic pixel (x, y), of ray (s, c, t), sample this camera - it lies in the patch rectangle
+// and is not masked - and where in its frame.
+__device__ __forceinline__ bool camera_sees(const pano_camera *cam, int x, int y, double s, double c,
+                                            double t, float &fx, float &fy) {
+    const int px = x - cam->x0, py = y - cam->y0;
+    if ((unsigned)px >= (unsigned)cam->w || (unsigned)py >= (unsigned)cam->h) return false;
+    return !map_pixel(cam->proj, s, c, t, cam->sw, cam->sh, fx, fy);
+}
+
+// The sample there (same taps and colour table as the warp kernel) into rgb; the taps are
+// returned for alpha_at, which only a caller that weighs the sample asks.
+__device__ __forceinline__ Taps sample_camera(const pano_camera *cam, const float *__restrict__ table,
+                                              float fx, float fy, float *rgb) {
+    const int sw = cam->sw;
+    const Taps tp = make_taps_unmasked(fx, fy, sw, cam->sh);
+    const TapBytes tb = load_taps(cam->frame, sw, tp);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        rgb[ch] = lerp4(lut_at(table, tb.v[0][ch]), lut_at(table, tb.v[1][ch]),
+                        lut_at(table, tb.v[2][ch]), lut_at(table, tb.v[3][ch]), tp);
+    return tp;
 }
 
 #define OWN_ROWS 16
@@ -507,58 +592,14 @@ __global__ __launch_bounds__(256) void blend_cameras_kernel(
     const double *__restrict__ tan_p, const float *__restrict__ lut,
     uint8_t *__restrict__ mosaic, uint8_t *__restrict__ valid) {
     __shared__ CamList sh;
+    __shared__ CamPrune pr;
     __shared__ float s_lut[256];
     if (!PERCAM) s_lut[threadIdx.y * 64 + threadIdx.x] = lut[threadIdx.y * 64 + threadIdx.x];
     const int bx0 = xs0 + blockIdx.x * 64, by0 = blockIdx.y * 4;
     const int bx1 = min(bx0 + 64, xs1), by1 = min(by0 + 4, H);
     const int listed = build_camera_list(sh, cams, n, bx0, bx1, by0, by1);   // has the barriers s_lut needs
-    int ncand = listed < 0 ? n : listed;
-    const int *list = sh.list;
-    // Cameras masked on the whole block (the interval bound of alpha_bound: behind the camera
-    // or outside the frame everywhere) contribute nothing to either blend and leave the list.
-    // On a closed sweep every pixel lies in the full-width rectangles of the ~20 frames across
-    // the +-pi seam (stitcher.py:107-122 has no wrap handling), nearly all of them masked there:
-    // 228 MP x 40 inverse maps made config 5's linear blend slower than its multiband blend.
-    __shared__ double s_rng[6];
-    __shared__ int s_keep[OWN_LIST];
-    __shared__ int s_kept[4];
-    if (listed > 16) {           // (a dozen cameras, config 3: the bounds cost more than they save)
-        const int lane = threadIdx.x, wave = threadIdx.y;
-        if (wave == 0) {
-            const int xc = min(bx0 + lane, bx1 - 1);
-            double lo_s = sin_t[xc], hi_s = lo_s, lo_c = cos_t[xc], hi_c = lo_c;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                lo_s = fmin(lo_s, __shfl_xor(lo_s, off, 64));
-                hi_s = fmax(hi_s, __shfl_xor(hi_s, off, 64));
-                lo_c = fmin(lo_c, __shfl_xor(lo_c, off, 64));
-                hi_c = fmax(hi_c, __shfl_xor(hi_c, off, 64));
-            }
-            if (lane == 0) {
-                s_rng[0] = lo_s; s_rng[1] = hi_s; s_rng[4] = lo_c; s_rng[5] = hi_c;
-            }
-        } else if (wave == 1 && lane == 0) {
-            double lo_t = tan_p[by0], hi_t = lo_t;
-            for (int yy = by0 + 1; yy < by1; ++yy) {
-                lo_t = fmin(lo_t, tan_p[yy]);
-                hi_t = fmax(hi_t, tan_p[yy]);
-            }
-            s_rng[2] = lo_t; s_rng[3] = hi_t;
-        }
-        __syncthreads();
-        const int tid = wave * 64 + lane;
-        const bool keep = tid < listed && alpha_bound(cams + sh.list[tid], s_rng).hi >= 0.0f;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_kept[wave] = __popcll(bal);
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wave; ++w) off += s_kept[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep) s_keep[off] = sh.list[tid];                 // index order preserved
-        ncand = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
-        list = s_keep;
-        __syncthreads();
-    }
+    const Candidates cand = prune_masked_cameras(pr, sh, listed, cams, n, bx0, bx1, by0, by1,
+                                                 sin_t, cos_t, tan_p);
 
     const int x = bx0 + threadIdx.x, y = by0 + threadIdx.y;
     if (x >= xs1 || y >= H) return;
@@ -568,26 +609,14 @@ __global__ __launch_bounds__(256) void blend_cameras_kernel(
     bool any = false;
     // no_blend keeps the LAST unmasked camera (stitcher.py:164-166): walked from the end, the
     // first unmasked one is the answer
-    for (int kk = 0; kk < ncand; ++kk) {
-        const int k = LINEAR ? kk : ncand - 1 - kk;
-        const int i = listed < 0 ? k : __builtin_amdgcn_readfirstlane(list[k]);
+    for (int kk = 0; kk < cand.count; ++kk) {
+        const int k = LINEAR ? kk : cand.count - 1 - kk;
+        const int i = cand.list ? __builtin_amdgcn_readfirstlane(cand.list[k]) : k;
         const pano_camera *cam = cams + i;
-        const int px = x - cam->x0, py = y - cam->y0;
-        if ((unsigned)px >= (unsigned)cam->w || (unsigned)py >= (unsigned)cam->h) continue;
-        float fx, fy;
-        const int sw = cam->sw, sh_ = cam->sh;
-        if (map_pixel(cam->proj, s, c, t, sw, sh_, fx, fy)) continue;
+        float fx, fy, rgb[3];
+        if (!camera_sees(cam, x, y, s, c, t, fx, fy)) continue;
         any = true;
-        const Taps tp = make_taps_unmasked(fx, fy, sw, sh_);
-        const TapBytes tb = load_taps(cam->frame, sw, tp);
-        float rgb[3];
-        const float *__restrict__ gl = lut + (size_t)i * 256;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-            rgb[ch] = PERCAM ? lerp4(lut_at(gl, tb.v[0][ch]), lut_at(gl, tb.v[1][ch]), lut_at(gl, tb.v[2][ch]),
-                                     lut_at(gl, tb.v[3][ch]), tp)
-                             : lerp4(lut_at(s_lut, tb.v[0][ch]), lut_at(s_lut, tb.v[1][ch]), lut_at(s_lut, tb.v[2][ch]),
-                                     lut_at(s_lut, tb.v[3][ch]), tp);
+        const Taps tp = sample_camera(cam, PERCAM ? lut + (size_t)i * 256 : s_lut, fx, fy, rgb);
         if (LINEAR) {
             const float a = alpha_at(cam->hat_x, cam->hat_y, tp);
 #pragma unroll
@@ -1109,6 +1138,28 @@ static int check_table(const void *table, int n, int H, int W, const char *who) 
     return PANO_OK;
 }
 
+static int check_strip(int xs0, int xs1, int W, const char *who) {
+    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "%s: bad strip [%d, %d)", who, xs0, xs1);
+    return PANO_OK;
+}
+
+static int check_lut_stride(int lut_stride, const char *who) {
+    PANO_REQUIRE(lut_stride == 0 || lut_stride == 256,
+                 "%s: lut_stride %d (0 = shared table, 256 = per camera)", who, lut_stride);
+    return PANO_OK;
+}
+
+// The arguments pano_blend_cameras and pano_median_cameras share.
+static int check_fused_blend(const pano_camera *cams, int n, int H, int W, int xs0, int xs1,
+                             const double *sin_t, const double *cos_t, const double *tan_p,
+                             const float *lut, int lut_stride, const uint8_t *mosaic,
+                             const char *who) {
+    if (int rc = check_table(cams, n, H, W, who)) return rc;
+    PANO_REQUIRE(sin_t && cos_t && tan_p && lut && mosaic, "%s: null pointer", who);
+    if (int rc = check_lut_stride(lut_stride, who)) return rc;
+    return check_strip(xs0, xs1, W, who);
+}
+
 #define MOSAIC_GRID dim3 block(64, 4), grid(ceil_div(W, 64), ceil_div(H, 4))
 
 // The stage-level kernels index whole-patch planes: V must be the patch.
@@ -1131,7 +1182,7 @@ extern "C" int pano_ownership_cameras(pano_ctx *ctx, const pano_camera *cams, in
     PANO_ENTER(ctx, "pano_ownership_cameras");
     if (int rc = check_table(cams, n, H, W, "pano_ownership_cameras")) return rc;
     PANO_REQUIRE(sin_t && cos_t && tan_p && owner && valid, "pano_ownership_cameras: null pointer");
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_ownership_cameras: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_strip(xs0, xs1, W, "pano_ownership_cameras")) return rc;
     if (xs0 == xs1) return PANO_OK;
     // option PANO_OPT_OWN_PRUNE: bit 0 = prune by bounds (0: every listed camera at every pixel),
     // bit 1 = the round-4 kernel with one level of bounds (A/B, and a second implementation the
@@ -1153,11 +1204,8 @@ extern "C" int pano_blend_cameras(pano_ctx *ctx, const pano_camera *cams, int n,
                                   const double *cos_t, const double *tan_p, const float *lut,
                                   int lut_stride, uint8_t *mosaic, uint8_t *valid) {
     PANO_ENTER(ctx, "pano_blend_cameras");
-    if (int rc = check_table(cams, n, H, W, "pano_blend_cameras")) return rc;
-    PANO_REQUIRE(sin_t && cos_t && tan_p && lut && mosaic, "pano_blend_cameras: null pointer");
-    PANO_REQUIRE(lut_stride == 0 || lut_stride == 256,
-                 "pano_blend_cameras: lut_stride %d (0 = shared table, 256 = per camera)", lut_stride);
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_blend_cameras: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_fused_blend(cams, n, H, W, xs0, xs1, sin_t, cos_t, tan_p, lut, lut_stride,
+                                   mosaic, "pano_blend_cameras")) return rc;
     if (xs0 == xs1) return PANO_OK;
     dim3 block(64, 4), grid(ceil_div(xs1 - xs0, 64), ceil_div(H, 4));
     hipStream_t s = (hipStream_t)stream;
@@ -1273,7 +1321,7 @@ extern "C" int pano_owned_regions(pano_ctx *ctx, const int16_t *owner, int H, in
     PANO_REQUIRE(owner && marks && regions, "pano_owned_regions: null pointer");
     PANO_REQUIRE(H > 0 && W > 0 && n >= 0 && n <= 32767 && max_spans >= 1 && min_gap >= 0,
                  "pano_owned_regions: bad argument");
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_owned_regions: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_strip(xs0, xs1, W, "pano_owned_regions")) return rc;
     if (n == 0) return PANO_OK;
     hipStream_t s = (hipStream_t)stream;
     const int stride = 5 + 2 * max_spans;
@@ -1305,7 +1353,7 @@ extern "C" int pano_ownership_regions(pano_ctx *ctx, const pano_camera *cams, in
     if (int rc = check_table(cams, n, H, W, "pano_ownership_regions")) return rc;
     PANO_REQUIRE(sin_t && cos_t && tan_p && owner && valid && marks && regions,
                  "pano_ownership_regions: null pointer");
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_ownership_regions: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_strip(xs0, xs1, W, "pano_ownership_regions")) return rc;
     PANO_REQUIRE(max_spans >= 1 && min_gap >= 0, "pano_ownership_regions: bad argument");
     if (n == 0) return PANO_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -1333,7 +1381,7 @@ static int interior_map_launch(pano_ctx *ctx, const int16_t *owner, int H, int W
     void *const stream = (void *)ctx->stream;
     PANO_REQUIRE(owner && block_owner && interior && radii, "%s: null pointer", who);
     PANO_REQUIRE(H > 0 && W > 0 && n_radii >= 1 && n_radii < PANO_MAX_LEVELS, "%s: bad argument", who);
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "%s: bad strip [%d, %d)", who, xs0, xs1);
+    if (int rc = check_strip(xs0, xs1, W, who)) return rc;
     LevelReaches lv = {};
     lv.n = n_radii;
     for (int k = 0; k < n_radii; ++k) {
@@ -1392,13 +1440,10 @@ extern "C" int pano_multiband_compose(pano_ctx *ctx, const pano_patch *patches, 
     PANO_REQUIRE(owner && mosaic && valid, "pano_multiband_compose: null pointer");
     PANO_REQUIRE(n_levels >= 1 && n_levels <= PANO_MAX_LEVELS,
                  "pano_multiband_compose: n_levels %d outside [1, %d]", n_levels, PANO_MAX_LEVELS);
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1,
-                 "pano_multiband_compose: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_strip(xs0, xs1, W, "pano_multiband_compose")) return rc;
     PANO_REQUIRE(!interior || (cams && sin_t && cos_t && tan_p && lut),
                  "pano_multiband_compose: the interior map needs cameras, tables and LUT");
-    PANO_REQUIRE(lut_stride == 0 || lut_stride == 256,
-                 "pano_multiband_compose: lut_stride %d (0 = shared table, 256 = per camera)",
-                 lut_stride);
+    if (int rc = check_lut_stride(lut_stride, "pano_multiband_compose")) return rc;
     if (xs0 == xs1) return PANO_OK;
     PANO_REQUIRE(!classes || interior, "pano_multiband_compose: level classes without the interior map");
     InteriorArgs ia = {interior, ceil_div(W, IB), cams, sin_t, cos_t, tan_p, lut,
@@ -1457,8 +1502,8 @@ extern "C" int pano_no_blend(pano_ctx *ctx, const pano_patch *patches, int n, in
 // ---- median blend: vote out what moved, blend the rest linearly (median.h) ------------------------
 #include "median.h"
 
-// The samples of blend_cameras_kernel's linear blend: same candidates, same map, taps, colour
-// table and alpha.  A walk runs under whatever lanes need it, all of them at the same list
+// The samples of blend_cameras_kernel's linear blend, by the same code: the candidates of
+// prune_masked_cameras, then camera_sees and sample_camera per camera.  A walk runs under whatever lanes need it, all of them at the same list
 // position (they enter together and step together), so the listed index is still wave-uniform.
 template <bool PERCAM>
 struct CameraSampler {
@@ -1474,21 +1519,11 @@ struct CameraSampler {
         for (int k = 0; k < ncand; ++k) {
             const int i = list ? __builtin_amdgcn_readfirstlane(list[k]) : k;
             const pano_camera *cam = cams + i;
-            const int px = x - cam->x0, py = y - cam->y0;
-            if ((unsigned)px >= (unsigned)cam->w || (unsigned)py >= (unsigned)cam->h) continue;
-            float fx, fy;
-            const int sw = cam->sw, sh_ = cam->sh;
-            if (map_pixel(cam->proj, s, c, t, sw, sh_, fx, fy)) continue;
+            float fx, fy, rgb[3];
+            if (!camera_sees(cam, x, y, s, c, t, fx, fy)) continue;
             const int at = ord++;
             if (at < lo) continue;
-            const Taps tp = make_taps_unmasked(fx, fy, sw, sh_);
-            const TapBytes tb = load_taps(cam->frame, sw, tp);
-            const float *__restrict__ tab = PERCAM ? lut + (size_t)i * 256 : lut;
-            float rgb[3];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                rgb[ch] = lerp4(lut_at(tab, tb.v[0][ch]), lut_at(tab, tb.v[1][ch]),
-                                lut_at(tab, tb.v[2][ch]), lut_at(tab, tb.v[3][ch]), tp);
+            const Taps tp = sample_camera(cam, PERCAM ? lut + (size_t)i * 256 : lut, fx, fy, rgb);
             visit(at, rgb, alpha_at(cam->hat_x, cam->hat_y, tp));
             if (at >= hi) break;
         }
@@ -1503,57 +1538,19 @@ __global__ __launch_bounds__(256) void median_cameras_kernel(
     uint8_t *__restrict__ mosaic, uint8_t *__restrict__ valid) {
     __shared__ uint32_t s_mem[2 * MED_KEEP][256];
     __shared__ CamList sh;
+    __shared__ CamPrune pr;
     __shared__ float s_lut[256];
     const int lane = threadIdx.x, wave = threadIdx.y, tid = wave * 64 + lane;
     if (!PERCAM) s_lut[tid] = lut[tid];
     const int bx0 = xs0 + blockIdx.x * 64, by0 = blockIdx.y * 4;
     const int bx1 = min(bx0 + 64, xs1), by1 = min(by0 + 4, H);
     const int listed = build_camera_list(sh, cams, n, bx0, bx1, by0, by1);   // has the barriers s_lut needs
-    int ncand = listed < 0 ? n : listed;
-    const int *list = listed < 0 ? nullptr : sh.list;
-    // blend_cameras_kernel's prune: of a long list, the cameras masked on the whole block go
-    __shared__ double s_rng[6];
-    __shared__ int s_keep[OWN_LIST];
-    __shared__ int s_kept[4];
-    if (listed > 16) {
-        if (wave == 0) {
-            const int xc = min(bx0 + lane, bx1 - 1);
-            double lo_s = sin_t[xc], hi_s = lo_s, lo_c = cos_t[xc], hi_c = lo_c;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                lo_s = fmin(lo_s, __shfl_xor(lo_s, off, 64));
-                hi_s = fmax(hi_s, __shfl_xor(hi_s, off, 64));
-                lo_c = fmin(lo_c, __shfl_xor(lo_c, off, 64));
-                hi_c = fmax(hi_c, __shfl_xor(hi_c, off, 64));
-            }
-            if (lane == 0) {
-                s_rng[0] = lo_s; s_rng[1] = hi_s; s_rng[4] = lo_c; s_rng[5] = hi_c;
-            }
-        } else if (wave == 1 && lane == 0) {
-            double lo_t = tan_p[by0], hi_t = lo_t;
-            for (int yy = by0 + 1; yy < by1; ++yy) {
-                lo_t = fmin(lo_t, tan_p[yy]);
-                hi_t = fmax(hi_t, tan_p[yy]);
-            }
-            s_rng[2] = lo_t; s_rng[3] = hi_t;
-        }
-        __syncthreads();
-        const bool keep = tid < listed && alpha_bound(cams + sh.list[tid], s_rng).hi >= 0.0f;
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_kept[wave] = __popcll(bal);
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wave; ++w) off += s_kept[w];
-        off += __popcll(bal & ((1ull << lane) - 1ull));
-        if (keep) s_keep[off] = sh.list[tid];                 // index order preserved
-        ncand = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
-        list = s_keep;
-        __syncthreads();
-    }
+    const Candidates cand = prune_masked_cameras(pr, sh, listed, cams, n, bx0, bx1, by0, by1,
+                                                 sin_t, cos_t, tan_p);
 
     const int x = bx0 + lane, y = by0 + wave;
     if (x >= xs1 || y >= H) return;
-    const CameraSampler<PERCAM> sm = {cams, list, ncand, x, y, sin_t[x], cos_t[x], tan_p[y],
+    const CameraSampler<PERCAM> sm = {cams, cand.list, cand.count, x, y, sin_t[x], cos_t[x], tan_p[y],
                                       PERCAM ? lut : s_lut};
     uint8_t px[3];
     const bool any = median_pixel(sm, s_mem, tid, tol, px);
@@ -1584,11 +1581,8 @@ extern "C" int pano_median_cameras(pano_ctx *ctx, const pano_camera *cams, int n
                                    const double *cos_t, const double *tan_p, const float *lut,
                                    int lut_stride, uint8_t *mosaic, uint8_t *valid) {
     PANO_ENTER(ctx, "pano_median_cameras");
-    if (int rc = check_table(cams, n, H, W, "pano_median_cameras")) return rc;
-    PANO_REQUIRE(sin_t && cos_t && tan_p && lut && mosaic, "pano_median_cameras: null pointer");
-    PANO_REQUIRE(lut_stride == 0 || lut_stride == 256,
-                 "pano_median_cameras: lut_stride %d (0 = shared table, 256 = per camera)", lut_stride);
-    PANO_REQUIRE(xs0 >= 0 && xs1 <= W && xs0 <= xs1, "pano_median_cameras: bad strip [%d, %d)", xs0, xs1);
+    if (int rc = check_fused_blend(cams, n, H, W, xs0, xs1, sin_t, cos_t, tan_p, lut, lut_stride,
+                                   mosaic, "pano_median_cameras")) return rc;
     PANO_REQUIRE(tol >= 0.0f, "pano_median_cameras: tol %g (>= 0)", (double)tol);
     if (xs0 == xs1) return PANO_OK;
     dim3 block(64, 4), grid(ceil_div(xs1 - xs0, 64), ceil_div(H, 4));

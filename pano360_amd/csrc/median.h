@@ -1,8 +1,9 @@
 // ---- median blend: vote out what moved, blend the rest linearly ----------------------------------
 // No reference counterpart; DESIGN.md section 5m and include/pano360.h state the contract.  One
 // thread per mosaic pixel, like the linear blends above, in up to three walks over the pixel's
-// samples (a sampler yields them in index order: the fused one maps and samples the cameras
-// exactly as blend_cameras_kernel does, the stage one reads whole-patch planes):
+// samples (a sampler yields them in index order: the fused one walks prune_masked_cameras'
+// candidates and takes each sample with camera_sees and sample_camera, the routines of blend.hip
+// that blend_cameras_kernel calls too; the stage one reads whole-patch planes):
 //   1. every sample: the integer weight total T, the per-channel range of the colours, the plain
 //      linear sums, and (key, weight) of the first PANO_MEDIAN_KEEP samples into LDS.  Where the
 //      range is within tol in all three channels every sample is an inlier whichever the median

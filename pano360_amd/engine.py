@@ -1036,29 +1036,27 @@ class Engine:
             "pano_multiband_compose")
         return mosaic, fl
 
-    def simple_blend(self, patches, shape, linear, table=None):
+    def _patch_blend(self, name, patches, shape, table, *mode):
+        """A whole-patch blender ``name`` of the library (``mode``: its arguments between the
+        mosaic's shape and the output) on device patches.  Returns the mosaic (u8)."""
         torch = _torch()
         H, W = shape
         if table is None:
             table = patch_table(patches, self)
         mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-        fn = self.lib.pano_linear_blend if linear else self.lib.pano_no_blend
-        _lib.check(fn(self.ctx(), table.ptr, table.n, H, W, _ptr(mosaic)),
-                   "pano_linear_blend" if linear else "pano_no_blend")
+        _lib.check(getattr(self.lib, name)(self.ctx(), table.ptr, table.n, H, W, *mode, _ptr(mosaic)),
+                   name)
         return mosaic
+
+    def simple_blend(self, patches, shape, linear, table=None):
+        return self._patch_blend("pano_linear_blend" if linear else "pano_no_blend", patches, shape,
+                                 table)
 
     def median_blend(self, patches, shape, tol, table=None):
         """The ghost-rejecting median blend of whole-patch device patches:
         per pixel the weighted median sample, then the linear blend over the samples within
         ``tol`` of it in every channel.  Returns the mosaic (u8)."""
-        torch = _torch()
-        H, W = shape
-        if table is None:
-            table = patch_table(patches, self)
-        mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pano_median_blend(self.ctx(), table.ptr, table.n, H, W, float(tol),
-                                              _ptr(mosaic)), "pano_median_blend")
-        return mosaic
+        return self._patch_blend("pano_median_blend", patches, shape, table, float(tol))
 
     def _lut_args(self, luts):
         """(lut, lut_stride) of include/pano360.h: one shared table, or one per camera."""
@@ -1439,9 +1437,11 @@ class Engine:
         Raises ``PanoError`` if they differ: the cameras were changed under a kept Plan."""
         _lib.check(self.lib.pano_stitch_verify(self._ctx), "pano_stitch_verify")
 
-    def blend_fused(self, frames, plan, linear, frame_ids=None, strip=None, luts=None):
-        """linear_blend / no_blend of the mosaic columns ``strip`` straight from
-        the frames (no patch buffers).  Returns (mosaic u8, valid u8)."""
+    def _fused_blend(self, name, mode, frames, plan, frame_ids, strip, luts):
+        """A blender ``name`` of the library that samples the frames itself (``mode``: its argument
+        after the strip), on the mosaic columns ``strip``.  ``frames`` are the cameras
+        ``frame_ids`` (default: all of them); every camera whose rectangle meets the strip must
+        be among them.  Returns (mosaic u8, valid u8)."""
         torch = _torch()
         H, W = plan.shape
         c0, c1 = strip if strip is not None else (0, W)
@@ -1455,27 +1455,24 @@ class Engine:
         cams = self.camera_table(plan, have)
         mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
         valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pano_blend_cameras(
-            self.ctx(), _ptr(cams), plan.n, H, W, c0, c1, 1 if linear else 0, _ptr(plan.dev[0]),
+        _lib.check(getattr(self.lib, name)(
+            self.ctx(), _ptr(cams), plan.n, H, W, c0, c1, mode, _ptr(plan.dev[0]),
             _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(mosaic),
-            _ptr(valid)), "pano_blend_cameras")
+            _ptr(valid)), name)
         return mosaic, valid
 
-    def median_fused(self, frames, plan, tol, luts=None, strip=None):
+    def blend_fused(self, frames, plan, linear, frame_ids=None, strip=None, luts=None):
+        """linear_blend / no_blend of the mosaic columns ``strip`` straight from
+        the frames (no patch buffers).  Returns (mosaic u8, valid u8)."""
+        return self._fused_blend("pano_blend_cameras", 1 if linear else 0, frames, plan, frame_ids,
+                                 strip, luts)
+
+    def median_fused(self, frames, plan, tol, luts=None, strip=None, frame_ids=None):
         """The median blend of the mosaic columns ``strip`` straight from the frames (no patch
         buffers), on the samples ``blend_fused``'s linear blend combines.  Returns (mosaic u8,
         valid u8)."""
-        torch = _torch()
-        H, W = plan.shape
-        c0, c1 = strip if strip is not None else (0, W)
-        cams = self.camera_table(plan, dict(enumerate(frames)))
-        mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-        valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pano_median_cameras(
-            self.ctx(), _ptr(cams), plan.n, H, W, c0, c1, float(tol), _ptr(plan.dev[0]),
-            _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(mosaic),
-            _ptr(valid)), "pano_median_cameras")
-        return mosaic, valid
+        return self._fused_blend("pano_median_cameras", float(tol), frames, plan, frame_ids, strip,
+                                 luts)
 
     # -- crop and filters -------------------------------------------------------------
     def crop_rect(self, valid):

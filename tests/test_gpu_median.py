@@ -158,6 +158,67 @@ def test_per_camera_colour_tables(eng):
         assert np.array_equal(valid.cpu().numpy().astype(bool), want_valid)
 
 
+@pytest.mark.parametrize("n,step_deg,seed", [(260, 1.3, 11), (290, 0.2, 5)])
+def test_per_camera_tables_on_long_camera_lists(eng, oracle, n, step_deg, seed):
+    """The two rigs above - camera lists the kernels prune by the alpha bound, and lists longer
+    than a block holds - with a colour table per camera, rows all different: the three fused
+    blends take the samples of the warp with the same tables, mosaics and valid masks."""
+    import torch
+    from pano360_amd import engine, stitcher, synth
+    imgs, rots, intrs = synth.make_scene(n, 32, 24, step_deg=step_deg, seed=seed, kind="A")
+    plan = eng.upload_plan(engine.Plan([im.shape[:2] for im in imgs], rots, intrs, False, 1400))
+    hits = block_hits(plan.rects, plan.shape)
+    assert (16 < hits.min() and hits.max() <= OWN_LIST) if n == 260 else hits.min() > OWN_LIST
+    frames = eng.upload_frames(imgs)
+    gains = 0.7 + 0.06 * ((7 * np.arange(n)) % 11)           # forged: 0.7 .. 1.3, neighbours differ
+    luts = torch.from_numpy(engine.gain_tables(gains)).to(eng.device)
+    patches = stitcher._download_patches(eng.warp_all(frames, plan, luts=luts)[0])
+    plain = stitcher._download_patches(eng.warp_all(frames, plan)[0])
+    assert any(not np.array_equal(a[0], b[0]) for a, b in zip(patches, plain))
+    want_median, want_valid = median_model.median_blend(patches, plan.shape, 0.1)
+    want = {True: oracle.linear_blend(patches, plan.shape), False: oracle.no_blend(patches, plan.shape)}
+
+    def same(got, want_mosaic, cols=slice(None)):
+        mosaic, valid = got
+        return (np.array_equal(mosaic[:, cols].cpu().numpy(), want_mosaic[:, cols])
+                and np.array_equal(valid[:, cols].cpu().numpy().astype(bool), want_valid[:, cols]))
+
+    assert same(eng.median_fused(frames, plan, 0.1, luts=luts), want_median)
+    for linear in (True, False):
+        assert same(eng.blend_fused(frames, plan, linear, luts=luts), want[linear]), linear
+        if n == 260:                                          # a strip start that is no multiple of 64
+            assert plan.shape[1] == 192
+            for strip in ((0, 100), (100, 192)):
+                assert same(eng.blend_fused(frames, plan, linear, strip=strip, luts=luts),
+                            want[linear], slice(*strip)), (linear, strip)
+
+
+def test_fused_on_a_subset_of_the_frames(eng, monkeypatch):
+    """A rank's share: only the frames whose rectangles meet the strip, with their ids, give the
+    strip of the whole; one of them missing is an error before any kernel runs."""
+    from pano360_amd import _lib, engine, synth
+    imgs, rots, intrs = synth.make_scene(10, 480, 270, sweep_deg=120.0, jitter=0.01, seed=41,
+                                         kind="A")
+    plan = eng.upload_plan(engine.Plan([im.shape[:2] for im in imgs], rots, intrs, False, 10 ** 9))
+    frames = eng.upload_frames(imgs)
+    W = plan.shape[1]
+    strip = (W // 3 + 5, W // 2)
+    ids = [i for i, (_, _, x0, x1) in enumerate(plan.rects) if x0 < strip[1] and x1 > strip[0]]
+    assert 1 < len(ids) < len(imgs)
+    want, want_valid = eng.median_fused(frames, plan, 0.1, strip=strip)
+    got, got_valid = eng.median_fused([frames[i] for i in ids], plan, 0.1, strip=strip, frame_ids=ids)
+    cols = slice(*strip)
+    assert np.array_equal(got[:, cols].cpu().numpy(), want[:, cols].cpu().numpy())
+    assert np.array_equal(got_valid[:, cols].cpu().numpy(), want_valid[:, cols].cpu().numpy())
+    assert want_valid[:, cols].any()
+    monkeypatch.setattr(eng, "camera_table", lambda *a, **k: pytest.fail("went on to the kernel's arguments"))
+    for fused in (lambda f, i: eng.median_fused(f, plan, 0.1, strip=strip, frame_ids=i),
+                  lambda f, i: eng.blend_fused(f, plan, True, frame_ids=i, strip=strip)):
+        with pytest.raises(_lib.PanoError, match=rf"frames \[{ids[-1]}\] are needed for columns "
+                                                 rf"\[{strip[0]}, {strip[1]}\) but are not resident"):
+            fused([frames[i] for i in ids[:-1]], ids[:-1])
+
+
 def test_drop_in_blender(eng, scene_patches):
     import bundle_adj
     from pano360_amd import stitcher

@@ -5,6 +5,7 @@ stated tolerances (1e-4 relative L2 on the float mosaic, 1 LSB on uint8)."""
 import numpy as np
 import pytest
 
+import median_model
 from conftest import SCENES, load_golden, n_patches, scene_inputs
 from sift_reference import assert_same_detection
 
@@ -1707,10 +1708,13 @@ def test_three_hundred_cameras(eng, oracle, step_deg):
     _, ref_patches, _ = oracle.warp_all(imgs, rots, intrs, True, 10 ** 9)
     assert np.array_equal(valid.cpu().numpy().astype(bool), oracle.valid(ref_patches, plan.shape))
     plan_l = engine.Plan(shapes, rots, intrs, False, 10 ** 9)
+    _, ref_unpadded, _ = oracle.warp_all(imgs, rots, intrs, False, 10 ** 9)
+    want_valid = median_model.sample_counts(ref_unpadded, plan_l.shape) > 0
     for kind in ("linear", "none"):
-        got = eng.stitch(frames, plan_l, kind)[0]
+        got, _, got_valid, _ = eng.stitch(frames, plan_l, kind)
         assert np.array_equal(got.cpu().numpy(),
                               oracle.stitch(imgs, rots, intrs, kind, max_resolution=10 ** 9)), kind
+        assert np.array_equal(got_valid.cpu().numpy().astype(bool), want_valid), kind
 
 
 def _edge_scene(case):

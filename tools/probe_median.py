@@ -9,19 +9,22 @@ degree sweep at native resolution, unpadded patches) with two sets of frames:
 Per set and item, median / min / max over --reps runs, in ms, from device events around the call
 (the host's share of a call is inside: the two output allocations):
   linear           blend_fused(linear=True)
+  none             blend_fused(linear=False)
   median_tol0.1    median_fused at the default tolerance
   median_tol0      median_fused at tol = 0: every pixel whose samples differ at all votes
   median_tol2      median_fused at tol = 2: no pixel votes (the cost of the first walk alone)
 each median item with its ratio to `linear`.  Beside them the samples per pixel (mean over the
 covered pixels, maximum) and the share of covered pixels with more than PANO_MEDIAN_KEEP samples,
 which the kernel consumes in passes; the share of pixels whose median mosaic differs from the
-linear one.  Prints one JSON line per item.
+linear one; and the CRC-32 of every mosaic, to compare two builds of the library (PANO_LIB).
+Prints one JSON line per item.
 
     python tools/probe_median.py [--reps 20] [--small] [--sets noise,static]"""
 import argparse
 import json
 import os
 import sys
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -58,6 +61,10 @@ def sample_counts(eng, frames, plan):
     return counts
 
 
+def crc(mosaic):
+    return zlib.crc32(mosaic.cpu().numpy().tobytes())
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("--reps", type=int, default=20)
@@ -86,13 +93,16 @@ def main():
         del counts
         torch.cuda.synchronize()
         base, (linear, _) = timed(lambda: eng.blend_fused(frames, plan, True), args.reps)
-        print(json.dumps({"item": "linear", **scene, "ms": base}), flush=True)
+        print(json.dumps({"item": "linear", **scene, "ms": base, "crc32": crc(linear)}), flush=True)
+        stats, (mosaic, _) = timed(lambda: eng.blend_fused(frames, plan, False), args.reps)
+        print(json.dumps({"item": "none", **scene, "ms": stats, "crc32": crc(mosaic)}), flush=True)
         for tol in (0.1, 0.0, 2.0):
             stats, (mosaic, _) = timed(lambda t=tol: eng.median_fused(frames, plan, t), args.reps)
             differs = int((mosaic != linear).any(dim=-1).sum())
             print(json.dumps({"item": f"median_tol{tol:g}", **scene, "ms": stats,
                               "ratio_to_linear": round(stats["median"] / base["median"], 3),
-                              "share_differs_from_linear": round(differs / (H * W), 6)}),
+                              "share_differs_from_linear": round(differs / (H * W), 6),
+                              "crc32": crc(mosaic)}),
                   flush=True)
         del frames, linear, mosaic
 
