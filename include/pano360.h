@@ -1283,6 +1283,53 @@ int pano_fill_u8(pano_ctx *ctx, const uint8_t *img, int64_t img_pitch, const uin
 int pano_select_u8(pano_ctx *ctx, const uint8_t *a, const uint8_t *mask, const uint8_t *b,
                    uint8_t *out, int64_t n_pixels);
 
+/* Lens correction at the ingest          (the reference has none: it assumes an ideal pinhole
+ * camera whose principal point is the image centre; csrc/lens.hip, NumPy statement:
+ * tests/lens_model.py)
+ * pano_lens_undistort_u8: ONE call resamples n uint8 [h][w][3] frames (any n; of any sizes,
+ *     pitches and calibrations) into the centred pinhole image of focal length f_new, each into
+ *     a new frame of its size.  frames: HOST records; src, dst: dev, rows src_pitch / dst_pitch
+ *     bytes apart; dst must not overlap its src.  Sides 1 .. PANO_LENS_MAX_SIDE.  For output pixel
+ *     (u, v), in float64, one rounding per operation in the order written:
+ *       x = (u - w / 2) / f_new, y = (v - h / 2) / f_new
+ *       PANO_LENS_BROWN (k = OpenCV's k1 k2 p1 p2 k3):
+ *         r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+ *         xd = x rad + 2 p1 x y + p2 (r2 + 2 x x), yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y
+ *       PANO_LENS_FISHEYE (k = OpenCV's fisheye k1 .. k4; k[4] is not read):
+ *         r = sqrt(x x + y y), th = atan(r), t2 = th th
+ *         thd = th (1 + t2 (k1 + t2 (k2 + t2 (k3 + t2 k4)))), s = r > 0 ? thd / r : 1
+ *         xd = x s, yd = y s
+ *       px = fx xd + cx, py = fy yd + cy: the calibration's FORWARD model, nothing is iterated.
+ *     px is clamped to [-2, w + 1], py to [-2, h + 1] (a position that is not a number becomes -2)
+ *     and quantised to 1 / 32 pixel: sx = rint(32 px) (ties to even), ix = sx >> 5, t = (sx & 31)
+ *     / 32, the same in y.  PANO_LENS_CUBIC: Catmull-Rom over the columns ix - 1 .. ix + 2 and the
+ *     rows iy - 1 .. iy + 2, every index clamped to the frame, with the weights
+ *       w0 = ((-0.5 t + 1) t - 0.5) t, w1 = (1.5 t - 2.5) t t + 1,
+ *       w2 = ((-1.5 t + 2) t + 0.5) t, w3 = (0.5 t - 0.5) t t        (exact in float32);
+ *     a row is ((p0 w0 + p1 w1) + p2 w2) + p3 w3 in float32, the four rows are combined the same
+ *     way with the y weights, and the result is rint (ties to even) clamped to 0 .. 255.
+ *     PANO_LENS_LINEAR: the taps ix, ix + 1 and iy, iy + 1 with the weights 1 - t, t, likewise.
+ *     A refused batch (PANO_EINVAL: a null pointer, a side, a pitch below 3 w, an overlap, a
+ *     parameter that is not finite, fx, fy or f_new <= 0, an unknown model or interpolation,
+ *     n < 1) queues nothing.  The records travel in a buffer of the context (it grows on demand,
+ *     the call then waits for the stream first); one launch per 64 frames, asynchronous on the
+ *     stream.  No atomics: the same input gives the same bytes. */
+#define PANO_LENS_MAX_SIDE 32767
+#define PANO_LENS_BROWN 0
+#define PANO_LENS_FISHEYE 1
+#define PANO_LENS_CUBIC 0
+#define PANO_LENS_LINEAR 1
+typedef struct pano_lens_frame {
+    const uint8_t *src;        /* dev uint8 [h][w][3], rows src_pitch bytes apart   */
+    uint8_t *dst;              /* dev, the same size, rows dst_pitch bytes apart    */
+    int64_t src_pitch, dst_pitch;
+    double fx, fy, cx, cy;     /* the calibration, in pixels of this frame          */
+    double f_new;              /* focal length of the corrected frame               */
+    double k[5];               /* Brown: k1 k2 p1 p2 k3; fisheye: k1 k2 k3 k4, -    */
+    int32_t w, h, model, interp;
+} pano_lens_frame;
+int pano_lens_undistort_u8(pano_ctx *ctx, const pano_lens_frame *frames, int n);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

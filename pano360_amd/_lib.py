@@ -95,6 +95,10 @@ MEDIAN_KEEP = 32
 # pano_fill_u8: PANO_FILL_TAIL_PIXELS
 FILL_TAIL_PIXELS = 4096
 # pano_jpeg_encode_batch: PANO_JPEG_BATCH_MAX, PANO_JPEG_BATCH_MAX_BLOCKS
+# pano_lens_undistort_u8: PANO_LENS_MAX_SIDE, the models and interpolations
+LENS_MAX_SIDE = 32767
+LENS_BROWN, LENS_FISHEYE = 0, 1
+LENS_CUBIC, LENS_LINEAR = 0, 1
 JPEG_BATCH_MAX = 16384
 JPEG_BATCH_MAX_BLOCKS = 1 << 28
 
@@ -116,6 +120,15 @@ class ViewMosaic(C.Structure):
     _fields_ = [("low", C.c_double * 2), ("res", C.c_double * 2),
                 ("h", C.c_int32), ("w", C.c_int32), ("closed", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class LensFrame(C.Structure):
+    """``pano_lens_frame`` of include/pano360.h (128 bytes)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p),
+                ("src_pitch", C.c_int64), ("dst_pitch", C.c_int64),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("f_new", C.c_double), ("k", C.c_double * 5),
+                ("w", C.c_int32), ("h", C.c_int32), ("model", C.c_int32), ("interp", C.c_int32)]
 
 
 class Pair(C.Structure):
@@ -246,6 +259,7 @@ _SIGNATURES = {
                               C.POINTER(View), _i]),
     "pano_fill_u8": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64]),
     "pano_select_u8": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
+    "pano_lens_undistort_u8": (_i, [_vp, C.POINTER(LensFrame), _i]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -156,6 +156,8 @@ enum PanoBufId {
     BUF_PNG_HOST,
     // pano_fill_u8 (fill.hip): the "any pixel valid" word and the float32 levels >= 1 (fill_layout.h)
     BUF_FILL_DEV,
+    // pano_lens_undistort_u8 (lens.hip): the batch's frame records
+    BUF_LENS_DEV,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it

@@ -1057,20 +1057,41 @@ def _assemble(kpts, found):
     return kpt_arr, match_arr
 
 
-def main(argv=None):
-    """Script entry point (features.py:300-320): the images of ``--path``, shrunk by half,
-    matched; writes ``matches_<name>.npz`` (``--detector msop``: ``matches_<name>_msop.npz``).  Read with Pillow, resized on the device."""
-    from .stitcher import ingest
+def parse_args(argv=None):
+    """The command line of ``main``."""
+    from . import lens as _lens
     parser = argparse.ArgumentParser(description="Extract features.")
     parser.add_argument("--path", type=str, default="../data/ppwwyyxx/CMU2",
                         help="directory with the images to process.")
     parser.add_argument("--detector", default="sift", choices=["sift", "msop"],
                         help="feature detector (msop writes matches_<name>_msop.npz).")
+    _lens.add_arguments(parser)
     args = parser.parse_args(argv)
+    _lens.check_arguments(parser, args)
+    return args
+
+
+def cache_name(args):
+    """``<name>`` of ``matches_<name>.npz``: the directory, ``_msop`` for that detector, ``_lens``
+    with ``--lens``."""
     name = os.path.basename(args.path)
     if args.detector == "msop":
         name += "_msop"
-    imgs = ingest(args.path, 2)
+    if args.lens is not None:
+        name += "_lens"
+    return name
+
+
+def main(argv=None):
+    """Script entry point (features.py:300-320): the images of ``--path``, shrunk by half,
+    matched; writes ``matches_<name>.npz`` (``--detector msop``: ``matches_<name>_msop.npz``;
+    ``--lens FILE``: the images' lens distortion corrected first, ``matches_<name>_lens.npz``).
+    Read with Pillow, resized on the device."""
+    from . import lens as _lens
+    from .stitcher import ingest
+    args = parse_args(argv)
+    name = cache_name(args)
+    imgs = ingest(args.path, 2, lens=_lens.from_args(args))
     kpts, matches = matching(imgs, **detector_kwargs(args.detector))
     np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
     return kpts, matches

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import bundle_adj as _ba
 from . import engine as _eng
+from . import lens as _lens
 from .engine import CylProj, SphProj  # noqa: F401  (re-exported API)
 
 MAX_RESOLUTION = 1400       # read at call time, like the reference (stitcher.py:17,154)
@@ -329,13 +330,15 @@ def _download_cropped(mosaic, rect):
 IMAGE_EXTENSIONS = (".jpg", ".png", ".bmp", ".JPG", ".PNG", ".BMP")     # stitcher.py:411-412
 
 
-def ingest(path, shrink, decode="device"):
+def ingest(path, shrink, decode="device", lens=None):
     """The head of the reference's ``main`` (stitcher.py:415-421): every image of the
     directory, in ``os.listdir`` order, as ``cv2.imread`` would return it (uint8 BGR), shrunk by
     ``cv2.resize(im, None, fx=1/shrink, fy=1/shrink)`` when shrink > 1 - on the device.
     decode="device": baseline JPEGs are decoded on the device in one batch
     (``jpeg.read_images``), everything else by Pillow; "host": every file by Pillow.  The frames
-    are the same either way.  Returns uint8 [h][w][3] device tensors."""
+    are the same either way.  ``lens`` (a ``lens.Calibration``): every decoded frame's lens
+    distortion is corrected on the device, at the file's own resolution, before the shrink.
+    Returns uint8 [h][w][3] device tensors."""
     from . import blend as _blend
     from . import jpeg as _jpeg
     if decode not in ("device", "host"):
@@ -346,8 +349,14 @@ def ingest(path, shrink, decode="device"):
         # cv2.imread's defaults: the EXIF orientation applied (a phone's rotated JPEG arrives
         # upright, with its shape swapped), 8 bits, three channels: 16-bit images are scaled
         # down to 8 bits and an alpha channel is dropped, as IMREAD_COLOR does
-        return _blend.shrink_images([_jpeg._pillow_read(p) for p in paths], shrink)
-    frames, _ = _jpeg.read_images(paths)
+        images = [_jpeg._pillow_read(p) for p in paths]
+        if lens is None:
+            return _blend.shrink_images(images, shrink)
+        frames = _blend.shrink_images(images, 1)            # (the upload alone)
+    else:
+        frames, _ = _jpeg.read_images(paths)
+    if lens is not None:
+        frames = lens.correct_device(frames, files)
     if shrink > 1:
         eng = _eng.engine()
         frames = [_blend.shrink_device(f, shrink, eng) for f in frames]
@@ -469,7 +478,9 @@ def parse_args(argv=None):
                         help="fill what no frame covers from the pixels around it: the saved "
                              "mosaic and --deepzoom show no ragged border, and --view, --equirect, "
                              "--cube and --multires no black outside the mosaic (not with --crop).")
+    _lens.add_arguments(parser)
     args = parser.parse_args(argv)
+    _lens.check_arguments(parser, args)
     if args.ghost_tol is not None and args.blend != "median":
         parser.error("--ghost-tol needs -b median")
     if args.fill and args.crop:
@@ -485,13 +496,24 @@ def parse_args(argv=None):
     return args
 
 
+def cache_name(args):
+    """``<name>`` of ``matches_<name>.npz`` and ``ba_<name>.pkl``: the directory and the shrink
+    as in the reference, ``_msop`` for that detector, ``_lens`` with ``--lens``: matches and
+    cameras of corrected and uncorrected frames never mix."""
+    name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
+    if args.detector == "msop":
+        name += "_msop"
+    if args.lens is not None:
+        name += "_lens"
+    return name
+
+
 def main(argv=None):
     """Same command line as the reference (stitcher.py:390-451)."""
     args = parse_args(argv)
 
-    name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
-    if args.detector == "msop":
-        name += "_msop"
+    name = cache_name(args)
+    lens = _lens.from_args(args)
     cache = f"ba_{name}.pkl"
     try:
         with open(cache, "rb") as fid:
@@ -514,10 +536,10 @@ def main(argv=None):
             "cameras here (the reference CLI's registration), or produce the camera cache with "
             "the reference (the pickle written at stitcher.py:438-439) and re-run")
     if regions is None:
-        regions = _register(args.path, name, ingest(args.path, args.shrink), args.ba,
+        regions = _register(args.path, name, ingest(args.path, args.shrink, lens=lens), args.ba,
                             args.detector)
     if any(reg.img is None for reg in regions):
-        frames = ingest(args.path, args.shrink) if os.path.isdir(args.path) else []
+        frames = ingest(args.path, args.shrink, lens=lens) if os.path.isdir(args.path) else []
         if len(frames) != len(regions):
             raise SystemExit(f"{cache} holds {len(regions)} cameras, {args.path} "
                              f"{len(frames)} images")
