@@ -1330,6 +1330,76 @@ typedef struct pano_lens_frame {
 } pano_lens_frame;
 int pano_lens_undistort_u8(pano_ctx *ctx, const pano_lens_frame *frames, int n);
 
+/* Photometric alignment of the frames before the stitch          (the reference has one scalar
+ * gain per camera, equalize_gains; csrc/photo.hip, NumPy statement: tests/photo_model.py)
+ * The model: camera i records I = g[i][c] V(rho) E in channel c, log V(rho) = a1 rho + a2 rho^2 +
+ * a3 rho^3, rho = ((2x + 1 - w)^2 + (2y + 1 - h)^2) / (w^2 + h^2) at pixel position (x, y) of a
+ * w x h frame: the squared distance from the image centre over the squared half diagonal.
+ *
+ * pano_photo_stats: the 25 weighted sums of the normal equations for each of n_pairs camera pairs,
+ *     in ONE call.  frames, pairs, log_gains, alpha: HOST; sums: dev float64 [n_pairs][25].
+ *     Frames are uint8 [h][w][3], rows `pitch` bytes apart, sides 2 .. PANO_PHOTO_MAX_SIDE, of any
+ *     sizes.  A pair (i, j, H) maps frame i's centred pixel positions into frame j's.  For every
+ *     step-th pixel (x, y) of frame i in x and y, from 0, in float64, one rounding per operation
+ *     in the order written:
+ *       xc = x - w_i / 2, yc = y - h_i / 2
+ *       X = (H0 xc + H1 yc) + H2, Y = (H3 xc + H4 yc) + H5, Z = (H6 xc + H7 yc) + H8; Z > 0 or drop
+ *       px = X / Z + w_j / 2, py = Y / Z + h_j / 2; 0 <= px <= w_j - 1 and 0 <= py <= h_j - 1 or drop
+ *       sx = rint(32 px) (ties to even), ix = min(sx >> 5, w_j - 2), tx = (sx - 32 ix) / 32; y alike
+ *     Frame j is sampled bilinearly in float32 at the taps ix, ix + 1 and iy, iy + 1:
+ *     top = p00 (1 - tx) + p01 tx, bot alike, v_j = top (1 - ty) + bot ty (exact: dyadic weights,
+ *     8-bit values); v_i is the byte of frame i.  The sample counts only when all six values lie
+ *     in [lo, hi] (1 <= lo <= hi <= 255).  Then, in float64,
+ *       d_c = log(v_i,c) - log(v_j,c)
+ *       rho_i from (x, y), rho_j from (sx / 32, sy / 32): the squares and their sum are exact,
+ *                                                         the division rounds once
+ *       e1 = rho_i - rho_j, e2 = rho_i rho_i - rho_j rho_j, e3 = (rho_i rho_i) rho_i - (rho_j rho_j) rho_j
+ *       r_c = (d_c - (lg[i][c] - lg[j][c])) - ((a1 e1 + a2 e2) + a3 e3), m = max_c |r_c|
+ *       wt = m > tau ? tau / m : 1          (tau > 0; +infinity: every weight is 1)
+ *     and the pair's sums are, at [0] wt; [1 .. 3] wt e_k; [4 .. 9] wt e_k e_l for (k, l) = 11, 12,
+ *     13, 22, 23, 33; and at [10 + 5 c ..] per channel wt d_c, wt d_c e_1, wt d_c e_2, wt d_c e_3,
+ *     wt d_c d_c.  No floating-point atomics: per-thread sums, a wave butterfly, per-workgroup
+ *     partials (in a buffer of the context; it grows on demand, the call then waits for the stream
+ *     first) and a second kernel that adds a pair's partials, all in a fixed order - two calls give
+ *     the same bytes, and a pair's sums do not depend on what else is in the batch.  A pair
+ *     without a sample gets 25 zeros.  PANO_EINVAL, with nothing launched: a null pointer,
+ *     n_frames < 1, n_pairs < 0, a side, a pitch below 3 w, step < 1 or > PANO_PHOTO_MAX_SIDE, lo < 1, hi > 255, lo > hi, a
+ *     pair index out of range, i == j, an H, log-gain or alpha that is not finite, tau that is not
+ *     a number or <= 0.  n_pairs == 0 launches nothing.  Asynchronous on the stream.
+ * pano_photo_apply_u8: ONE call corrects n uint8 [h][w][3] frames (any n, any sizes 1 ..
+ *     PANO_PHOTO_MAX_SIDE) by their tables.  frames: HOST records; src, dst, table: dev; table is
+ *     float32 [3][PANO_PHOTO_TABLE], T[c][k] the factor of channel c at rho = k / 1024.  Per pixel
+ *       d2 = (2x + 1 - w)^2 + (2y + 1 - h)^2 (64-bit integers), s = (double)d2 / (double)(w^2 + h^2)
+ *       * 1024.0, k = (int)s, t = (float)(s - k), f = T[c][k] + t (T[c][k + 1] - T[c][k]) in float32
+ *       without a fused multiply-add, out = rint(min(v f, 255)) (ties to even).
+ *     dst == src with equal pitches is allowed (the correction is pointwise); any other overlap of
+ *     a frame's dst with its src is refused, as are a null pointer, a side, a pitch below 3 w and
+ *     n < 1 (PANO_EINVAL, nothing launched).  The records travel in a buffer of the context; one
+ *     launch per 64 frames, asynchronous on the stream. */
+#define PANO_PHOTO_MAX_SIDE 32767
+#define PANO_PHOTO_SUMS 25
+#define PANO_PHOTO_TABLE 1026
+typedef struct pano_photo_frame {
+    const uint8_t *img;        /* dev uint8 [h][w][3], rows pitch bytes apart       */
+    int64_t pitch;
+    int32_t w, h;
+} pano_photo_frame;
+typedef struct pano_photo_pair {
+    double H[9];               /* centred pixels of frame i -> centred pixels of j  */
+    int32_t i, j;
+} pano_photo_pair;
+typedef struct pano_photo_apply {
+    const uint8_t *src;        /* dev uint8 [h][w][3], rows src_pitch bytes apart   */
+    uint8_t *dst;              /* dev, the same size; may be src itself             */
+    const float *table;        /* dev float32 [3][PANO_PHOTO_TABLE]                 */
+    int64_t src_pitch, dst_pitch;
+    int32_t w, h;
+} pano_photo_apply;
+int pano_photo_stats(pano_ctx *ctx, const pano_photo_frame *frames, int n_frames,
+                     const pano_photo_pair *pairs, int n_pairs, int step, int lo, int hi,
+                     const double *log_gains, const double *alpha, double tau, double *sums);
+int pano_photo_apply_u8(pano_ctx *ctx, const pano_photo_apply *frames, int n);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -99,6 +99,10 @@ FILL_TAIL_PIXELS = 4096
 LENS_MAX_SIDE = 32767
 LENS_BROWN, LENS_FISHEYE = 0, 1
 LENS_CUBIC, LENS_LINEAR = 0, 1
+# pano_photo_stats / pano_photo_apply_u8: PANO_PHOTO_MAX_SIDE, PANO_PHOTO_SUMS, PANO_PHOTO_TABLE
+PHOTO_MAX_SIDE = 32767
+PHOTO_SUMS = 25
+PHOTO_TABLE = 1026
 JPEG_BATCH_MAX = 16384
 JPEG_BATCH_MAX_BLOCKS = 1 << 28
 
@@ -129,6 +133,23 @@ class LensFrame(C.Structure):
                 ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("f_new", C.c_double), ("k", C.c_double * 5),
                 ("w", C.c_int32), ("h", C.c_int32), ("model", C.c_int32), ("interp", C.c_int32)]
+
+
+class PhotoFrame(C.Structure):
+    """``pano_photo_frame`` of include/pano360.h (24 bytes)."""
+    _fields_ = [("img", C.c_void_p), ("pitch", C.c_int64), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class PhotoPair(C.Structure):
+    """``pano_photo_pair`` of include/pano360.h (80 bytes)."""
+    _fields_ = [("H", C.c_double * 9), ("i", C.c_int32), ("j", C.c_int32)]
+
+
+class PhotoApply(C.Structure):
+    """``pano_photo_apply`` of include/pano360.h (48 bytes)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("table", C.c_void_p),
+                ("src_pitch", C.c_int64), ("dst_pitch", C.c_int64),
+                ("w", C.c_int32), ("h", C.c_int32)]
 
 
 class Pair(C.Structure):
@@ -260,6 +281,9 @@ _SIGNATURES = {
     "pano_fill_u8": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _i, _vp, C.c_int64]),
     "pano_select_u8": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_int64]),
     "pano_lens_undistort_u8": (_i, [_vp, C.POINTER(LensFrame), _i]),
+    "pano_photo_stats": (_i, [_vp, C.POINTER(PhotoFrame), _i, C.POINTER(PhotoPair), _i, _i, _i, _i,
+                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _vp]),
+    "pano_photo_apply_u8": (_i, [_vp, C.POINTER(PhotoApply), _i]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -90,6 +90,7 @@ enum PanoKernelId {
     PK_DEFLATE_SCAN,
     PK_DEFLATE_EMIT,
     PK_DEFLATE_LENGTHS,
+    PK_PHOTO_STATS,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------
@@ -158,6 +159,10 @@ enum PanoBufId {
     BUF_FILL_DEV,
     // pano_lens_undistort_u8 (lens.hip): the batch's frame records
     BUF_LENS_DEV,
+    // pano_photo_stats / pano_photo_apply_u8 (photo.hip): the batch's records, and the statistics'
+    // per-workgroup partial sums
+    BUF_PHOTO_DEV,
+    BUF_PHOTO_PARTIALS,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it

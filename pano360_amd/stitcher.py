@@ -28,6 +28,7 @@ import numpy as np
 from . import bundle_adj as _ba
 from . import engine as _eng
 from . import lens as _lens
+from . import photo as _photo
 from .engine import CylProj, SphProj  # noqa: F401  (re-exported API)
 
 MAX_RESOLUTION = 1400       # read at call time, like the reference (stitcher.py:17,154)
@@ -479,8 +480,10 @@ def parse_args(argv=None):
                              "mosaic and --deepzoom show no ragged border, and --view, --equirect, "
                              "--cube and --multires no black outside the mosaic (not with --crop).")
     _lens.add_arguments(parser)
+    _photo.add_arguments(parser)
     args = parser.parse_args(argv)
     _lens.check_arguments(parser, args)
+    _photo.check_arguments(parser, args)
     if args.ghost_tol is not None and args.blend != "median":
         parser.error("--ghost-tol needs -b median")
     if args.fill and args.crop:
@@ -546,6 +549,13 @@ def main(argv=None):
         for reg, frame in zip(regions, frames):
             if reg.img is None:
                 reg.img = frame
+    if _photo.mode_of(args) is not None:
+        # after the registration, which sees the frames as they are (no cache name changes),
+        # and before the stitch: every blender, --crop, --fill, the views and the tiles get
+        # the corrected frames
+        start = time.time()
+        _photo.correct_regions(regions, _photo.MODES[_photo.mode_of(args)])
+        logging.info(f"Photometric alignment, time: {time.time() - start}")
 
     start = time.time()
     background = None
