@@ -366,6 +366,29 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _engine(eng):
+    """``eng``, or the process's engine."""
+    from . import engine
+    return eng or engine.engine()
+
+
+def rgb_on_device(img, eng):
+    """A [h][w][3] host array or tensor as a tensor on ``eng``'s device whose pixels are 3 elements
+    apart and whose rows are at least 3 w apart - what the native calls take with a row pitch.  A
+    host array is uploaded (a read-only one is copied first: torch wraps writable memory only); a
+    tensor is copied only when its strides are not like that, so a crop view of a dense image is
+    returned as it is, the same object when it is on the device already."""
+    import numpy as np
+    import torch
+    if not isinstance(img, torch.Tensor):
+        img = np.ascontiguousarray(img)
+        img = torch.from_numpy(img if img.flags.writeable else img.copy())
+    img = img.to(torch.device(eng.device))
+    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * img.shape[1]:
+        img = img.contiguous()
+    return img
+
+
 def check(status, what):
     if status != 0:
         msg = lib().pano_last_error().decode("utf-8", "replace")

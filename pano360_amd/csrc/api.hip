@@ -107,6 +107,20 @@ int pano_buf_reserve(PanoBuf &b, size_t need, bool pinned, size_t slack) {
     return PANO_OK;
 }
 
+int pano_buf_reserve_sync(pano_ctx *ctx, int id, size_t need, hipStream_t stream) {
+    PanoBuf &b = ctx->buf[id];
+    // the last call's kernels may still use the old buffer
+    if (b.p && need > b.cap) PANO_HIP(hipStreamSynchronize(stream));
+    return pano_buf_reserve(b, need, false);
+}
+
+int pano_buf_upload(pano_ctx *ctx, int id, const void *host, size_t bytes, hipStream_t stream) {
+    if (int rc = pano_buf_reserve_sync(ctx, id, bytes, stream)) return rc;
+    // pageable source: the runtime stages it before returning
+    PANO_HIP(hipMemcpyAsync(ctx->buf[id].p, host, bytes, hipMemcpyHostToDevice, stream));
+    return PANO_OK;
+}
+
 extern "C" int pano_ctx_destroy(pano_ctx *ctx) {
     if (!ctx) return PANO_OK;
     PANO_HIP(hipSetDevice(ctx->device));

@@ -170,6 +170,11 @@ enum PanoBufId {
 // old contents are lost, and NOTHING here waits for queued work that still uses them: a caller
 // whose stream may not be idle synchronises first, and only when `need > b.cap`.
 int pano_buf_reserve(PanoBuf &b, size_t need, bool pinned, size_t slack = 0);
+// pano_buf_reserve of the context's device buffer `id` when kernels queued on `stream` may still
+// use the old one: waits for the stream first, and only when the buffer exists and must grow.
+int pano_buf_reserve_sync(pano_ctx *ctx, int id, size_t need, hipStream_t stream);
+// ... and then queues the copy of `bytes` bytes of pageable host memory into it.
+int pano_buf_upload(pano_ctx *ctx, int id, const void *host, size_t bytes, hipStream_t stream);
 
 #define GEOM_BUFS 11
 #define STITCH_SIG 13             // stitch.hip: stitch_signature

@@ -221,11 +221,9 @@ extern "C" int pano_fill_u8(pano_ctx *ctx, const uint8_t *img, int64_t img_pitch
                  "pano_fill_u8: in place, but the pitches are %lld and %lld", (long long)img_pitch,
                  (long long)out_pitch);
     const hipStream_t s = (hipStream_t)stream;
-    PanoBuf &work = ctx->buf[BUF_FILL_DEV];
-    // the last fill's kernels may still use the old buffer
-    if (work.p && (size_t)L.bytes > work.cap) PANO_HIP(hipStreamSynchronize(s));
-    if (int rc = pano_buf_reserve(work, (size_t)L.bytes, false)) return rc;
-    uint8_t *const base = (uint8_t *)work.p;
+    // (the last fill's kernels may still use the old buffer)
+    if (int rc = pano_buf_reserve_sync(ctx, BUF_FILL_DEV, (size_t)L.bytes, s)) return rc;
+    uint8_t *const base = (uint8_t *)ctx->buf[BUF_FILL_DEV].p;
     uint32_t *const any = (uint32_t *)base;
     const auto level = [&](int l) { return (float4 *)(base + L.off[l]); };
     const auto grid = [](int64_t pixels) { return capped_grid(ceil_div(pixels, FILL_BLOCK), FILL_MAX_GROUPS); };

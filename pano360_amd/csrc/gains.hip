@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void overlap_stats_kernel(
     const uint8_t *__restrict__ fi = ci->frame, *__restrict__ fj = cj->frame;
     const double *__restrict__ hat_x = cj->hat_x, *__restrict__ hat_y = cj->hat_y;
     const int x = tx0 + threadIdx.x;
-    double cnt = 0.0, sum_i = 0.0, sum_j = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};                 // the count, the sums of frame i and of frame j
     if (x < w) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -104,47 +104,25 @@ __global__ __launch_bounds__(256) void overlap_stats_kernel(
             const uint8_t *p00 = fj + ((size_t)sy * sw + sx) * 3, *p01 = p00 + 3;
             const uint8_t *p10 = p00 + (size_t)sw * 3, *p11 = p10 + 3;
             const uint8_t *q = fi + ((size_t)y * w + x) * 3;
-            cnt += 1.0;
+            acc[0] += 1.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                sum_j += (double)lerp4(s_lut[p00[c]], s_lut[p01[c]], s_lut[p10[c]],
-                                       s_lut[p11[c]], tp);
-                sum_i += (double)s_lut[q[c]];
+                acc[2] += (double)lerp4(s_lut[p00[c]], s_lut[p01[c]], s_lut[p10[c]],
+                                        s_lut[p11[c]], tp);
+                acc[1] += (double)s_lut[q[c]];
             }
         }
     }
-    cnt = wave_sum(cnt);
-    sum_i = wave_sum(sum_i);
-    sum_j = wave_sum(sum_j);
-    if (threadIdx.x == 0) {
-        s_red[threadIdx.y][0] = cnt;
-        s_red[threadIdx.y][1] = sum_i;
-        s_red[threadIdx.y][2] = sum_j;
-    }
-    __syncthreads();
-    if (tid < 3)
-        out[tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
+    const double sum = block_sum_fixed<3>(acc, s_red, threadIdx.x, threadIdx.y);
+    if (tid < 3) out[tid] = sum;
 }
 
-// stats[pair] = sum of the pair's partials, in a fixed order.
+// stats[pair] = sum of the pair's nblk partials (pair after pair), in a fixed order.
 __global__ __launch_bounds__(256) void overlap_reduce_kernel(const double *__restrict__ partials,
                                                              int nblk, double *__restrict__ stats) {
     __shared__ double s_red[4][3];
-    const double *src = partials + (size_t)blockIdx.x * nblk * 3;
-    double acc[3] = {0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < nblk; b += 256)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) acc[k] += src[(size_t)b * 3 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s_red[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < 3)
-        stats[(size_t)blockIdx.x * 3 + threadIdx.x] =
-            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) +
-            (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
+    const double sum = block_sum_partials<3>(partials + (size_t)blockIdx.x * nblk * 3, nblk, s_red);
+    if (threadIdx.x < 3) stats[(size_t)blockIdx.x * 3 + threadIdx.x] = sum;
 }
 
 extern "C" int pano_overlap_blocks(int h, int w) {

@@ -120,6 +120,76 @@ __device__ __forceinline__ void unpack_row(TapBytes &t, int r, uint32_t lo, uint
     t.v[2 * r + 1][2] = byte1_x4(hi);
 }
 
+// unpack_row's plain-byte sibling (lens.hip, photo.hip): px[0] and px[1] are the RGB of the two
+// neighbouring pixels whose six bytes start at `a`, fetched as one dword and one halfword at any
+// alignment.
+__device__ __forceinline__ void rgb2_load(frame_ptr a, uint32_t px[2][3]) {
+    const uint32_t lo = *(frame_ptr32)a, hi = *(frame_ptr16)(a + 4);
+    px[0][0] = lo & 255u, px[0][1] = (lo >> 8) & 255u, px[0][2] = (lo >> 16) & 255u;
+    px[1][0] = lo >> 24, px[1][1] = hi & 255u, px[1][2] = hi >> 8;
+}
+
+// Four neighbouring pixels of a row are twelve bytes are three dwords: b[j] is the RGB of pixel
+// u0 + j of a row of w, whose pixel u0 is at p.  Three dword accesses when the four are whole and p
+// is 4-aligned; else - a row's tail, an odd pitch or base - byte by byte, the pixels from w on
+// read as 0 and not written.  (A frame that is written lives in global memory like one that is
+// read; a pointer out of a record is generic to the compiler.)
+typedef __attribute__((address_space(1))) uint8_t *rgb_out_ptr;
+__device__ __forceinline__ void rgb4_unpack(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t b[4][3]) {
+    b[0][0] = d0 & 255u, b[0][1] = (d0 >> 8) & 255u, b[0][2] = (d0 >> 16) & 255u;
+    b[1][0] = d0 >> 24, b[1][1] = d1 & 255u, b[1][2] = (d1 >> 8) & 255u;
+    b[2][0] = (d1 >> 16) & 255u, b[2][1] = d1 >> 24, b[2][2] = d2 & 255u;
+    b[3][0] = (d2 >> 8) & 255u, b[3][1] = (d2 >> 16) & 255u, b[3][2] = d2 >> 24;
+}
+__device__ __forceinline__ void rgb4_load(frame_ptr p, int u0, int w, uint32_t b[4][3]) {
+    if (u0 + 4 <= w && ((uintptr_t)p & 3) == 0) {
+        typedef const __attribute__((address_space(1))) uint32_t *in_ptr32;
+        rgb4_unpack(((in_ptr32)p)[0], ((in_ptr32)p)[1], ((in_ptr32)p)[2], b);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b[j][0] = b[j][1] = b[j][2] = 0;
+            if (u0 + j < w) b[j][0] = p[3 * j], b[j][1] = p[3 * j + 1], b[j][2] = p[3 * j + 2];
+        }
+    }
+}
+__device__ __forceinline__ void rgb4_store(rgb_out_ptr q, int u0, int w, const uint32_t b[4][3]) {
+    if (u0 + 4 <= w && ((uintptr_t)q & 3) == 0) {
+        typedef __attribute__((address_space(1))) uint32_t *out_ptr32;
+        const out_ptr32 q4 = (out_ptr32)q;
+        q4[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
+        q4[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
+        q4[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (u0 + j < w) {
+                q[3 * j] = (uint8_t)b[j][0];
+                q[3 * j + 1] = (uint8_t)b[j][1];
+                q[3 * j + 2] = (uint8_t)b[j][2];
+            }
+    }
+}
+
+// Host: frame i of entry point `who` has sides 1 .. max_side and pitches of 3 w or more, and dst's
+// rectangle of h rows of 3 w bytes misses src's or - in_place: the kernel reads a pixel before it
+// writes it - is src's.
+static inline int rgb_frames_check(const char *who, int i, const void *src, int64_t src_pitch, const void *dst,
+                                   int64_t dst_pitch, int w, int h, int max_side, bool in_place) {
+    PANO_REQUIRE(w >= 1 && h >= 1 && w <= max_side && h <= max_side, "%s: frame %d: %d x %d (sides 1 .. %d)",
+                 who, i, w, h, max_side);
+    PANO_REQUIRE(src_pitch >= 3 * (int64_t)w && dst_pitch >= 3 * (int64_t)w,
+                 "%s: frame %d: pitches %lld, %lld for %d pixels", who, i, (long long)src_pitch,
+                 (long long)dst_pitch, w);
+    // (a frame's last row ends with its last pixel, not with its pitch)
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    const uintptr_t s1 = s0 + (uintptr_t)(h - 1) * (uintptr_t)src_pitch + 3 * (uintptr_t)w;
+    const uintptr_t d1 = d0 + (uintptr_t)(h - 1) * (uintptr_t)dst_pitch + 3 * (uintptr_t)w;
+    PANO_REQUIRE((in_place && s0 == d0 && src_pitch == dst_pitch) || d1 <= s0 || s1 <= d0,
+                 "%s: frame %d: dst overlaps src%s", who, i, in_place ? " without being src" : "");
+    return PANO_OK;
+}
+
 __device__ __forceinline__ TapBytes load_taps(const uint8_t *__restrict__ frame, int sw,
                                               const Taps &tp) {
     TapBytes t;

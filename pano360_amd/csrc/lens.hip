@@ -8,7 +8,7 @@
 // the same bytes.
 #include <math.h>
 
-#include "common.h"
+#include "batch.h"
 #include "geom.h"
 
 #define LENS_PX 4                   // neighbouring pixels of a row a thread owns: 12 bytes, 3 dwords
@@ -19,7 +19,7 @@
 
 struct LensDev {                    // a frame of a launch, in device memory
     pano_lens_frame f;
-    int block0, tiles_x;            // the frame's first workgroup in the grid, workgroups per tile row
+    TileSlot slot;
     int reserved[2];
 };
 
@@ -68,10 +68,6 @@ __device__ __forceinline__ void lens_weights(int f5, float w[TAPS]) {
     }
 }
 
-__device__ __forceinline__ float lens_byte(uint32_t word, int k) {
-    return (float)((word >> (8 * k)) & 0xffu);
-}
-
 // ((p0 w0 + p1 w1) + p2 w2) + p3 w3, one rounding per operation
 template <int TAPS>
 __device__ __forceinline__ float lens_dot(const float p[TAPS], const float w[TAPS]) {
@@ -100,18 +96,14 @@ __device__ __forceinline__ void lens_sample(frame_ptr src, int64_t pitch, int w,
         float p[3][TAPS];
         if (inside) {
             const frame_ptr a = row + 3 * x0;
-            const uint32_t d0 = *(frame_ptr32)a;
-            if constexpr (TAPS == 4) {
-                const uint32_t d1 = *(frame_ptr32)(a + 4), d2 = *(frame_ptr32)(a + 8);
-                p[0][0] = lens_byte(d0, 0), p[1][0] = lens_byte(d0, 1), p[2][0] = lens_byte(d0, 2);
-                p[0][1] = lens_byte(d0, 3), p[1][1] = lens_byte(d1, 0), p[2][1] = lens_byte(d1, 1);
-                p[0][2] = lens_byte(d1, 2), p[1][2] = lens_byte(d1, 3), p[2][2] = lens_byte(d2, 0);
-                p[0][3] = lens_byte(d2, 1), p[1][3] = lens_byte(d2, 2), p[2][3] = lens_byte(d2, 3);
-            } else {
-                const uint32_t d1 = *(frame_ptr16)(a + 4);
-                p[0][0] = lens_byte(d0, 0), p[1][0] = lens_byte(d0, 1), p[2][0] = lens_byte(d0, 2);
-                p[0][1] = lens_byte(d0, 3), p[1][1] = lens_byte(d1, 0), p[2][1] = lens_byte(d1, 1);
-            }
+            uint32_t px[TAPS][3];
+            if constexpr (TAPS == 4)
+                rgb4_unpack(*(frame_ptr32)a, *(frame_ptr32)(a + 4), *(frame_ptr32)(a + 8), px);
+            else
+                rgb2_load(a, px);
+#pragma unroll
+            for (int t = 0; t < TAPS; ++t)
+                p[0][t] = (float)px[t][0], p[1][t] = (float)px[t][1], p[2][t] = (float)px[t][2];
         } else {
 #pragma unroll
             for (int t = 0; t < TAPS; ++t) {
@@ -128,23 +120,14 @@ __device__ __forceinline__ void lens_sample(frame_ptr src, int64_t pitch, int w,
 }
 
 // One workgroup per 64 x 16 tile of one frame, one thread per four neighbouring pixels of a row.
-// The frame comes from the table's prefix of workgroup counts (workgroup-uniform: the record is
-// read with scalar loads).
+// The frame comes from the table's prefix of workgroup counts (batch.h).
 __global__ __launch_bounds__(LENS_GX *LENS_GY) void lens_undistort_kernel(
     const LensDev *__restrict__ table, int n) {
-    int lo = 0, hi = n - 1;                             // the last frame whose block0 <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)blockIdx.x >= table[mid].block0)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const LensDev &D = table[lo];
+    int tile;
+    const LensDev &D = batch_record(table, n, tile);
     const pano_lens_frame &F = D.f;
-    const int tile = (int)blockIdx.x - D.block0;
-    const int u0 = (tile % D.tiles_x) * LENS_TX + ((int)threadIdx.x % LENS_GX) * LENS_PX;
-    const int v = (tile / D.tiles_x) * LENS_GY + (int)threadIdx.x / LENS_GX;
+    const int u0 = (tile % D.slot.tiles_x) * LENS_TX + ((int)threadIdx.x % LENS_GX) * LENS_PX;
+    const int v = (tile / D.slot.tiles_x) * LENS_GY + (int)threadIdx.x / LENS_GX;
     const int w = F.w, h = F.h;
     if (u0 >= w || v >= h) return;
     const frame_ptr src = (frame_ptr)F.src;
@@ -164,39 +147,14 @@ __global__ __launch_bounds__(LENS_GX *LENS_GY) void lens_undistort_kernel(
                 lens_sample<2>(src, pitch, w, h, ix, iy, fx5, fy5, b[j]);
         }
     }
-    // (frames live in global memory; a pointer read out of a record is generic to the compiler)
-    typedef __attribute__((address_space(1))) uint8_t *out_ptr;
-    typedef __attribute__((address_space(1))) uint32_t *out_ptr32;
-    const out_ptr q = (out_ptr)F.dst + (int64_t)v * F.dst_pitch + 3 * u0;
-    if (u0 + LENS_PX <= w && ((uintptr_t)q & 3) == 0) {
-        const out_ptr32 q4 = (out_ptr32)q;              // 12 bytes as three dwords
-        q4[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
-        q4[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
-        q4[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
-    } else {                                            // a row's tail, an odd pitch or base
-#pragma unroll
-        for (int j = 0; j < LENS_PX; ++j)
-            if (u0 + j < w) {
-                q[3 * j] = (uint8_t)b[j][0];
-                q[3 * j + 1] = (uint8_t)b[j][1];
-                q[3 * j + 2] = (uint8_t)b[j][2];
-            }
-    }
+    rgb4_store((rgb_out_ptr)F.dst + (int64_t)v * F.dst_pitch + 3 * u0, u0, w, b);
 }
 
 static int lens_check(const pano_lens_frame &F, int i) {
     PANO_REQUIRE(F.src && F.dst, "pano_lens_undistort_u8: frame %d: null pointer", i);
-    PANO_REQUIRE(F.w >= 1 && F.h >= 1 && F.w <= PANO_LENS_MAX_SIDE && F.h <= PANO_LENS_MAX_SIDE,
-                 "pano_lens_undistort_u8: frame %d: %d x %d (sides 1 .. %d)", i, F.w, F.h,
-                 PANO_LENS_MAX_SIDE);
-    PANO_REQUIRE(F.src_pitch >= 3 * (int64_t)F.w && F.dst_pitch >= 3 * (int64_t)F.w,
-                 "pano_lens_undistort_u8: frame %d: pitches %lld, %lld for %d pixels", i,
-                 (long long)F.src_pitch, (long long)F.dst_pitch, F.w);
-    // (a frame's last row ends with its last pixel, not with its pitch)
-    const uintptr_t s0 = (uintptr_t)F.src, d0 = (uintptr_t)F.dst;
-    const uintptr_t s1 = s0 + (uintptr_t)(F.h - 1) * (uintptr_t)F.src_pitch + 3 * (uintptr_t)F.w;
-    const uintptr_t d1 = d0 + (uintptr_t)(F.h - 1) * (uintptr_t)F.dst_pitch + 3 * (uintptr_t)F.w;
-    PANO_REQUIRE(d1 <= s0 || s1 <= d0, "pano_lens_undistort_u8: frame %d: dst overlaps src", i);
+    if (int rc = rgb_frames_check("pano_lens_undistort_u8", i, F.src, F.src_pitch, F.dst, F.dst_pitch, F.w,
+                                  F.h, PANO_LENS_MAX_SIDE, false))
+        return rc;
     bool finite = isfinite(F.fx) && isfinite(F.fy) && isfinite(F.cx) && isfinite(F.cy) &&
                   isfinite(F.f_new);
     for (int k = 0; k < 5; ++k) finite = finite && isfinite(F.k[k]);
@@ -217,30 +175,18 @@ extern "C" int pano_lens_undistort_u8(pano_ctx *ctx, const pano_lens_frame *fram
     for (int i = 0; i < n; ++i)                         // (nothing is queued for a refused batch)
         if (int rc = lens_check(frames[i], i)) return rc;
 
-    // the whole table goes up at once; a launch takes LENS_CHUNK records of it
     std::vector<LensDev> table((size_t)n);
     std::vector<int> blocks((size_t)ceil_div(n, LENS_CHUNK), 0);
     for (int i = 0; i < n; ++i) {
         LensDev &D = table[i];
         D.f = frames[i];
-        D.tiles_x = ceil_div(D.f.w, LENS_TX);
-        D.block0 = blocks[i / LENS_CHUNK];              // (a chunk has at most 64 x 2^19 workgroups)
         D.reserved[0] = D.reserved[1] = 0;
-        blocks[i / LENS_CHUNK] += D.tiles_x * ceil_div(D.f.h, LENS_GY);
+        batch_assign<PANO_LENS_MAX_SIDE, LENS_TX, LENS_GY, LENS_CHUNK>(D.slot, blocks.data(), i, D.f.w, D.f.h);
     }
     const hipStream_t s = (hipStream_t)stream;
-    PanoBuf &dev = ctx->buf[BUF_LENS_DEV];
-    const size_t bytes = table.size() * sizeof(LensDev);
-    // the last call's kernels may still read the old buffer
-    if (dev.p && bytes > dev.cap) PANO_HIP(hipStreamSynchronize(s));
-    if (int rc = pano_buf_reserve(dev, bytes, false)) return rc;
-    // pageable source: the runtime stages it before returning
-    PANO_HIP(hipMemcpyAsync(dev.p, table.data(), bytes, hipMemcpyHostToDevice, s));
-    for (int first = 0; first < n; first += LENS_CHUNK) {
-        const int count = n - first < LENS_CHUNK ? n - first : LENS_CHUNK;
-        hipLaunchKernelGGL(lens_undistort_kernel, dim3((unsigned)blocks[first / LENS_CHUNK]),
-                           dim3(LENS_GX * LENS_GY), 0, s, (const LensDev *)dev.p + first, count);
-        PANO_LAUNCH_CHECK("lens_undistort_kernel");
-    }
-    return PANO_OK;
+    return batch_run(ctx, BUF_LENS_DEV, table, LENS_CHUNK, blocks.data(), s, "lens_undistort_kernel",
+                     [&](const LensDev *records, int count, int grid) {
+        hipLaunchKernelGGL(lens_undistort_kernel, dim3((unsigned)grid), dim3(LENS_GX * LENS_GY), 0, s, records,
+                           count);
+    });
 }

@@ -8,7 +8,7 @@
 // fixed order and a second kernel adds a pair's partials in a fixed order.
 #include <math.h>
 
-#include "common.h"
+#include "batch.h"
 #include "geom.h"
 #include "wave.h"
 
@@ -24,7 +24,7 @@ struct PhotoPairDev {               // a pair of a launch, in device memory
     int64_t pitch_i, pitch_j;
     int64_t part0;                  // the pair's first partial in the buffer
     int wi, hi, wj, hj;
-    int block0, tiles_x;            // the pair's first workgroup in its launch, tiles per tile row
+    TileSlot slot;
     int nblk, reserved;
 };
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ double photo_rho(double a, double b, double den) {
 
 // One workgroup per 64 x 16 tile of one pair's lattice (every step-th pixel of frame i), a thread
 // takes four lattice rows of a column.  The pair comes from the table's prefix of workgroup
-// counts (workgroup-uniform: the record is read with scalar loads).
+// counts (batch.h).
 __global__ __launch_bounds__(256) void photo_stats_kernel(
     const PhotoPairDev *__restrict__ table, int n, int step, int lo_v, int hi_v, double a1,
     double a2, double a3, double tau, double *__restrict__ partials) {
@@ -44,19 +44,11 @@ __global__ __launch_bounds__(256) void photo_stats_kernel(
     __shared__ double s_red[4][PH_NS];
     __shared__ int s_skip;
     const int tid = threadIdx.x;
-    int lo = 0, hi = n - 1;                             // the last pair whose block0 <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)blockIdx.x >= table[mid].block0)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const PhotoPairDev &P = table[lo];
-    const int tile = (int)blockIdx.x - P.block0;
+    int tile;
+    const PhotoPairDev &P = batch_record(table, n, tile);
     const int wi = P.wi, hgt_i = P.hi, wj = P.wj, hj = P.hj;
     const int lw = (wi + step - 1) / step, lh = (hgt_i + step - 1) / step;
-    const int tx0 = (tile % P.tiles_x) * PH_TW, ty0 = (tile / P.tiles_x) * PH_TH;
+    const int tx0 = (tile % P.slot.tiles_x) * PH_TW, ty0 = (tile / P.slot.tiles_x) * PH_TH;
     double *out = partials + (P.part0 + tile) * PH_NS;
     double H[9];
 #pragma unroll
@@ -104,6 +96,7 @@ __global__ __launch_bounds__(256) void photo_stats_kernel(
     if (lx < lw) {
         const int x = lx * step;
         const double xc = (double)x - cxi;
+#pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int ly = ty0 + wave * 4 + r;
             if (ly >= lh) break;
@@ -122,20 +115,17 @@ __global__ __launch_bounds__(256) void photo_stats_kernel(
             const float ty = (float)(sy - 32 * iy) * (1.0f / 32.0f);
             // a row's two taps are six neighbouring bytes; they end at 3 (ix + 2) - 1 <= 3 wj - 1
             const frame_ptr r0 = fj + (int64_t)iy * pitch_j + 3 * ix, r1 = r0 + pitch_j;
-            const uint32_t t0 = *(frame_ptr32)r0, t1 = *(frame_ptr16)(r0 + 4);
-            const uint32_t b0 = *(frame_ptr32)r1, b1 = *(frame_ptr16)(r1 + 4);
+            uint32_t t[2][3], b[2][3];
+            rgb2_load(r0, t);
+            rgb2_load(r1, b);
             const frame_ptr q = fi + (int64_t)y * pitch_i + 3 * x;
             const uint32_t vi[3] = {q[0], q[1], q[2]};
-            const float p00[3] = {(float)(t0 & 255u), (float)((t0 >> 8) & 255u), (float)((t0 >> 16) & 255u)};
-            const float p01[3] = {(float)(t0 >> 24), (float)(t1 & 255u), (float)(t1 >> 8)};
-            const float p10[3] = {(float)(b0 & 255u), (float)((b0 >> 8) & 255u), (float)((b0 >> 16) & 255u)};
-            const float p11[3] = {(float)(b0 >> 24), (float)(b1 & 255u), (float)(b1 >> 8)};
             float vj[3];
             bool ok = true;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float top = p00[c] * (1.0f - tx) + p01[c] * tx;
-                const float bot = p10[c] * (1.0f - tx) + p11[c] * tx;
+                const float top = (float)t[0][c] * (1.0f - tx) + (float)t[1][c] * tx;
+                const float bot = (float)b[0][c] * (1.0f - tx) + (float)b[1][c] * tx;
                 vj[c] = top * (1.0f - ty) + bot * ty;
                 ok = ok && vj[c] >= flo && vj[c] <= fhi && vi[c] >= (uint32_t)lo_v &&
                      vi[c] <= (uint32_t)hi_v;
@@ -179,39 +169,19 @@ __global__ __launch_bounds__(256) void photo_stats_kernel(
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < PH_NS; ++k) acc[k] = wave_sum(acc[k]);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < PH_NS; ++k) s_red[wave][k] = acc[k];
-    __syncthreads();
-    if (tid < PH_NS) out[tid] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
+    const double sum = block_sum_fixed<PH_NS>(acc, s_red, tid & 63, wave);
+    if (tid < PH_NS) out[tid] = sum;
 }
 
-// sums[pair] = the sum of the pair's partials, in a fixed order.
+// sums[pair] = the sum of the pair's partials, in a fixed order: the record says where they start
+// and how many they are.
 __global__ __launch_bounds__(256) void photo_reduce_kernel(const PhotoPairDev *__restrict__ table,
                                                            const double *__restrict__ partials,
                                                            double *__restrict__ sums) {
     __shared__ double s_red[4][PH_NS];
     const PhotoPairDev &P = table[blockIdx.x];
-    const double *src = partials + P.part0 * PH_NS;
-    const int nblk = P.nblk;
-    double acc[PH_NS];
-#pragma unroll
-    for (int k = 0; k < PH_NS; ++k) acc[k] = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 256)
-#pragma unroll
-        for (int k = 0; k < PH_NS; ++k) acc[k] += src[(size_t)b * PH_NS + k];
-#pragma unroll
-    for (int k = 0; k < PH_NS; ++k) acc[k] = wave_sum(acc[k]);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < PH_NS; ++k) s_red[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < PH_NS)
-        sums[(size_t)blockIdx.x * PH_NS + threadIdx.x] =
-            (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) +
-            (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
+    const double sum = block_sum_partials<PH_NS>(partials + P.part0 * PH_NS, P.nblk, s_red);
+    if (threadIdx.x < PH_NS) sums[(size_t)blockIdx.x * PH_NS + threadIdx.x] = sum;
 }
 
 extern "C" int pano_photo_stats(pano_ctx *ctx, const pano_photo_frame *frames, int n_frames,
@@ -261,35 +231,26 @@ extern "C" int pano_photo_stats(pano_ctx *ctx, const pano_photo_frame *frames, i
         D.fi = A.img, D.fj = B.img;
         D.pitch_i = A.pitch, D.pitch_j = B.pitch;
         D.wi = A.w, D.hi = A.h, D.wj = B.w, D.hj = B.h;
-        D.tiles_x = ceil_div(ceil_div(A.w, step), PH_TW);
-        D.nblk = D.tiles_x * ceil_div(ceil_div(A.h, step), PH_TH);
-        D.block0 = blocks[p / PH_CHUNK];                // (a chunk has at most 256 x 2^20 workgroups)
+        // (the lattice: every step-th pixel of frame i)
+        D.nblk = batch_assign<PANO_PHOTO_MAX_SIDE, PH_TW, PH_TH, PH_CHUNK>(
+            D.slot, blocks.data(), p, ceil_div(A.w, step), ceil_div(A.h, step));
         D.part0 = parts;
         D.reserved = 0;
-        blocks[p / PH_CHUNK] += D.nblk;
         parts += D.nblk;
     }
     const hipStream_t s = (hipStream_t)stream;
-    PanoBuf &dev = ctx->buf[BUF_PHOTO_DEV], &par = ctx->buf[BUF_PHOTO_PARTIALS];
-    const size_t bytes = table.size() * sizeof(PhotoPairDev);
-    const size_t par_bytes = (size_t)parts * PH_NS * sizeof(double);
-    // the last call's kernels may still use the old buffers
-    if ((dev.p && bytes > dev.cap) || (par.p && par_bytes > par.cap)) PANO_HIP(hipStreamSynchronize(s));
-    if (int rc = pano_buf_reserve(dev, bytes, false)) return rc;
-    if (int rc = pano_buf_reserve(par, par_bytes, false)) return rc;
-    // pageable source: the runtime stages it before returning
-    PANO_HIP(hipMemcpyAsync(dev.p, table.data(), bytes, hipMemcpyHostToDevice, s));
-    for (int first = 0; first < n_pairs; first += PH_CHUNK) {
-        const int count = n_pairs - first < PH_CHUNK ? n_pairs - first : PH_CHUNK;
-        PANO_TIMED(PK_PHOTO_STATS, s,
-                   hipLaunchKernelGGL(photo_stats_kernel, dim3((unsigned)blocks[first / PH_CHUNK]),
-                                      dim3(256), 0, s, (const PhotoPairDev *)dev.p + first, count,
-                                      step, lo, hi, alpha[0], alpha[1], alpha[2], tau,
-                                      (double *)par.p));
-        PANO_LAUNCH_CHECK("photo_stats_kernel");
-    }
+    if (int rc = pano_buf_reserve_sync(ctx, BUF_PHOTO_PARTIALS, (size_t)parts * PH_NS * sizeof(double), s))
+        return rc;
+    double *const par = (double *)ctx->buf[BUF_PHOTO_PARTIALS].p;
+    if (int rc = batch_run(ctx, BUF_PHOTO_DEV, table, PH_CHUNK, blocks.data(), s, "photo_stats_kernel",
+                           [&](const PhotoPairDev *records, int count, int grid) {
+            PANO_TIMED(PK_PHOTO_STATS, s,
+                       hipLaunchKernelGGL(photo_stats_kernel, dim3((unsigned)grid), dim3(256), 0, s, records,
+                                          count, step, lo, hi, alpha[0], alpha[1], alpha[2], tau, par));
+        }))
+        return rc;
     hipLaunchKernelGGL(photo_reduce_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s,
-                       (const PhotoPairDev *)dev.p, (const double *)par.p, sums);
+                       (const PhotoPairDev *)ctx->buf[BUF_PHOTO_DEV].p, (const double *)par, sums);
     PANO_LAUNCH_CHECK("photo_reduce_kernel");
     return PANO_OK;
 }
@@ -303,52 +264,26 @@ extern "C" int pano_photo_stats(pano_ctx *ctx, const pano_photo_frame *frames, i
 
 struct PhotoApplyDev {              // a frame of a launch, in device memory
     pano_photo_apply f;
-    int block0, tiles_x;            // the frame's first workgroup in the grid, workgroups per tile row
+    TileSlot slot;
 };
 
 // One workgroup per 64 x 16 tile of one frame, one thread per four neighbouring pixels of a row;
-// the frame comes from the table's prefix of workgroup counts, as in lens.hip.  A thread reads its
+// the frame comes from the table's prefix of workgroup counts (batch.h).  A thread reads its
 // twelve bytes before it writes them, so dst may be src.
 __global__ __launch_bounds__(PA_GX *PA_GY) void photo_apply_kernel(
     const PhotoApplyDev *__restrict__ table, int n) {
-    int lo = 0, hi = n - 1;                             // the last frame whose block0 <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)blockIdx.x >= table[mid].block0)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    const PhotoApplyDev &D = table[lo];
+    int tile;
+    const PhotoApplyDev &D = batch_record(table, n, tile);
     const pano_photo_apply &F = D.f;
-    const int tile = (int)blockIdx.x - D.block0;
-    const int u0 = (tile % D.tiles_x) * PA_TX + ((int)threadIdx.x % PA_GX) * PA_PX;
-    const int v = (tile / D.tiles_x) * PA_GY + (int)threadIdx.x / PA_GX;
+    const int u0 = (tile % D.slot.tiles_x) * PA_TX + ((int)threadIdx.x % PA_GX) * PA_PX;
+    const int v = (tile / D.slot.tiles_x) * PA_GY + (int)threadIdx.x / PA_GX;
     const int w = F.w, h = F.h;
     if (u0 >= w || v >= h) return;
     typedef const __attribute__((address_space(1))) float *table_ptr;
-    typedef const __attribute__((address_space(1))) uint32_t *in_ptr32;
-    typedef __attribute__((address_space(1))) uint8_t *out_ptr;
-    typedef __attribute__((address_space(1))) uint32_t *out_ptr32;
     const table_ptr T = (table_ptr)F.table;
-    const frame_ptr p = (frame_ptr)F.src + (int64_t)v * F.src_pitch + 3 * u0;
-    const out_ptr q = (out_ptr)F.dst + (int64_t)v * F.dst_pitch + 3 * u0;
-    const bool whole = u0 + PA_PX <= w;
 
     uint32_t b[PA_PX][3];
-    if (whole && ((uintptr_t)p & 3) == 0) {
-        const uint32_t d0 = ((in_ptr32)p)[0], d1 = ((in_ptr32)p)[1], d2 = ((in_ptr32)p)[2];
-        b[0][0] = d0 & 255u, b[0][1] = (d0 >> 8) & 255u, b[0][2] = (d0 >> 16) & 255u;
-        b[1][0] = d0 >> 24, b[1][1] = d1 & 255u, b[1][2] = (d1 >> 8) & 255u;
-        b[2][0] = (d1 >> 16) & 255u, b[2][1] = d1 >> 24, b[2][2] = d2 & 255u;
-        b[3][0] = (d2 >> 8) & 255u, b[3][1] = (d2 >> 16) & 255u, b[3][2] = d2 >> 24;
-    } else {
-#pragma unroll
-        for (int j = 0; j < PA_PX; ++j) {
-            b[j][0] = b[j][1] = b[j][2] = 0;
-            if (u0 + j < w) b[j][0] = p[3 * j], b[j][1] = p[3 * j + 1], b[j][2] = p[3 * j + 2];
-        }
-    }
+    rgb4_load((frame_ptr)F.src + (int64_t)v * F.src_pitch + 3 * u0, u0, w, b);
     const double den = (double)((int64_t)w * w + (int64_t)h * h);
     const int64_t dy = 2 * (int64_t)v + 1 - h;
 #pragma unroll
@@ -365,38 +300,13 @@ __global__ __launch_bounds__(PA_GX *PA_GY) void photo_apply_kernel(
             b[j][c] = (uint32_t)rintf(fmaxf(fminf((float)b[j][c] * f, 255.0f), 0.0f));
         }
     }
-    if (whole && ((uintptr_t)q & 3) == 0) {
-        const out_ptr32 q4 = (out_ptr32)q;              // 12 bytes as three dwords
-        q4[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
-        q4[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
-        q4[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
-    } else {                                            // a row's tail, an odd pitch or base
-#pragma unroll
-        for (int j = 0; j < PA_PX; ++j)
-            if (u0 + j < w) {
-                q[3 * j] = (uint8_t)b[j][0];
-                q[3 * j + 1] = (uint8_t)b[j][1];
-                q[3 * j + 2] = (uint8_t)b[j][2];
-            }
-    }
+    rgb4_store((rgb_out_ptr)F.dst + (int64_t)v * F.dst_pitch + 3 * u0, u0, w, b);
 }
 
 static int photo_apply_check(const pano_photo_apply &F, int i) {
     PANO_REQUIRE(F.src && F.dst && F.table, "pano_photo_apply_u8: frame %d: null pointer", i);
-    PANO_REQUIRE(F.w >= 1 && F.h >= 1 && F.w <= PANO_PHOTO_MAX_SIDE && F.h <= PANO_PHOTO_MAX_SIDE,
-                 "pano_photo_apply_u8: frame %d: %d x %d (sides 1 .. %d)", i, F.w, F.h,
-                 PANO_PHOTO_MAX_SIDE);
-    PANO_REQUIRE(F.src_pitch >= 3 * (int64_t)F.w && F.dst_pitch >= 3 * (int64_t)F.w,
-                 "pano_photo_apply_u8: frame %d: pitches %lld, %lld for %d pixels", i,
-                 (long long)F.src_pitch, (long long)F.dst_pitch, F.w);
-    // (a frame's last row ends with its last pixel, not with its pitch)
-    const uintptr_t s0 = (uintptr_t)F.src, d0 = (uintptr_t)F.dst;
-    const uintptr_t s1 = s0 + (uintptr_t)(F.h - 1) * (uintptr_t)F.src_pitch + 3 * (uintptr_t)F.w;
-    const uintptr_t d1 = d0 + (uintptr_t)(F.h - 1) * (uintptr_t)F.dst_pitch + 3 * (uintptr_t)F.w;
-    const bool in_place = s0 == d0 && F.src_pitch == F.dst_pitch;
-    PANO_REQUIRE(in_place || d1 <= s0 || s1 <= d0,
-                 "pano_photo_apply_u8: frame %d: dst overlaps src without being src", i);
-    return PANO_OK;
+    return rgb_frames_check("pano_photo_apply_u8", i, F.src, F.src_pitch, F.dst, F.dst_pitch, F.w, F.h,
+                            PANO_PHOTO_MAX_SIDE, true);
 }
 
 extern "C" int pano_photo_apply_u8(pano_ctx *ctx, const pano_photo_apply *frames, int n) {
@@ -411,22 +321,11 @@ extern "C" int pano_photo_apply_u8(pano_ctx *ctx, const pano_photo_apply *frames
     for (int i = 0; i < n; ++i) {
         PhotoApplyDev &D = table[i];
         D.f = frames[i];
-        D.tiles_x = ceil_div(D.f.w, PA_TX);
-        D.block0 = blocks[i / PA_CHUNK];                // (a chunk has at most 64 x 2^19 workgroups)
-        blocks[i / PA_CHUNK] += D.tiles_x * ceil_div(D.f.h, PA_GY);
+        batch_assign<PANO_PHOTO_MAX_SIDE, PA_TX, PA_GY, PA_CHUNK>(D.slot, blocks.data(), i, D.f.w, D.f.h);
     }
     const hipStream_t s = (hipStream_t)stream;
-    PanoBuf &dev = ctx->buf[BUF_PHOTO_DEV];
-    const size_t bytes = table.size() * sizeof(PhotoApplyDev);
-    // the last call's kernels may still read the old buffer
-    if (dev.p && bytes > dev.cap) PANO_HIP(hipStreamSynchronize(s));
-    if (int rc = pano_buf_reserve(dev, bytes, false)) return rc;
-    PANO_HIP(hipMemcpyAsync(dev.p, table.data(), bytes, hipMemcpyHostToDevice, s));
-    for (int first = 0; first < n; first += PA_CHUNK) {
-        const int count = n - first < PA_CHUNK ? n - first : PA_CHUNK;
-        hipLaunchKernelGGL(photo_apply_kernel, dim3((unsigned)blocks[first / PA_CHUNK]),
-                           dim3(PA_GX * PA_GY), 0, s, (const PhotoApplyDev *)dev.p + first, count);
-        PANO_LAUNCH_CHECK("photo_apply_kernel");
-    }
-    return PANO_OK;
+    return batch_run(ctx, BUF_PHOTO_DEV, table, PA_CHUNK, blocks.data(), s, "photo_apply_kernel",
+                     [&](const PhotoApplyDev *records, int count, int grid) {
+        hipLaunchKernelGGL(photo_apply_kernel, dim3((unsigned)grid), dim3(PA_GX * PA_GY), 0, s, records, count);
+    });
 }

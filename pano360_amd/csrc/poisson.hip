@@ -407,10 +407,8 @@ __global__ __launch_bounds__(PB_BLOCK) void pb_finish_kernel(const uint8_t *__re
 // ---- host ------------------------------------------------------------------------------------
 static int pb_reserve(pano_ctx *ctx, size_t bytes) {
     if (int rc = pano_buf_reserve(ctx->buf[BUF_POISSON_HOST], 4 * sizeof(PbChan), true)) return rc;
-    PanoBuf &dev = ctx->buf[BUF_POISSON_DEV];
-    // the last blend's finish kernel may still read the old buffer
-    if (dev.p && bytes > dev.cap) PANO_HIP(hipStreamSynchronize(ctx->stream));
-    return pano_buf_reserve(dev, bytes, false);
+    // (the last blend's finish kernel may still read the old buffer)
+    return pano_buf_reserve_sync(ctx, BUF_POISSON_DEV, bytes, ctx->stream);
 }
 
 extern "C" int pano_poisson_blend(pano_ctx *ctx, const uint8_t *src, uint8_t *tgt,

@@ -5,7 +5,7 @@
 // pano360_amd/view.py and a float64 NumPy statement of the arithmetic is tests/view_model.py.
 #include <math.h>
 
-#include "common.h"
+#include "batch.h"
 
 #define MIP_BLOCK 256
 #define MIP_MAX_GROUPS 4096         // grid cap of the mip kernel (it loops beyond it)
@@ -77,7 +77,7 @@ struct ViewDev {
     float p[4];                     // EQUIRECT: a0, sa, b0, sb; STEREOGRAPHIC: cx, cy, f
     uint8_t *image, *mask;
     int kind, w, h;
-    int block0, tiles_x;            // the view's first workgroup in the grid, workgroups per tile row
+    TileSlot slot;
 };
 
 struct ViewBatch {                  // a launch's arguments, by value: nothing to upload or keep alive
@@ -160,15 +160,13 @@ __device__ __forceinline__ void view_sample(const ViewBatch &B, int l, float fx,
     }
 }
 
-// One thread per output pixel, one workgroup per 32 x 8 tile of one view.  The footprint comes
-// from the thread's own evaluation of its right and lower neighbours' angles.
+// One thread per output pixel, one workgroup per 32 x 8 tile of one view (found as in batch.h).  The
+// footprint comes from the thread's own evaluation of its right and lower neighbours' angles.
 __global__ __launch_bounds__(VIEW_TX *VIEW_TY) void view_render_kernel(const ViewBatch B) {
-    int vi = 0;
-    while (vi + 1 < B.n && (int)blockIdx.x >= B.v[vi + 1].block0) ++vi;     // (workgroup-uniform)
-    const ViewDev &V = B.v[vi];
-    const int tile = (int)blockIdx.x - V.block0;
-    const int u = (tile % V.tiles_x) * VIEW_TX + (int)threadIdx.x;
-    const int v = (tile / V.tiles_x) * VIEW_TY + (int)threadIdx.y;
+    int tile;
+    const ViewDev &V = batch_record(B.v, B.n, tile);
+    const int u = (tile % V.slot.tiles_x) * VIEW_TX + (int)threadIdx.x;
+    const int v = (tile / V.slot.tiles_x) * VIEW_TY + (int)threadIdx.y;
     if (u >= V.w || v >= V.h) return;
 
     float theta, phi;
@@ -240,7 +238,7 @@ extern "C" int pano_view_render(pano_ctx *ctx, const uint8_t *mips, const int64_
     B.closed = mosaic->closed != 0;
     B.levels = n_levels;
     B.n = n;
-    int64_t blocks = 0;
+    int blocks = 0;
     for (int i = 0; i < n; ++i) {
         const pano_view &S = views[i];
         ViewDev &D = B.v[i];
@@ -265,10 +263,7 @@ extern "C" int pano_view_render(pano_ctx *ctx, const uint8_t *mips, const int64_
         D.kind = S.kind;
         D.w = S.w;
         D.h = S.h;
-        D.block0 = (int)blocks;
-        D.tiles_x = ceil_div(S.w, VIEW_TX);
-        blocks += (int64_t)D.tiles_x * ceil_div(S.h, VIEW_TY);
-        PANO_REQUIRE(blocks <= 0x7fffffff, "pano_view_render: the batch has too many pixels");
+        batch_assign<PANO_VIEW_MAX_SIDE, VIEW_TX, VIEW_TY, PANO_VIEW_MAX_VIEWS>(D.slot, &blocks, i, S.w, S.h);
     }
     const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(view_render_kernel, dim3((unsigned)blocks), dim3(VIEW_TX, VIEW_TY), 0, s, B);

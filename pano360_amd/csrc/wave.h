@@ -1,8 +1,8 @@
 // Wave and workgroup primitives of the kernels (gfx950: 64 lanes), and the one kernel that is
-// nothing but one of them.  All are for one-dimensional workgroups of whole waves, every lane
-// active at the call.  (The min / max / key reductions of blend.hip, own_tile.inc and crop.hip are
-// interleaved with other work and stay where they are; so do sums over fewer lanes or in another
-// order: blur_mfma.hip's 16-lane prefix, msop.hip's sum64.)
+// nothing but one of them.  All are for one-dimensional workgroups of whole waves (block_sum_fixed
+// also for 64 x 4), every lane active at the call.  (The min / max / key reductions of blend.hip,
+// own_tile.inc and crop.hip are interleaved with other work and stay where they are; so do sums
+// over fewer lanes or in another order: blur_mfma.hip's 16-lane prefix, msop.hip's sum64.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +14,37 @@ __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// The sums of N accumulators over a workgroup of 256 threads, one-dimensional or 64 x 4 (the
+// caller says which lane of which wave it is), in ONE fixed order - what makes the statistics of
+// gains.hip and photo.hip return the same bytes on every call: wave_sum of each accumulator, the
+// four waves' values through r (LDS of the caller's, one barrier), and thread k < N returns
+// (r[0][k] + r[1][k]) + (r[2][k] + r[3][k]); the other threads return 0.  Every addition is in the
+// order those kernels wrote out themselves before they shared this: another order, other bytes.
+template <int N>
+__device__ __forceinline__ double block_sum_fixed(double (&acc)[N], double (*r)[N], int lane,
+                                                  int wave) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] = wave_sum(acc[k]);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < N; ++k) r[wave][k] = acc[k];
+    __syncthreads();
+    const int k = wave * 64 + lane;
+    return k < N ? (r[0][k] + r[1][k]) + (r[2][k] + r[3][k]) : 0.0;
+}
+
+// block_sum_fixed of a pair's nblk partial sums (N doubles each, from src on): thread t adds
+// the partials t, t + 256, ... in that order.  One-dimensional workgroups of 256 threads.
+template <int N>
+__device__ __forceinline__ double block_sum_partials(const double *__restrict__ src, int nblk,
+                                                     double (*r)[N]) {
+    double acc[N] = {};
+    for (int b = threadIdx.x; b < nblk; b += 256)
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] += src[(size_t)b * N + k];
+    return block_sum_fixed<N>(acc, r, threadIdx.x & 63, threadIdx.x >> 6);
 }
 
 // Lane k's result: the sum of v over lanes 0 .. k.

@@ -61,16 +61,6 @@ def launches(h, w):
 
 
 # ------------------------------------------------------------------ the fill
-def _device_image(image, eng):
-    import torch
-    if not isinstance(image, torch.Tensor):
-        image = torch.from_numpy(np.ascontiguousarray(image))
-    image = image.to(torch.device(eng.device))
-    if image.stride(2) != 1 or image.stride(1) != 3 or image.stride(0) < 3 * image.shape[1]:
-        image = image.contiguous()
-    return image
-
-
 def _check_mask(mask, shape):
     if tuple(mask.shape) != tuple(shape):
         raise ValueError(f"a mask of shape {tuple(mask.shape)} for an image of {tuple(shape)}")
@@ -97,9 +87,9 @@ def fill_device(image, mask, closed=False, eng=None, out=None):
     import torch
     _view._check_mosaic(image)
     _check_mask(mask, image.shape[:2])
-    eng = _view._engine(eng)
+    eng = _lib._engine(eng)
     in_place = out is not None and out is image
-    image = _device_image(image, eng)
+    image = _lib.rgb_on_device(image, eng)
     if in_place and image is not out:
         raise ValueError("out=image: a device tensor whose rows' pixels are contiguous")
     mask = _device_mask(mask, eng)
@@ -121,7 +111,7 @@ def select_device(a, mask, b, eng=None, out=None):
     """``mask ? a : b`` per pixel of two dense uint8 [h][w][3] device tensors (``mask`` uint8
     [h][w]); ``out`` may be ``a`` or ``b``."""
     import torch
-    eng = _view._engine(eng)
+    eng = _lib._engine(eng)
     if a.shape != b.shape or tuple(mask.shape) != tuple(a.shape[:2]) or a.shape[-1] != 3:
         raise ValueError(f"images of {tuple(a.shape)} and {tuple(b.shape)}, a mask of {tuple(mask.shape)}")
     if out is None:
@@ -160,7 +150,7 @@ def sphere_device(mosaic, geom, valid=None, width=None, eng=None):
     neighbouring row rolled by ``width // 2``: the image continued over the pole, so that the
     renderer's row clamp never leaves a hole there.  uint8 [width // 2 + 2][width][3]."""
     import torch
-    eng = _view._engine(eng)
+    eng = _lib._engine(eng)
     width = sphere_width(geom) if width is None else int(width)
     sphere_geom = sphere_geometry(width)
     if valid is not None:
@@ -180,7 +170,7 @@ def render_filled_device(mosaic_or_mips, geom, views, background, eng=None):
     the same views of ``background`` = (``view.Mips`` or image, geometry) of ``sphere_device``.
     Covered pixels are bit for bit what ``render_device`` returns.  Returns (images, masks), the
     masks as from the mosaic's render."""
-    eng = _view._engine(eng)
+    eng = _lib._engine(eng)
     views = list(views)
     back_source, back_geom = background
     images, masks = _view.render_device(mosaic_or_mips, geom, views, eng)

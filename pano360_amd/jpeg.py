@@ -437,7 +437,7 @@ def decode_device(blobs, eng=None, want_coefs=False, _headers=None):
     import torch
     from . import _lib
     from . import engine as _eng
-    eng = eng or _eng.engine()
+    eng = _lib._engine(eng)
     headers = _headers or [parse(b) for b in blobs]
     for i, h in enumerate(headers):
         if h is None:
@@ -495,8 +495,8 @@ def read_images(paths, eng=None, max_packed=BATCH_PACKED, max_work=BATCH_WORK,
     ``plan_batches`` cuts to the budgets) or "pillow" (everything else, and a JPEG that fits no
     batch, exactly as before)."""
     import torch
-    from . import engine as _eng
-    eng = eng or _eng.engine()
+    from . import _lib
+    eng = _lib._engine(eng)
     blobs, headers = [], []
     for p in paths:
         with open(p, "rb") as fid:
@@ -626,15 +626,10 @@ def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_c
     if not encodable(img, quality, subsampling):
         raise ValueError(f"{tuple(img.shape)} {img.dtype} at quality {quality}, subsampling "
                          f"{subsampling}: not a case the device encodes")
-    eng = eng or _eng.engine()
+    eng = _lib._engine(eng)
     dev = torch.device(eng.device)
-    if not isinstance(img, torch.Tensor):
-        img = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-    elif img.device != dev:
-        img = img.to(dev)
+    img = _lib.rgb_on_device(img, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
-    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * w:
-        img = img.contiguous()
     sub = 2 if subsampling == -1 else subsampling
     lib = eng.lib
     work_bytes = int(lib.pano_jpeg_encode_work_bytes(h, w, sub))
@@ -716,7 +711,7 @@ def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=Non
     shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
     blocks = [encode_blocks(h, w, subsampling) for h, w in shapes]
     batches = plan_encode_batches(blocks, max_work)
-    eng = eng or _eng.engine()
+    eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     lib = eng.lib
     sub = 2 if subsampling == -1 else subsampling
@@ -726,14 +721,8 @@ def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=Non
         held = []                                       # uploads and copies live until the call ends
         table = (_lib.JpegImage * len(batch))()
         for rec, i in zip(table, batch):
-            img = images[i]
-            if not isinstance(img, torch.Tensor):
-                img = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-            elif img.device != dev:
-                img = img.to(dev)
+            img = _lib.rgb_on_device(images[i], eng)
             h, w = shapes[i]
-            if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * w:
-                img = img.contiguous()
             held.append(img)
             rec.img, rec.pitch, rec.h, rec.w = img.data_ptr(), img.stride(0), h, w
         total = sum(blocks[i] for i in batch)

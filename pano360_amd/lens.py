@@ -224,7 +224,6 @@ def undistort_device(frames, models, interp="cubic", focal=None, eng=None):
     calibrated frame then replicate its edge.  Returns (new device tensors, focal lengths).
     ``ValueError`` when a frame's size is not its model's.  Queued on the engine's stream."""
     import torch
-    from . import engine as _eng
     frames = list(frames)
     if isinstance(models, LensModel):
         models = [models] * len(frames)
@@ -243,19 +242,13 @@ def undistort_device(frames, models, interp="cubic", focal=None, eng=None):
     focals = _focals(models, focal)
     if not frames:
         return [], []
-    eng = eng or _eng.engine()
-    device = torch.device(eng.device)
+    eng = _lib._engine(eng)
     records = (_lib.LensFrame * len(frames))()
     sources, outs = [], []
     for rec, frame, model, f_new in zip(records, frames, models, focals):
-        if not isinstance(frame, torch.Tensor):
-            frame = np.ascontiguousarray(frame)
-            frame = torch.from_numpy(frame if frame.flags.writeable else frame.copy())
-        frame = frame.to(device)
+        frame = _lib.rgb_on_device(frame, eng)
         h, w = int(frame.shape[0]), int(frame.shape[1])
-        if frame.stride(2) != 1 or frame.stride(1) != 3 or frame.stride(0) < 3 * w:
-            frame = frame.contiguous()
-        out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=frame.device)
         rec.src, rec.dst = frame.data_ptr(), out.data_ptr()
         rec.src_pitch, rec.dst_pitch = frame.stride(0), out.stride(0)
         rec.fx, rec.fy, rec.cx, rec.cy, rec.f_new = model.fx, model.fy, model.cx, model.cy, f_new

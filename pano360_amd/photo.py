@@ -125,22 +125,15 @@ def _check_frame(i, frame):
         raise ValueError(f"frame {i}: {frame.dtype} {shape}, not uint8 [h][w][3]")
 
 
-def _to_device(frames, device, min_side):
+def _to_device(frames, eng, min_side):
     """Device tensors whose pixels are 3 bytes apart (rows may be further apart than 3 w)."""
-    import torch
     out = []
     for i, frame in enumerate(frames):
         _check_frame(i, frame)
         if min(frame.shape[:2]) < min_side or max(frame.shape[:2]) > _lib.PHOTO_MAX_SIDE:
             raise ValueError(f"frame {i}: {frame.shape[1]} x {frame.shape[0]} (sides {min_side} .. "
                              f"{_lib.PHOTO_MAX_SIDE})")
-        if not isinstance(frame, torch.Tensor):
-            frame = np.ascontiguousarray(frame)
-            frame = torch.from_numpy(frame if frame.flags.writeable else frame.copy())
-        frame = frame.to(device)
-        if frame.stride(2) != 1 or frame.stride(1) != 3 or frame.stride(0) < 3 * frame.shape[1]:
-            frame = frame.contiguous()
-        out.append(frame)
+        out.append(_lib.rgb_on_device(frame, eng))
     return out
 
 
@@ -153,7 +146,6 @@ def stats_device(frames, rots, intrs, lo=LO, hi=HI, step=1, params=None, tau=np.
     and y.  ``params`` (a ``PhotoModel``) and ``tau``: the sample weights are
     ``min(1, tau / max_c |residual_c|)`` under those parameters; None: every weight is 1."""
     import torch
-    from . import engine as _eng
     frames = list(frames)
     n = len(frames)
     if not (len(rots) == len(intrs) == n):
@@ -174,9 +166,8 @@ def stats_device(frames, rots, intrs, lo=LO, hi=HI, step=1, params=None, tau=np.
             raise ValueError(f"params: log-gains {log_gains.shape} for {n} frames")
         if not (np.isfinite(log_gains).all() and np.isfinite(alpha).all()):
             raise ValueError("params: a parameter is not finite")
-    eng = eng or _eng.engine()
-    device = torch.device(eng.device)
-    frames = _to_device(frames, device, 2)
+    eng = _lib._engine(eng)
+    frames = _to_device(frames, eng, 2)
     if pairs is None:
         pairs = pair_table([f.shape[:2] for f in frames], rots, intrs)
     pairs = [(int(i), int(j), np.asarray(H, np.float64).reshape(3, 3)) for i, j, H in pairs]
@@ -195,7 +186,7 @@ def stats_device(frames, rots, intrs, lo=LO, hi=HI, step=1, params=None, tau=np.
     for rec, (i, j, H) in zip(pair_recs, pairs):
         rec.H[:] = H.ravel().tolist()
         rec.i, rec.j = i, j
-    sums = torch.empty((len(pairs), SUMS), dtype=torch.float64, device=device)
+    sums = torch.empty((len(pairs), SUMS), dtype=torch.float64, device=frames[0].device)
     dptr = C.POINTER(C.c_double)
     _lib.check(eng.lib.pano_photo_stats(eng.ctx(), frame_recs, n, pair_recs, len(pairs), step, lo,
                                         hi, log_gains.ctypes.data_as(dptr),
@@ -275,13 +266,11 @@ def estimate_device(frames, rots, intrs, terms=2, rounds=ROUNDS, tau=TAU, lo=LO,
     pass is one ``stats_device`` over all pairs and one ``solve``.  ``step`` None:
     ``default_step``.  The frames are uploaded once.  Logs the gains, the falloff at the corner
     and the RMS residual at INFO."""
-    import torch
-    from . import engine as _eng
     rounds = int(rounds)
     if rounds < 0:
         raise ValueError(f"rounds {rounds}: >= 0")
-    eng = eng or _eng.engine()
-    frames = _to_device(list(frames), torch.device(eng.device), 2)
+    eng = _lib._engine(eng)
+    frames = _to_device(list(frames), eng, 2)
     shapes = [f.shape[:2] for f in frames]
     if step is None:
         step = default_step(shapes)
@@ -317,15 +306,14 @@ def apply_device(frames, model, eng=None):
     ``1024 rho``, the product rounded and clamped to 255).  ``frames``: uint8 [h][w][3] host
     arrays or device tensors of any sizes, one per camera of ``model``."""
     import torch
-    from . import engine as _eng
     frames = list(frames)
     if len(frames) != len(model.log_gains):
         raise ValueError(f"{len(frames)} frames for a model of {len(model.log_gains)} cameras")
     if not frames:
         return []
-    eng = eng or _eng.engine()
-    device = torch.device(eng.device)
-    frames = _to_device(frames, device, 1)
+    eng = _lib._engine(eng)
+    frames = _to_device(frames, eng, 1)
+    device = frames[0].device
     table = torch.from_numpy(tables(model)).to(device)
     records = (_lib.PhotoApply * len(frames))()
     outs = []
@@ -346,10 +334,8 @@ def correct_regions(regions, terms=2, eng=None):
     the corrected device tensor.  Returns the ``PhotoModel``."""
     frames = [reg.img for reg in regions]
     rots, intrs = [reg.rot for reg in regions], [reg.intr for reg in regions]
-    import torch
-    from . import engine as _eng
-    eng = eng or _eng.engine()
-    frames = _to_device(frames, torch.device(eng.device), 2)
+    eng = _lib._engine(eng)
+    frames = _to_device(frames, eng, 2)
     model = estimate_device(frames, rots, intrs, terms=terms, eng=eng)
     for reg, frame in zip(regions, apply_device(frames, model, eng)):
         reg.img = frame

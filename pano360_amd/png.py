@@ -14,17 +14,14 @@ import zlib
 
 import numpy as np
 
+from . import _lib
+
 CHUNK = 65536               # input bytes per deflate block (PANO_DEFLATE_CHUNK)
 MAX_SIDE = (1 << 31) - 1    # what a PNG's IHDR holds
 MAX_DEFLATE = (1 << 34) - 1     # pano_deflate's limit (PANO_DEFLATE_MAX_BYTES - 1)
 MAX_IDAT = (1 << 31) - 1    # a chunk's length field
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 PNG_EXTENSIONS = (".png",)
-
-
-def _engine(eng):
-    from . import engine as _eng
-    return eng or _eng.engine()
 
 
 def _on_device(x, dev):
@@ -50,19 +47,15 @@ def filter_device(img, order="bgr", eng=None):
     as long as the pixels of a row are contiguous (a crop view of a mosaic needs no copy).
     Queued on the engine's stream.  Raises ValueError for what ``encodable`` rejects."""
     import torch
-    from . import _lib
     from . import engine as _eng
     if order not in ("bgr", "rgb"):
         raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
     if not encodable(img):
         raise ValueError(f"{tuple(img.shape)} {img.dtype}: not a case the device encodes")
-    eng = _engine(eng)
-    dev = torch.device(eng.device)
-    img = _on_device(img, dev)
+    eng = _lib._engine(eng)
+    img = _lib.rgb_on_device(img, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
-    if img.stride(2) != 1 or img.stride(1) != 3 or img.stride(0) < 3 * w:
-        img = img.contiguous()
-    out = torch.empty((h, 1 + 3 * w), dtype=torch.uint8, device=dev)
+    out = torch.empty((h, 1 + 3 * w), dtype=torch.uint8, device=img.device)
     _lib.check(eng.lib.pano_png_filter(
         eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)),
         1 if order == "bgr" else 0, _eng._ptr(out)), "pano_png_filter")
@@ -76,9 +69,8 @@ def deflate_device(data, eng=None):
     the Adler-32 big-endian.  ``zlib.decompress`` returns the buffer.  The call waits on the
     stream twice and downloads the stream; not capturable."""
     import torch
-    from . import _lib
     from . import engine as _eng
-    eng = _engine(eng)
+    eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     if isinstance(data, (bytes, bytearray, memoryview)):
         data = np.frombuffer(bytes(data), np.uint8).copy()
@@ -103,9 +95,8 @@ def code_lengths_device(freq, max_bits, eng=None):
     """``pano_deflate_lengths``: the optimal code lengths of at most ``max_bits`` bits for the
     symbol frequencies ``freq`` (up to 288 of them, their sum below 2^32), as a uint8 array."""
     import torch
-    from . import _lib
     from . import engine as _eng
-    eng = _engine(eng)
+    eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     f = np.ascontiguousarray(freq, dtype=np.int64)
     if f.ndim != 1 or f.min(initial=0) < 0 or int(f.sum()) >= 1 << 32:
@@ -142,7 +133,7 @@ def encode_device(img, order="bgr", eng=None, idat_bytes=MAX_IDAT):
     """The PNG file of a uint8 [h][w][3] image (device tensor or host array, ``order`` "bgr" or
     "rgb"; a crop view needs no copy): ``Image.open`` returns exactly its pixels, the same image
     gives the same bytes on every run.  Raises ValueError for what ``encodable`` rejects."""
-    eng = _engine(eng)
+    eng = _lib._engine(eng)
     lines = filter_device(img, order, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
     return container(deflate_device(lines, eng), w, h, idat_bytes)

@@ -227,27 +227,17 @@ def _check_mosaic(img):
         raise ValueError(f"a mosaic of shape {shape}: sides 1 .. {MAX_SIDE}")
 
 
-def _engine(eng):
-    from . import engine as _eng
-    return eng or _eng.engine()
-
-
 def mip_device(mosaic, eng=None):
     """The mip chain (``Mips``) of a uint8 [H][W][3] mosaic: a device tensor (a crop view needs no
     copy as long as a row's pixels are contiguous) or a host array, which is uploaded.  Queued on
     the engine's stream."""
     import torch
     _check_mosaic(mosaic)
-    eng = _engine(eng)
-    dev = torch.device(eng.device)
-    if not isinstance(mosaic, torch.Tensor):
-        mosaic = torch.from_numpy(np.ascontiguousarray(mosaic))
-    mosaic = mosaic.to(dev)
+    eng = _lib._engine(eng)
+    mosaic = _lib.rgb_on_device(mosaic, eng)
     h, w = int(mosaic.shape[0]), int(mosaic.shape[1])
-    if mosaic.stride(2) != 1 or mosaic.stride(1) != 3 or mosaic.stride(0) < 3 * w:
-        mosaic = mosaic.contiguous()
     offs = mip_offsets(h, w)
-    buf = torch.empty(offs[-1], dtype=torch.uint8, device=dev)
+    buf = torch.empty(offs[-1], dtype=torch.uint8, device=mosaic.device)
     table = (C.c_int64 * len(offs))(*offs)
     _lib.check(eng.lib.pano_mip_u8(eng.ctx(), C.c_void_p(mosaic.data_ptr()), h, w,
                                    C.c_int64(mosaic.stride(0)), _lib._ptr(buf), table,
@@ -291,7 +281,7 @@ def render_device(mosaic_or_mips, geom, views, eng=None):
         _check_mosaic(mosaic_or_mips)
         shape = tuple(mosaic_or_mips.shape[:2])
     table, record = view_records(views, geom, tuple(shape))
-    eng = _engine(eng)
+    eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     mips = mosaic_or_mips if isinstance(mosaic_or_mips, Mips) else mip_device(mosaic_or_mips, eng)
     images = [torch.empty((v.h, v.w, 3), dtype=torch.uint8, device=dev) for v in views]

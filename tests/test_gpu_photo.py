@@ -88,7 +88,8 @@ def test_reweighted_stats_equal_the_model(eng, name, step):
 
 
 def test_a_batch_equals_single_calls(eng):
-    """A pair's sums do not depend on what else is in the batch: mixed sizes, empty pairs."""
+    """A pair's sums do not depend on what else is in the batch: mixed sizes, empty pairs, more
+    pairs than one launch takes."""
     for name, step in (("mixed", 1), ("behind", 3)):
         pairs = list(pc.pairs(name))
         lg, alpha = pc.first_params(name, step)
@@ -100,6 +101,18 @@ def test_a_batch_equals_single_calls(eng):
             # ... nor on its place in it
             back = _device_stats(eng, name, step, params, tau, pairs[::-1])
             assert np.array_equal(back[::-1].view(np.uint64), batch.view(np.uint64))
+            # ... nor on the launch that takes it: the twelve ordered pairs, 22 times over, are 264
+            # pairs, more than one launch's 256; the second launch's table and partials continue
+            # where the first one's end
+            if name == "mixed":
+                ordered = pairs + [(j, i, np.linalg.inv(H)) for i, j, H in pairs]
+                twelve = _device_stats(eng, name, step, params, tau, ordered)
+                assert len(twelve) == 12
+                assert np.array_equal(twelve[:6].view(np.uint64), batch.view(np.uint64))
+                many = _device_stats(eng, name, step, params, tau, ordered * 22)
+                assert len(many) == 264
+                for k in range(len(many)):
+                    assert np.array_equal(many[k].view(np.uint64), twelve[k % 12].view(np.uint64)), k
 
 
 def test_stats_take_pitched_device_frames_and_the_default_pairs(eng):

@@ -131,6 +131,45 @@ def test_undistort_device_checks_before_it_needs_a_device():
     assert lens.undistort_device([], model) == ([], [])
 
 
+def test_rgb_on_device_copies_only_what_a_pitch_cannot_describe():
+    """The frame helper of every stage (_lib.rgb_on_device), with the CPU standing in for the
+    engine's device."""
+    import types
+    import warnings
+
+    import torch
+    eng = types.SimpleNamespace(device=torch.device("cpu"))
+    rng = np.random.default_rng(7)
+    pixels = rng.integers(0, 256, (9, 11, 3), dtype=np.uint8)
+
+    def dense(t, w):
+        return t.stride(2) == 1 and t.stride(1) == 3 and t.stride(0) >= 3 * w
+
+    # a read-only array: copied, so that torch has nothing to warn about
+    frozen = pixels.copy()
+    frozen.setflags(write=False)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        got = _lib.rgb_on_device(frozen, eng)
+    assert dense(got, 11) and np.array_equal(got.numpy(), pixels)
+    assert not np.shares_memory(got.numpy(), frozen)
+    # a strided array is made contiguous
+    got = _lib.rgb_on_device(pixels[:, ::2], eng)
+    assert dense(got, 6) and np.array_equal(got.numpy(), pixels[:, ::2])
+    # the colour planes of an RGBA tensor: pixels 4 bytes apart, copied
+    rgba = torch.from_numpy(rng.integers(0, 256, (9, 11, 4), dtype=np.uint8))
+    view = rgba[..., :3]
+    got = _lib.rgb_on_device(view, eng)
+    assert got is not view and dense(got, 11) and torch.equal(got, view)
+    assert got.data_ptr() != view.data_ptr()
+    # a crop of a dense image: pixels 3 bytes apart, rows further: the same object
+    image = torch.from_numpy(pixels.copy())
+    crop = image[2:7, 3:9]
+    assert crop.stride(0) > 3 * crop.shape[1] and not crop.is_contiguous()
+    assert _lib.rgb_on_device(crop, eng) is crop
+    assert _lib.rgb_on_device(image, eng) is image
+
+
 # -------------------------------------------------------------------- files
 ONE = {"model": "brown", "fx": 100.0, "fy": 101.0, "cx": 66.3, "cy": 47.1,
        "k": [-0.25, 0.05, 1e-3, -5e-4, 0.0], "size": [131, 97]}
