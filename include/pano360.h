@@ -895,6 +895,50 @@ int pano_ba_normal(pano_ctx *ctx, const double *rows, const int32_t *pairs, int 
                    const int32_t *slot, int n_active, const double *jtab, const double *hom_r,
                    double lambda, void *work, double *jtj, double *jtr);
 
+/* Robust refinement of registered cameras with a shared radial distortion  (bundle_adj.refine)
+ * Not the reference's: the stage after traverse.  Per pair the Huber-weighted normal equations of
+ * the reprojection error, J the TRUE derivative of the residual.  f64, one rounding per operation,
+ * sqrt the only function called.  ONE launch, no atomics, no allocation, no wait.
+ *   rows    dev double [n_rows][4], pairs dev int32 [n_pairs][4]: as pano_ba_residuals takes them
+ *           (coordinates centred on the image; count may be 0)
+ *   cams    dev double [n_cameras][12]: f, px, py, then R row-major (world -> camera)
+ *   k1, k2  the radial coefficients, shared by all cameras; delta: the Huber threshold, pixels
+ * undist(c, x, y): d = ((x - px_c) / f_c, (y - py_c) / f_c), rd = sqrt(d0 d0 + d1 d1); r solves
+ *   h(r) = r ((1 + k1 r^2) + k2 r^4) = rd by exactly 10 Newton steps r <- r - (h(r) - rd) / h'(r)
+ *   from r = rd, h'(r) = (1 + 3 k1 r^2) + 5 k2 r^4; s = rd > 0 ? r / rd : 1; the result is
+ *   u = s d: the inverse of the forward Brown radial model of pano_lens_undistort_u8.
+ * Residual of a match: q = (u_a, 1), v = R_b (R_a^T q), pi = (v0 / v2, v1 / v2),
+ *   e = f_b (u_b - pi): pixels of camera b's corrected image.
+ * A match is INVALID when an h' met (the ten steps' and the one at the solution, of either
+ *   camera) is <= 0, when v2 <= 0, or when e or an entry of J is not finite; so is every match of
+ *   a pair that names a camera outside [0, n_cameras) or rows outside [0, n_rows), which reads
+ *   nothing.  An invalid match adds to out[p][67] and to nothing else.
+ * J, 2 x 10, by the local parameters (f_b, omega_b[3], f_a, omega_a[3], k1, k2), the
+ *   perturbations f + df and R <- exp([omega]x) R at omega = 0, through the Newton solution by the
+ *   implicit function theorem (dr/drd = 1 / h', dr/dk1 = -r^3 / h', dr/dk2 = -r^5 / h'):
+ *     du/df  = -d / (h' f)        du/dk1 = -(s r^2) d / h'        du/dk2 = r^2 du/dk1
+ *     P w    = ((w0 - pi0 w2) / v2, (w1 - pi1 w2) / v2)           (the derivative of pi, on w)
+ *     M w    = R_b (R_a^T w)
+ *     f_b:       (u_b - pi) - d_b / h'_b
+ *     omega_b,k: -f_b P (e_k x v)
+ *     f_a:       -f_b P M (du_a/df_a, 0)
+ *     omega_a,k: +f_b P M (e_k x q)
+ *     k1, k2:    f_b (du_b/dk - P M (du_a/dk, 0))
+ * With n = |e|: w = n <= delta ? 1 : delta / n, rho = n <= delta ? n^2 / 2 : delta (n - delta / 2).
+ * out: dev double [n_pairs][70], every entry written, per pair over its valid matches:
+ *     [0..54]  sum of (w J_c)^T J_e, c <= e: the upper triangle of sum w J^T J, row-major
+ *     [55..64] sum of (w J)^T e      [65] sum rho      [66] sum w      [67] invalid matches
+ *     [68] sum n^2 over the matches with n <= delta    [69] the number of those
+ * Summation: one block of 256 per pair; thread t adds the pair's matches t, t + 256, ... in
+ *   order to its own 70 sums, from 0; then per sum the 64 lanes of a wave by the xor butterfly
+ *   (offsets 32, 16, .. 1) and the four waves as (w0 + w1) + (w2 + w3).  The same input gives the
+ *   same bytes on every call.
+ * PANO_EINVAL, with nothing launched and out untouched: a null pointer, n_pairs < 1,
+ *   n_cameras < 1, n_rows < 0, a delta that is not finite or not positive. */
+int pano_ba_refine(pano_ctx *ctx, const double *rows, int64_t n_rows, const int32_t *pairs,
+                   int n_pairs, const double *cams, int n_cameras, double k1, double k2,
+                   double delta, double *out);
+
 /* Baseline JPEG decode of a batch                               stitcher.py:415-421 (cv2.imread)
  * Frames equal to libjpeg-turbo's default decompression as Pillow runs it, bit for bit, after
  * ImageOps.exif_transpose and convert("RGB"), written as uint8 BGR [h][w][3].  Scope: SOF0 /

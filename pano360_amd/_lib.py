@@ -86,6 +86,8 @@ SEAM_RESIDENT_CELLS = 81408
 # pano_ssc_probe's paths, the on-chip bitmap's capacity in cells
 SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
 SSC_ONCHIP_CELLS = 524288
+# pano_ba_refine: the sums per pair
+BA_REFINE_TERMS = 70
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
 # pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
 VIEW_MAX_LEVELS = 16
@@ -252,6 +254,8 @@ _SIGNATURES = {
     "pano_ba_work_bytes": (C.c_size_t, [_i]),
     "pano_ba_residuals": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "pano_ba_normal": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _vp]),
+    "pano_ba_refine": (_i, [_vp, _vp, C.c_int64, _vp, _i, _vp, _i, C.c_double, C.c_double,
+                            C.c_double, _vp]),
     "pano_jpeg_decode": (_i, [_vp, _vp, _i, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64]),
     "pano_jpeg_encode_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_jpeg_encode": (_i, [_vp, _vp, _i, _i, C.c_int64, _i, _i, _vp, _vp, C.c_int64,

@@ -8,6 +8,8 @@ pairs (``traverse``), Levenberg-Marquardt with a constant damping (``Incremental
 and straightening.  The per-match work of every LM iteration (residuals, the Jacobian of
 ``_jacobian_symbolic``, J^T J and J^T r) runs in ``csrc/bundle.hip`` in f64; the per-camera
 3 x 3 algebra, the solve and the control flow stay here (include/pano360.h, pano_ba_normal).
+``refine`` is not the reference's: a robust refinement of the cameras ``traverse`` made, with the
+true derivative and optionally a shared radial distortion (``csrc/refine.hip``, pano_ba_refine).
 
 The class is importable as ``bundle_adj.Image`` through the top-level
 ``bundle_adj.py`` re-export, so ``ba_<name>.pkl`` caches written by the
@@ -555,3 +557,266 @@ def traverse(imgs, matches, badjust="incr", use_straighten=True):
         for cam, rot in zip(cameras, straighten([c.rot for c in cameras])):
             cam.rot = rot
     return cameras
+
+
+# ------------------------------------------------------------------ robust refinement
+REFINE_TERMS = 70           # pano_ba_refine's sums per pair (include/pano360.h)
+REFINE_LOCAL = 10           # a pair's local parameters: f_b, omega_b, f_a, omega_a, k1, k2
+REFINE_LAMBDA = 1e-3        # the first damping; / 10 after a step that is taken, * 10 otherwise
+REFINE_LAMBDA_MAX = 1e12
+REFINE_MIN_DECREASE = 1e-10
+
+
+@dataclass
+class Refinement:
+    """What ``refine`` returns.  ``cameras``: new ``Image`` records (``img`` carried over);
+    ``k``: (k1, k2); ``history``: one (cost, lambda, accepted) per iteration, cost the candidate's
+    sum of Huber losses; ``rms_before`` / ``rms_after``: the root of the mean squared distance
+    (pixels, per match) over the matches within the Huber threshold, at the cameras given and at
+    the cameras returned; ``inlier_share``: those matches' share of all matches, and
+    ``n_invalid`` the matches without a residual, both at the cameras returned."""
+    cameras: list
+    k: tuple
+    history: list
+    rms_before: float
+    rms_after: float
+    inlier_share: float
+    n_invalid: int
+
+    def lens_models(self, sizes):
+        """One ``lens.LensModel`` per camera for ``lens.undistort_device``: the forward Brown
+        model of the fitted (k1, k2) at the camera's focal length and principal point.
+        ``sizes``: one (w, h), or one per camera."""
+        from . import lens as _lens
+        if len(sizes) == 2 and np.ndim(sizes[0]) == 0:
+            sizes = [sizes] * len(self.cameras)
+        if len(sizes) != len(self.cameras):
+            raise ValueError(f"{len(sizes)} sizes for {len(self.cameras)} cameras")
+        return [_lens.LensModel("brown", fx=cam.intr[0, 0], fy=cam.intr[0, 0],
+                                cx=w / 2 + cam.intr[0, 2], cy=h / 2 + cam.intr[1, 2],
+                                k=self.k, size=(w, h))
+                for cam, (w, h) in zip(self.cameras, sizes)]
+
+
+def _refine_pairs(matches, index):
+    """[(a, b, rows [M][4])]: every unordered pair of ``matches`` between two images of ``index``
+    once, in ascending (i, j), i < j: camera b is i's position, camera a is j's."""
+    slot = {int(img): k for k, img in enumerate(index)}
+    out = []
+    keys = sorted({(min(i, j), max(i, j)) for i in matches for j in matches[i] if i != j})
+    for i, j in keys:
+        if i not in slot or j not in slot:
+            continue
+        if i in matches and j in matches[i]:
+            rows = _rows_of(matches[i][j][0])
+        else:
+            rows = _rows_of(matches[j][i][0])[:, [2, 3, 0, 1]]
+        out.append((slot[j], slot[i], rows))
+    return out
+
+
+def _refine_map(n, pairs, lens_terms, shared_focal):
+    """[4 n + 2] -> the reduced system's index of every full parameter (camera c: f, omega at
+    4 c .. 4 c + 3; k1, k2 last), -1 where it is not estimated: the rotation of the first camera
+    that has a match (the gauge), the cameras without a pair, the k beyond ``lens_terms``; with
+    ``shared_focal`` every f is the one parameter 0."""
+    used = np.zeros(n, bool)
+    for a, b, rows in pairs:
+        if len(rows):
+            used[a] = used[b] = True
+    red = np.full(4 * n + 2, -1, np.int64)
+    nxt = 1 if shared_focal else 0
+    gauge = int(np.argmax(used))
+    for c in range(n):
+        if not used[c]:
+            continue
+        if shared_focal:
+            red[4 * c] = 0
+        else:
+            red[4 * c], nxt = nxt, nxt + 1
+        if c != gauge:
+            red[4 * c + 1:4 * c + 4] = np.arange(nxt, nxt + 3)
+            nxt += 3
+    for t in range(lens_terms):
+        red[4 * n + t], nxt = nxt, nxt + 1
+    return red, nxt
+
+
+class _Refiner:
+    """The matches of one ``refine`` on the device and its evaluations: one pano_ba_refine and
+    one wait each."""
+
+    def __init__(self, pairs, n, huber):
+        from . import _lib
+        self._lib = _lib
+        self.dev = _Device(n)
+        self.n, self.huber = n, float(huber)
+        firsts = [self.dev.append(rows) for _, _, rows in pairs]
+        table = np.array([(a, b, first, len(rows)) for (a, b, rows), first in zip(pairs, firsts)],
+                         np.int64).reshape(-1, 4)
+        self.n_pairs = len(table)
+        self.pairs = self.dev.upload(table, np.int32)
+        self.out = self.dev.torch.empty((self.n_pairs, REFINE_TERMS),
+                                        dtype=self.dev.torch.float64, device=self.dev.dev)
+
+    def sums(self, f, pp, R, k):
+        """out [n_pairs][70] at one state."""
+        from . import engine as _eng
+        dev = self.dev
+        cams = dev.upload(np.concatenate([f[:, None], pp, R.reshape(self.n, 9)], axis=1),
+                          np.float64)
+        self._lib.check(dev.eng.lib.pano_ba_refine(
+            dev.eng.ctx(), _eng._ptr(dev.rows), dev.n_rows, _eng._ptr(self.pairs), self.n_pairs,
+            _eng._ptr(cams), self.n, C.c_double(k[0]), C.c_double(k[1]), C.c_double(self.huber),
+            _eng._ptr(self.out)), "pano_ba_refine")
+        return dev.download(self.out)[0].copy()
+
+
+def _centre(focal, pp):
+    """The least rotation C that takes the ray of the principal point ``pp`` of a camera that
+    looks along z, (-px / f, -py / f, 1), to z: C R with the principal point at the centre looks
+    where R with ``pp`` looked."""
+    ray = np.array([-pp[0] / focal, -pp[1] / focal, 1.0])
+    ray /= np.linalg.norm(ray)
+    axis = np.cross(ray, [0.0, 0.0, 1.0])
+    sin = np.linalg.norm(axis)
+    return rotation_to_mat(axis / sin * np.arctan2(sin, ray[2])) if sin > 0 else np.eye(3)
+
+
+def _refine_where(pairs, n):
+    """[n_pairs][10]: where a pair's local parameters (f_b, omega_b, f_a, omega_a, k1, k2) are
+    among the 4 n + 2."""
+    a = np.array([p[0] for p in pairs], np.int64)
+    b = np.array([p[1] for p in pairs], np.int64)
+    return np.concatenate([4 * b[:, None] + np.arange(4), 4 * a[:, None] + np.arange(4),
+                           np.tile([4 * n, 4 * n + 1], (len(pairs), 1))], axis=1)
+
+
+def _refine_system(out, where, red, size):
+    """(A, g) of the reduced system from the per-pair blocks, the pairs added in order."""
+    uu, vv = np.triu_indices(REFINE_LOCAL)
+    A, g = np.zeros((size, size)), np.zeros(size)
+    ru, rv = red[where[:, uu]], red[where[:, vv]]
+    val = out[:, :55]
+    keep = (ru >= 0) & (rv >= 0)
+    np.add.at(A, (ru[keep], rv[keep]), val[keep])
+    keep &= (uu != vv)[None, :]
+    np.add.at(A, (rv[keep], ru[keep]), val[keep])
+    rg = red[where]
+    keep = rg >= 0
+    np.add.at(g, rg[keep], out[:, 55:65][keep])
+    return A, g
+
+
+def _refine_totals(out):
+    """(cost, invalid, sum n^2 of the inliers, inliers) of one evaluation, the pairs in order."""
+    cost = ssq = 0.0
+    for row in out:
+        cost, ssq = cost + row[65], ssq + row[68]
+    return cost, int(round(np.sum(out[:, 67]))), ssq, int(round(np.sum(out[:, 69])))
+
+
+def refine(cameras, matches, index=None, *, lens_terms=0, shared_focal=None, huber=3.0,
+           max_iter=100):
+    """A robust refinement of registered cameras, optionally with a radial distortion shared by
+    all of them: the stage after ``traverse``, which stays the reference's step for step.
+
+    ``cameras``: ``Image`` records as ``traverse`` returns them; ``matches``: the dict
+    ``traverse`` takes; ``index[k]``: the image number of ``cameras[k]`` (None: camera k is image
+    k; ``ValueError`` when the lengths make that impossible).  Every unordered pair of
+    ``matches`` between two images present is used once, the pairs ``traverse``'s gate dropped
+    included: the Huber loss deals with them.  ``huber`` is its threshold in pixels; 3.0 is the
+    project's RANSAC threshold (``features.find_homographies_device``, ``thresh=3.0``): what the
+    matcher calls an inlier is what the refinement weighs in full.  ``lens_terms``: 0, 1 (k1) or
+    2 (k1 and k2) of ``r (1 + k1 r^2 + k2 r^4) = r_d`` in units of the focal length;
+    ``shared_focal`` (default: ``lens_terms > 0``, since k is expressed in units of f and a focal
+    length per camera leaves it weakly determined) gives all cameras one focal length.
+
+    The distortion is centred on the principal point and everything behind the registration
+    takes that for the image centre, while ``traverse`` moves it freely (by hundreds of pixels on
+    noisy rings): each camera's principal point is therefore first folded into its rotation
+    (``_centre``) and the cameras returned have it at the centre; with ``shared_focal`` the focal
+    lengths start at their median.  Then Levenberg-Marquardt in float64 on the host over f (one
+    per camera, or the one shared), the rotations (that of the first camera with a match is the
+    gauge and stays: ``traverse``'s straightening survives) and k.  The per-match work (the
+    residual under the distortion, its true derivative, the Huber weights, the per-pair sums) is
+    pano_ba_refine (include/pano360.h): one call and one wait per iteration, since the call that scores a
+    candidate holds the system of the next step.  ``(A + lambda diag A) step = -g`` from lambda
+    = 1e-3; a candidate is taken when the sum of losses falls (and no further match lost its
+    residual), lambda / 10, else lambda * 10; the loop ends after a taken step's relative
+    decrease below 1e-10, with lambda above 1e12, or after ``max_iter`` iterations.
+    Returns a ``Refinement``; the input records are not modified."""
+    cameras = list(cameras)
+    n = len(cameras)
+    if lens_terms not in (0, 1, 2):
+        raise ValueError(f"lens_terms={lens_terms!r}: 0, 1 or 2")
+    if not (np.isfinite(huber) and huber > 0):
+        raise ValueError(f"huber={huber!r}: a positive number of pixels")
+    if index is None:
+        images = {int(i) for i in matches} | {int(j) for i in matches for j in matches[i]}
+        if n == 0 or (images and max(images) >= n):
+            raise ValueError(f"{n} cameras for matches between images up to "
+                             f"{max(images) if images else 0}: pass index")
+        index = range(n)
+    index = [int(i) for i in index]
+    if len(index) != n or len(set(index)) != n:
+        raise ValueError(f"index: {len(index)} image numbers ({len(set(index))} distinct) for "
+                         f"{n} cameras")
+    if shared_focal is None:
+        shared_focal = lens_terms > 0
+    pairs = _refine_pairs(matches, index)
+    if not any(len(rows) for _, _, rows in pairs):
+        raise ValueError("refine: no matches between the cameras")
+
+    f = np.array([c.intr[0, 0] for c in cameras], np.float64)
+    pp = np.array([[c.intr[0, 2], c.intr[1, 2]] for c in cameras], np.float64)
+    R = np.stack([np.asarray(c.rot, np.float64) for c in cameras])
+    R, pp = np.stack([_centre(f[c], pp[c]).dot(R[c]) for c in range(n)]), np.zeros((n, 2))
+    if shared_focal:
+        f = np.full(n, np.median(f))
+    k = np.zeros(2)
+    red, size = _refine_map(n, pairs, lens_terms, bool(shared_focal))
+    dev = _Refiner(pairs, n, huber)
+    where = _refine_where(pairs, n)
+    n_matches = sum(len(rows) for _, _, rows in pairs)
+
+    cur = dev.sums(f, pp, R, k)
+    cost, invalid, ssq, inl = _refine_totals(cur)
+    rms_before = float(np.sqrt(ssq / inl)) if inl else float("nan")
+    history, lam = [], REFINE_LAMBDA
+    for _ in range(max_iter):
+        if lam > REFINE_LAMBDA_MAX:
+            break
+        A, g = _refine_system(cur, where, red, size)
+        try:
+            step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+        except np.linalg.LinAlgError:
+            step = None
+        if step is None or not np.all(np.isfinite(step)):
+            history.append((float("nan"), lam, False))
+            lam *= 10
+            continue
+        full = np.where(red >= 0, step[np.maximum(red, 0)], 0.0)
+        f_c = f + full[0:4 * n:4]
+        R_c = np.stack([rotation_to_mat(full[4 * c + 1:4 * c + 4]).dot(R[c]) for c in range(n)])
+        k_c = k + full[4 * n:]
+        cand = dev.sums(f_c, pp, R_c, k_c)
+        c_cost, c_invalid, c_ssq, c_inl = _refine_totals(cand)
+        keep = bool(c_cost < cost and c_invalid <= invalid)
+        history.append((float(c_cost), lam, keep))
+        if keep:
+            decrease = (cost - c_cost) / cost
+            f, R, k, cur = f_c, R_c, k_c, cand
+            cost, invalid, ssq, inl = c_cost, c_invalid, c_ssq, c_inl
+            lam /= 10
+            if decrease < REFINE_MIN_DECREASE:
+                break
+        else:
+            lam *= 10
+    # (a Deferred image is handed on as it is, not downloaded)
+    out = [Image(c.__dict__.get("_img"), R[i].copy(),
+                 intrinsics(float(f[i]), (float(pp[i, 0]), float(pp[i, 1]))), c.range)
+           for i, c in enumerate(cameras)]
+    return Refinement(out, (float(k[0]), float(k[1])), history, rms_before,
+                      float(np.sqrt(ssq / inl)) if inl else float("nan"),
+                      inl / n_matches, invalid)

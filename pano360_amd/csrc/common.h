@@ -91,6 +91,7 @@ enum PanoKernelId {
     PK_DEFLATE_EMIT,
     PK_DEFLATE_LENGTHS,
     PK_PHOTO_STATS,
+    PK_BA_REFINE,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------

@@ -15,7 +15,8 @@ distortion's radial profile as monotone over the frame (a calibration whose poly
 inside the frame is not a usable one), and it keeps the frame's size, so a wide fisheye loses
 field of view: what a rectilinear image of that size cannot show is cropped.  Keeping that field
 needs a fisheye term in the warp itself, which is a different, later piece of work.
-Vignetting, chromatic aberration and estimating the coefficients are out of scope.
+Vignetting and chromatic aberration are out of scope; ``bundle_adj.refine`` estimates k1 and k2
+from the matches and hands them over as ``LensModel`` records (``Refinement.lens_models``).
 """
 import ctypes as C
 import json

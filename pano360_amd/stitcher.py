@@ -405,6 +405,58 @@ def _register(path, name, frames, badjust, detector="sift"):
     return regions
 
 
+def _image_index(regions, frames):
+    """The image number of every camera ``traverse`` returned: it attaches ``frames[i]`` itself
+    to camera i and leaves out the images it did not reach."""
+    return [next(i for i, frame in enumerate(frames) if frame is reg.img) for reg in regions]
+
+
+REFINE_MIN_SHARE = 0.5      # of the matches within the threshold, for a refinement to be used
+
+
+def _refine(regions, name, index, lens_terms):
+    """``--refine`` / ``--refine-lens``: ``bundle_adj.refine`` of the cameras in hand over the
+    matches of ``matches_<name>.npz`` and, with ``lens_terms``, the correction of their frames by
+    the fitted distortion (``lens.undistort_device``: cubic, the fitted focal length, which
+    becomes the camera's).  Returns the new regions - or, when fewer than REFINE_MIN_SHARE of the
+    matches end within the threshold, the regions given, with a warning."""
+    try:
+        arr = np.load(f"matches_{name}.npz", allow_pickle=True)
+    except IOError:
+        raise SystemExit(f"--refine needs the matches of matches_{name}.npz, which is missing: "
+                         "run with --register (and without a camera cache) to write it") from None
+    kpts, matches = arr["kpts"], arr["matches"]
+    if index is None:
+        if len(regions) != len(kpts):
+            raise SystemExit(f"ba_{name}.pkl holds {len(regions)} cameras for the {len(kpts)} "
+                             f"images of matches_{name}.npz and does not say which: remove it "
+                             "and run --register and --refine in one call")
+        index = range(len(regions))
+    start = time.time()
+    res = _ba.refine(regions, idx_to_keypoints(matches, kpts), list(index),
+                     lens_terms=lens_terms or 0)
+    focals = ", ".join(f"{reg.intr[0, 0]:.3f}" for reg in res.cameras)
+    logging.info(f"Refinement, time: {time.time() - start}: rms {res.rms_before:.4f} -> "
+                 f"{res.rms_after:.4f} px over the matches within the threshold, inlier share "
+                 f"{res.inlier_share:.4f}, k = ({res.k[0]:.6g}, {res.k[1]:.6g}), focal lengths "
+                 f"{focals}")
+    if res.inlier_share < REFINE_MIN_SHARE:
+        # the loop is local: from cameras too far off it can end anywhere, and a distortion
+        # fitted there would bend every frame
+        logging.warning(f"Refinement discarded: only {res.inlier_share:.2f} of the matches end "
+                        "within the threshold, so the cameras it started from were too far off; "
+                        "the cameras and the frames stay as they were")
+        return regions
+    regions = res.cameras
+    if lens_terms:
+        frames = [reg.img for reg in regions]
+        models = res.lens_models([(f.shape[1], f.shape[0]) for f in frames])
+        frames, focals = _lens.undistort_device(frames, models, "cubic")
+        for reg, frame, focal in zip(regions, frames, focals):
+            reg.img, reg.intr = frame, _ba.intrinsics(focal)
+    return regions
+
+
 def _view_spec(text):
     """``YAW,PITCH,FOV[,WxH]`` of --view, degrees: (yaw, pitch, fov, (w, h))."""
     parts = text.split(",")
@@ -432,6 +484,13 @@ def _tolerance(text):
     if not value >= 0:
         raise argparse.ArgumentTypeError(f"{text}: >= 0")
     return value
+
+
+def refine_of(args):
+    """(whether to refine, the radial terms to fit or None): what ``--refine`` and
+    ``--refine-lens`` asked for."""
+    terms = getattr(args, "refine_lens", None)
+    return bool(getattr(args, "refine", False)) or terms is not None, terms
 
 
 def parse_args(argv=None):
@@ -479,9 +538,23 @@ def parse_args(argv=None):
                         help="fill what no frame covers from the pixels around it: the saved "
                              "mosaic and --deepzoom show no ragged border, and --view, --equirect, "
                              "--cube and --multires no black outside the mosaic (not with --crop).")
+    # (absent flags leave no attribute: the parsed namespace without them is what it was)
+    parser.add_argument("--refine", action="store_true", default=argparse.SUPPRESS,
+                        help="refine the cameras robustly after the registration or the camera "
+                             "cache (bundle_adj.refine over matches_<name>.npz); recomputed on "
+                             "every run, no cache changes.")
+    parser.add_argument("--refine-lens", type=int, choices=[1, 2], default=argparse.SUPPRESS,
+                        metavar="{1,2}",
+                        help="--refine that also fits 1 (k1) or 2 (k1, k2) radial distortion "
+                             "terms shared by all images, and corrects the images by them before "
+                             "the stitch (not with --lens).")
     _lens.add_arguments(parser)
     _photo.add_arguments(parser)
     args = parser.parse_args(argv)
+    if refine_of(args)[1] is not None:
+        if args.lens is not None:
+            parser.error("--refine-lens and --lens both set the lens: give one of them")
+        args.refine = True
     _lens.check_arguments(parser, args)
     _photo.check_arguments(parser, args)
     if args.ghost_tol is not None and args.blend != "median":
@@ -538,9 +611,11 @@ def main(argv=None):
             f"{cache} not found: run with --register to match the images and adjust the "
             "cameras here (the reference CLI's registration), or produce the camera cache with "
             "the reference (the pickle written at stitcher.py:438-439) and re-run")
+    index = None                    # of a cache: camera k is image k, if their numbers agree
     if regions is None:
-        regions = _register(args.path, name, ingest(args.path, args.shrink, lens=lens), args.ba,
-                            args.detector)
+        frames = ingest(args.path, args.shrink, lens=lens)
+        regions = _register(args.path, name, frames, args.ba, args.detector)
+        index = _image_index(regions, frames)
     if any(reg.img is None for reg in regions):
         frames = ingest(args.path, args.shrink, lens=lens) if os.path.isdir(args.path) else []
         if len(frames) != len(regions):
@@ -549,6 +624,9 @@ def main(argv=None):
         for reg, frame in zip(regions, frames):
             if reg.img is None:
                 reg.img = frame
+    if refine_of(args)[0]:
+        # refine -> undistort -> --photometric -> stitch
+        regions = _refine(regions, name, index, refine_of(args)[1])
     if _photo.mode_of(args) is not None:
         # after the registration, which sees the frames as they are (no cache name changes),
         # and before the stitch: every blender, --crop, --fill, the views and the tiles get
