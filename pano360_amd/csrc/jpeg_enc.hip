@@ -1,8 +1,9 @@
 // Baseline JPEG encode of one image (pano_jpeg_encode) or of a batch of images of any sizes
 // (pano_jpeg_encode_batch): colour conversion, downsampling, the ISLOW FDCT and quantisation per
 // block, per-block Huffman bit counts, an int64 scan of them, the bit emission and the byte
-// stuffing.  The batch runs the same stages over all images' blocks at once; what differs is at
-// "the batch" below.  The contract (what is bit-exact with what, the scratch layout, the waits) is
+// stuffing.  The batch runs the same stages over all images' blocks at once: every stage is one
+// kernel template and one driver (enc_run) runs both calls; what differs is in the two policies
+// at "which image" below.  The contract (what is bit-exact with what, the scratch layout, the waits) is
 // in include/pano360.h; the host side (quantisation tables, the header) is
 // pano360_amd/jpeg.py and a NumPy restatement of every stage is tests/jpeg_encode_model.py.
 //
@@ -224,13 +225,25 @@ __device__ __forceinline__ void enc_block(const EncGeom &E, const uint8_t (*q)[6
     __syncthreads();
 }
 
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_blocks_kernel(EncImage E,
+// Every stage's kernel is a template over W, "which image", a kernel argument passed by value:
+// EncOne for pano_jpeg_encode, EncBatch for pano_jpeg_encode_batch (both at "which image" below).
+// S holds what all images share (sampling, channel order, quantisers; nblocks: the blocks of all
+// images, numbered one after the other) and where.at(S, g, live) is the image of block g.
+struct EncAt {
+    EncGeom E;
+    int i, first, end;              // the image, its first block, one past its last
+};
+
+template <class W>
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_blocks_kernel(EncImage S, W where,
                                                                     int16_t *__restrict__ coef) {
     __shared__ int tile[ENC_TILE][8][9];
-    for (int64_t base = (int64_t)blockIdx.x * ENC_TILE; base < E.nblocks;
+    for (int64_t base = (int64_t)blockIdx.x * ENC_TILE; base < S.nblocks;
          base += (int64_t)gridDim.x * ENC_TILE) {
-        const int b = (int)base + (threadIdx.x >> 3);
-        enc_block(E, E.q, b, b < E.nblocks, tile, coef + 64 * (int64_t)b);
+        const int g = (int)base + (threadIdx.x >> 3);
+        const bool live = g < S.nblocks;
+        const EncAt a = where.at(S, g, live);
+        enc_block(a.E, S.q, g - a.first, live, tile, coef + 64 * (int64_t)g);
     }
 }
 
@@ -291,14 +304,17 @@ __device__ __forceinline__ EncCode enc_lane_code(const EncGeom &E, const int16_t
 }
 
 // ---- 2. bit counts: one wave per block ------------------------------------------------------------
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_count_kernel(EncImage E,
+template <class W>
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_count_kernel(EncImage S, W where,
                                                                    const int16_t *__restrict__ coef,
                                                                    uint32_t *__restrict__ counts) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t b = (int64_t)blockIdx.x * ENC_WAVES + wave; b < E.nblocks;
-         b += (int64_t)gridDim.x * ENC_WAVES) {
-        const int n = wave_sum(enc_lane_code(E, coef, (int)b, lane).n);
-        if (lane == 0) counts[b] = (uint32_t)n;
+    for (int64_t g = (int64_t)blockIdx.x * ENC_WAVES + wave; g < S.nblocks;
+         g += (int64_t)gridDim.x * ENC_WAVES) {
+        const EncAt a = where.at(S, (int)g, true);
+        const int bits = wave_sum(
+            enc_lane_code(a.E, coef + 64 * (int64_t)a.first, (int)g - a.first, lane).n);
+        if (lane == 0) counts[g] = (uint32_t)bits;
     }
 }
 
@@ -379,17 +395,21 @@ __device__ __forceinline__ void enc_emit_block(const EncGeom &E, const int16_t *
     __syncthreads();
 }
 
+// where.bit0(a, off, part, g): the bit of raw at which block g, of image a, starts
+template <class W>
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_emit_kernel(
-    EncImage E, const int16_t *__restrict__ coef, const uint32_t *__restrict__ counts,
+    EncImage S, W where, const int16_t *__restrict__ coef, const uint32_t *__restrict__ counts,
     const int64_t *__restrict__ off, const int64_t *__restrict__ part, uint32_t *__restrict__ raw) {
     __shared__ uint32_t words[ENC_WAVES][ENC_WORDS];
     const int wave = threadIdx.x >> 6;
-    for (int64_t base = (int64_t)blockIdx.x * ENC_WAVES; base < E.nblocks;
+    for (int64_t base = (int64_t)blockIdx.x * ENC_WAVES; base < S.nblocks;
          base += (int64_t)gridDim.x * ENC_WAVES) {
-        const int64_t b = base + wave;
-        const bool live = b < E.nblocks;
-        enc_emit_block(E, coef, (int)b, live, live ? enc_offset(off, part, b) : 0,
-                       live ? (int)counts[b] : 0, b == E.nblocks - 1, words[wave], raw);
+        const int64_t g = base + wave;
+        const bool live = g < S.nblocks;
+        const EncAt a = where.at(S, (int)g, live);
+        enc_emit_block(a.E, coef + 64 * (int64_t)a.first, (int)g - a.first, live,
+                       live ? where.bit0(a, off, part, g) : 0, live ? (int)counts[g] : 0,
+                       g == a.end - 1, words[wave], raw);
     }
 }
 
@@ -409,11 +429,13 @@ __device__ __forceinline__ uint32_t enc_chunk_ffs(const uint32_t *__restrict__ r
     return n;
 }
 
+// where.counted(c): what chunk c's count holds besides its 0xFF bytes
+template <class W>
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_count_kernel(
-    const uint32_t *__restrict__ raw, int64_t nchunks, uint32_t *__restrict__ counts) {
+    W where, const uint32_t *__restrict__ raw, int64_t nchunks, uint32_t *__restrict__ counts) {
     const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
     if (c >= nchunks) return;
-    counts[c] = enc_chunk_ffs(raw, c);
+    counts[c] = where.counted(c) + enc_chunk_ffs(raw, c);
 }
 
 // bytes [a, e) of raw to out[o ...], a 0x00 after every 0xFF; returns where the next byte goes
@@ -427,16 +449,131 @@ __device__ __forceinline__ int64_t enc_stuff_bytes(const uint8_t *__restrict__ r
     return o;
 }
 
+// where.stuff(raw, c, nbytes, nchunks, o, out): chunk c's bytes to their place in out; o is the
+// scan of the counts before c, nbytes the end of raw
+template <class W>
 __global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_stuff_write_kernel(
-    const uint8_t *__restrict__ raw, int64_t nbytes, int64_t nchunks, const int64_t *__restrict__ off,
-    const int64_t *__restrict__ part, uint8_t *__restrict__ out) {
+    W where, const uint8_t *__restrict__ raw, int64_t nbytes, int64_t nchunks,
+    const int64_t *__restrict__ off, const int64_t *__restrict__ part, uint8_t *__restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
     if (c >= nchunks) return;
-    const int64_t a = c * ENC_CHUNK, e = a + ENC_CHUNK < nbytes ? a + ENC_CHUNK : nbytes;
-    enc_stuff_bytes(raw, a, e, out, a + enc_offset(off, part, c));
+    where.stuff(raw, c, nbytes, nchunks, enc_offset(off, part, c), out);
 }
 
-// ---- the entry points ------------------------------------------------------------------------------
+// ---- which image: one (pano_jpeg_encode) ---------------------------------------------------------
+// The image is S itself.  Its bits start at bit 0 of raw, a chunk's count is its 0xFF bytes, so a
+// chunk's bytes move up by the scan of the counts, and the stuffed stream is all of out.
+struct EncOne {
+    static constexpr bool kBatch = false;
+    static constexpr int n = 1;
+    static constexpr int64_t head = 0;
+    __device__ EncAt at(const EncImage &S, int, bool) const { return {S, 0, 0, S.nblocks}; }
+    __device__ int64_t bit0(const EncAt &, const int64_t *off, const int64_t *part, int64_t g) const {
+        return enc_offset(off, part, g);
+    }
+    __device__ uint32_t counted(int64_t) const { return 0; }
+    static int64_t stuffed(int64_t nbytes, int64_t sum) { return nbytes + sum; }
+    __device__ void stuff(const uint8_t *__restrict__ raw, int64_t c, int64_t nbytes, int64_t,
+                          int64_t o, uint8_t *__restrict__ out) const {
+        const int64_t a = c * ENC_CHUNK, e = a + ENC_CHUNK < nbytes ? a + ENC_CHUNK : nbytes;
+        enc_stuff_bytes(raw, a, e, out, a + o);
+    }
+};
+
+// ---- which image: a batch (pano_jpeg_encode_batch) -----------------------------------------------
+// The blocks of all images are numbered one after the other, image by image; first[i] is image
+// i's first block (first[n]: the total) and a block finds its image by bisecting that table, so
+// the stages run on (image, block in the image) and their workgroups straddle images freely.  (A
+// faster search, wave-wide or one per workgroup, goes into at() and nowhere else.)  The counts of
+// all blocks are scanned together; an image's bits are the difference of the offsets at its two
+// ends.  Every image's raw bits start on a whole stuffing chunk (chunk0[i], from a scan of the
+// images' chunk counts), so no word, pad byte or 0xFF of one image touches another's, and the
+// stuffed streams are packed byte after byte: a chunk's count is its stream bytes plus its 0xFF
+// bytes, and the scan of those is the output position.  out: int64 offsets[n + 1] of the images'
+// streams, then (at out + head) the streams.
+struct EncDesc {
+    const uint8_t *img;
+    int64_t pitch;
+    int w, h, mx, my;
+    int wib[2], hib[2];
+};
+
+// the largest i in [0, n) with t[i] <= v (t ascending, t[0] <= v)
+template <class T>
+__device__ __forceinline__ int enc_find(const T *__restrict__ t, int n, T v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+struct EncBatch {
+    static constexpr bool kBatch = true;
+    const EncDesc *__restrict__ desc;
+    const int *__restrict__ first;
+    int n;
+    int64_t *__restrict__ chunk0, *__restrict__ ibytes;     // per image: first chunk, stream bytes
+    int64_t head;                                           // bytes of the offsets in front of the streams
+
+    __device__ EncAt at(const EncImage &S, int g, bool live) const {
+        const int i = live ? enc_find(first, n, g) : 0;
+        const EncDesc d = desc[i];
+        EncAt a{S, i, first[i], first[i + 1]};
+        a.E.img = d.img;
+        a.E.pitch = d.pitch;
+        a.E.w = d.w;
+        a.E.h = d.h;
+        a.E.mx = d.mx;
+        a.E.my = d.my;
+        a.E.wib[0] = d.wib[0];
+        a.E.wib[1] = d.wib[1];
+        a.E.hib[0] = d.hib[0];
+        a.E.hib[1] = d.hib[1];
+        a.E.nblocks = a.end - a.first;
+        return a;
+    }
+    __device__ int64_t bit0(const EncAt &a, const int64_t *off, const int64_t *part, int64_t g) const {
+        return chunk0[a.i] * (8 * ENC_CHUNK) + enc_offset(off, part, g) - enc_offset(off, part, a.first);
+    }
+    // the stream bytes of chunk c, which is image i's
+    __device__ int chunk_bytes(int i, int64_t c) const {
+        const int64_t left = ibytes[i] - (c - chunk0[i]) * ENC_CHUNK;
+        return (int)(left < ENC_CHUNK ? left : ENC_CHUNK);
+    }
+    __device__ uint32_t counted(int64_t c) const {
+        return (uint32_t)chunk_bytes(enc_find(chunk0, n, c), c);
+    }
+    static int64_t stuffed(int64_t, int64_t sum) { return sum; }
+    __device__ void stuff(const uint8_t *__restrict__ raw, int64_t c, int64_t, int64_t nchunks,
+                          int64_t o, uint8_t *__restrict__ out) const {
+        const int i = enc_find(chunk0, n, c);
+        const int64_t a = c * ENC_CHUNK;
+        const int64_t end = enc_stuff_bytes(raw, a, a + chunk_bytes(i, c), out + head, o);
+        int64_t *offsets = (int64_t *)out;
+        if (c == chunk0[i]) offsets[i] = o;
+        if (c == nchunks - 1) offsets[n] = end;
+    }
+};
+
+// per image: its stream's bytes before stuffing (the bits of its blocks, padded to a byte) and its
+// chunks.  nparts: the parts of the blocks' scan, part[nparts] their total.
+__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_images_kernel(
+    const int *__restrict__ first, int n, const int64_t *__restrict__ off,
+    const int64_t *__restrict__ part, int64_t nparts, int64_t *__restrict__ ibytes,
+    int64_t *__restrict__ ichunks) {
+    const int i = blockIdx.x * ENC_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int64_t a = enc_offset(off, part, first[i]);
+    const int64_t e = i + 1 < n ? enc_offset(off, part, first[i + 1]) : part[nparts];
+    const int64_t bytes = (e - a + 7) >> 3;
+    ibytes[i] = bytes;
+    ichunks[i] = (bytes + ENC_CHUNK - 1) / ENC_CHUNK;
+}
+
+// ---- the scratch and the checks --------------------------------------------------------------------
 // the scratch of pano_jpeg_encode: coefficients, bit counts, bit offsets, scan parts
 struct EncWork {
     int64_t coef, counts, offs, parts, bytes;
@@ -494,243 +631,6 @@ static inline dim3 enc_groups(int64_t n, int per) {
     return capped_grid(ceil_div(n, per), ENC_MAX_GROUPS);
 }
 
-extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch,
-                                int flags, int subsampling, const uint8_t *qt, void *work,
-                                int64_t work_bytes, const uint8_t **stream_out,
-                                int64_t *stream_bytes) {
-    PANO_ENTER(ctx, "pano_jpeg_encode");
-    PANO_REQUIRE(img && qt && work && stream_out && stream_bytes, "pano_jpeg_encode: null pointer");
-    *stream_out = nullptr;
-    *stream_bytes = 0;
-    EncImage E;
-    PANO_REQUIRE(enc_geometry(h, w, subsampling, E),
-                 "pano_jpeg_encode: %d x %d, subsampling %d (1..%d per side, 0..2)", w, h,
-                 subsampling, PANO_JPEG_MAX_SIDE);
-    PANO_REQUIRE(pitch >= 3 * (int64_t)w && (flags & ~PANO_JPEG_BGR) == 0,
-                 "pano_jpeg_encode: pitch %lld for %d pixels, flags %d", (long long)pitch, w, flags);
-    for (int i = 0; i < 128; ++i)
-        PANO_REQUIRE(qt[i] >= 1, "pano_jpeg_encode: quantiser %d is 0", i);
-    const EncWork L = enc_work(E.nblocks);
-    PANO_REQUIRE(work_bytes >= L.bytes, "pano_jpeg_encode: work of %lld bytes, %lld needed",
-                 (long long)work_bytes, (long long)L.bytes);
-    E.img = img;
-    E.pitch = pitch;
-    E.bgr = flags & PANO_JPEG_BGR;
-    for (int i = 0; i < 128; ++i) E.q[i >> 6][i & 63] = qt[i];
-    const hipStream_t s = (hipStream_t)stream;
-    uint8_t *w8 = (uint8_t *)work;
-    int16_t *coef = (int16_t *)(w8 + L.coef);
-    uint32_t *counts = (uint32_t *)(w8 + L.counts);
-    int64_t *offs = (int64_t *)(w8 + L.offs), *parts = (int64_t *)(w8 + L.parts);
-    const int64_t nb = E.nblocks, nbparts = ceil_div(nb, ENC_SCAN_TILE);
-
-    // 1. blocks, 2. bit counts, 3. their scan; wait for the total
-    PANO_TIMED(PK_JPEG_ENC_BLOCKS, s,
-               hipLaunchKernelGGL(jpeg_enc_blocks_kernel, enc_groups(nb, ENC_TILE), dim3(ENC_BLOCK),
-                                  0, s, E, coef));
-    PANO_LAUNCH_CHECK("jpeg_enc_blocks_kernel");
-    PANO_TIMED(PK_JPEG_ENC_COUNT, s,
-               hipLaunchKernelGGL(jpeg_enc_count_kernel, enc_groups(nb, ENC_WAVES), dim3(ENC_BLOCK),
-                                  0, s, E, (const int16_t *)coef, counts));
-    PANO_LAUNCH_CHECK("jpeg_enc_count_kernel");
-    if (int rc = enc_scan(ctx, s, counts, nb, offs, parts)) return rc;
-    int64_t total_bits = 0;
-    PANO_HIP(hipMemcpyAsync(&total_bits, parts + nbparts, 8, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
-    PANO_REQUIRE(total_bits > 0 && total_bits < ((int64_t)1 << 40),
-                 "pano_jpeg_encode: %lld bits", (long long)total_bits);
-
-    // the stream buffer: raw words (whole chunks, zeroed), the chunks' 0xFF counts and offsets
-    const int64_t nbytes = ceil_div(total_bits, 8), nchunks = ceil_div(nbytes, ENC_CHUNK);
-    const int64_t raw_bytes = align_up(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
-                  off_at = cnt_at + align_up(4 * nchunks), part_at = off_at + align_up(8 * nchunks),
-                  dev_bytes = part_at + align_up(8 * (ceil_div(nchunks, ENC_SCAN_TILE) + 1));
-    // (the context's buffers grow with a quarter to spare; the stream is idle, nothing reads them)
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_DEV], dev_bytes, false, dev_bytes / 4)) return rc;
-    uint8_t *const dev = (uint8_t *)ctx->buf[BUF_ENC_DEV].p;
-    uint32_t *raw = (uint32_t *)dev;
-    uint32_t *ccount = (uint32_t *)(dev + cnt_at);
-    int64_t *coff = (int64_t *)(dev + off_at), *cpart = (int64_t *)(dev + part_at);
-    PANO_HIP(hipMemsetAsync(raw, 0, raw_bytes, s));
-
-    // 4. emission, 5. stuffing counts and their scan; wait for the stuffed size
-    PANO_TIMED(PK_JPEG_ENC_EMIT, s,
-               hipLaunchKernelGGL(jpeg_enc_emit_kernel, enc_groups(nb, ENC_WAVES), dim3(ENC_BLOCK),
-                                  0, s, E, (const int16_t *)coef, (const uint32_t *)counts,
-                                  (const int64_t *)offs, (const int64_t *)parts, raw));
-    PANO_LAUNCH_CHECK("jpeg_enc_emit_kernel");
-    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_stuff_count_kernel, dim3((unsigned)ceil_div(nchunks, ENC_BLOCK)),
-                                  dim3(ENC_BLOCK), 0, s, (const uint32_t *)raw, nchunks, ccount));
-    PANO_LAUNCH_CHECK("jpeg_enc_stuff_count_kernel");
-    if (int rc = enc_scan(ctx, s, ccount, nchunks, coff, cpart)) return rc;
-    int64_t ffs = 0;
-    PANO_HIP(hipMemcpyAsync(&ffs, cpart + ceil_div(nchunks, ENC_SCAN_TILE), 8, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
-    PANO_REQUIRE(ffs >= 0 && ffs <= nbytes, "pano_jpeg_encode: %lld 0xFF bytes", (long long)ffs);
-    const int64_t out_bytes = nbytes + ffs;
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_OUT], out_bytes, false, out_bytes / 4)) return rc;
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], out_bytes, true, out_bytes / 4)) return rc;
-    uint8_t *const out = (uint8_t *)ctx->buf[BUF_ENC_OUT].p;
-    uint8_t *const host = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
-    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_stuff_write_kernel, dim3((unsigned)ceil_div(nchunks, ENC_BLOCK)),
-                                  dim3(ENC_BLOCK), 0, s, (const uint8_t *)raw, nbytes, nchunks,
-                                  (const int64_t *)coff, (const int64_t *)cpart, out));
-    PANO_LAUNCH_CHECK("jpeg_enc_stuff_write_kernel");
-
-    // the download
-    PANO_HIP(hipMemcpyAsync(host, out, out_bytes, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
-    *stream_out = host;
-    *stream_bytes = out_bytes;
-    return PANO_OK;
-}
-
-// ---- the batch (pano_jpeg_encode_batch) ------------------------------------------------------------
-// The blocks of all images are numbered one after the other, image by image; first[i] is image
-// i's first block (first[n]: the total) and a workgroup finds a block's image by bisecting that
-// table, so the block-wise kernels above run unchanged on (image, block in the image) and their
-// workgroups straddle images freely.  The counts of all blocks are scanned together; an image's
-// bits are the difference of the offsets at its two ends.  Every image's raw bits start on a whole
-// stuffing chunk (chunk0[i], from a scan of the images' chunk counts), so no word, pad byte or 0xFF
-// of one image touches another's, and the stuffed streams are packed byte after byte: a chunk's
-// count is its stream bytes plus its 0xFF bytes, and the scan of those is the output position.
-struct EncDesc {
-    const uint8_t *img;
-    int64_t pitch;
-    int w, h, mx, my;
-    int wib[2], hib[2];
-};
-
-// the largest i in [0, n) with t[i] <= v (t ascending, t[0] <= v)
-template <class T>
-__device__ __forceinline__ int enc_find(const T *__restrict__ t, int n, T v) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (t[mid] <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// image i's geometry: S holds what the batch shares (sampling, channel order)
-__device__ __forceinline__ EncGeom enc_batch_geom(const EncImage &S, const EncDesc *__restrict__ desc,
-                                                  const int *__restrict__ first, int i) {
-    const EncDesc d = desc[i];
-    EncGeom E = S;
-    E.img = d.img;
-    E.pitch = d.pitch;
-    E.w = d.w;
-    E.h = d.h;
-    E.mx = d.mx;
-    E.my = d.my;
-    E.wib[0] = d.wib[0];
-    E.wib[1] = d.wib[1];
-    E.hib[0] = d.hib[0];
-    E.hib[1] = d.hib[1];
-    E.nblocks = first[i + 1] - first[i];
-    return E;
-}
-
-// S.nblocks is the batch's total
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_blocks_kernel(
-    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
-    int16_t *__restrict__ coef) {
-    __shared__ int tile[ENC_TILE][8][9];
-    for (int64_t base = (int64_t)blockIdx.x * ENC_TILE; base < S.nblocks;
-         base += (int64_t)gridDim.x * ENC_TILE) {
-        const int g = (int)base + (threadIdx.x >> 3);
-        const bool live = g < S.nblocks;
-        const int i = live ? enc_find(first, n, g) : 0;
-        const EncGeom E = enc_batch_geom(S, desc, first, i);
-        enc_block(E, S.q, g - first[i], live, tile, coef + 64 * (int64_t)g);
-    }
-}
-
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_count_kernel(
-    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
-    const int16_t *__restrict__ coef, uint32_t *__restrict__ counts) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int64_t g = (int64_t)blockIdx.x * ENC_WAVES + wave; g < S.nblocks;
-         g += (int64_t)gridDim.x * ENC_WAVES) {
-        const int i = enc_find(first, n, (int)g);
-        const EncGeom E = enc_batch_geom(S, desc, first, i);
-        const int16_t *ci = coef + 64 * (int64_t)first[i];
-        const int bits = wave_sum(enc_lane_code(E, ci, (int)g - first[i], lane).n);
-        if (lane == 0) counts[g] = (uint32_t)bits;
-    }
-}
-
-// per image: its stream's bytes before stuffing (the bits of its blocks, padded to a byte) and its
-// chunks.  nparts: the parts of the blocks' scan, part[nparts] their total.
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_images_kernel(
-    const int *__restrict__ first, int n, const int64_t *__restrict__ off,
-    const int64_t *__restrict__ part, int64_t nparts, int64_t *__restrict__ ibytes,
-    int64_t *__restrict__ ichunks) {
-    const int i = blockIdx.x * ENC_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int64_t a = enc_offset(off, part, first[i]);
-    const int64_t e = i + 1 < n ? enc_offset(off, part, first[i + 1]) : part[nparts];
-    const int64_t bytes = (e - a + 7) >> 3;
-    ibytes[i] = bytes;
-    ichunks[i] = (bytes + ENC_CHUNK - 1) / ENC_CHUNK;
-}
-
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_emit_kernel(
-    EncImage S, const EncDesc *__restrict__ desc, const int *__restrict__ first, int n,
-    const int16_t *__restrict__ coef, const uint32_t *__restrict__ counts,
-    const int64_t *__restrict__ off, const int64_t *__restrict__ part,
-    const int64_t *__restrict__ chunk0, uint32_t *__restrict__ raw) {
-    __shared__ uint32_t words[ENC_WAVES][ENC_WORDS];
-    const int wave = threadIdx.x >> 6;
-    for (int64_t base = (int64_t)blockIdx.x * ENC_WAVES; base < S.nblocks;
-         base += (int64_t)gridDim.x * ENC_WAVES) {
-        const int64_t g = base + wave;
-        const bool live = g < S.nblocks;
-        const int i = live ? enc_find(first, n, (int)g) : 0;
-        const EncGeom E = enc_batch_geom(S, desc, first, i);
-        const int f = first[i];
-        const int64_t b0 = live ? chunk0[i] * (8 * ENC_CHUNK) + enc_offset(off, part, g) -
-                                      enc_offset(off, part, f)
-                                : 0;
-        enc_emit_block(E, coef + 64 * (int64_t)f, (int)g - f, live, b0, live ? (int)counts[g] : 0,
-                       g == first[i + 1] - 1, words[wave], raw);
-    }
-}
-
-// the stream bytes of chunk c, which is image i's
-__device__ __forceinline__ int enc_chunk_bytes(const int64_t *__restrict__ chunk0,
-                                               const int64_t *__restrict__ ibytes, int i, int64_t c) {
-    const int64_t left = ibytes[i] - (c - chunk0[i]) * ENC_CHUNK;
-    return (int)(left < ENC_CHUNK ? left : ENC_CHUNK);
-}
-
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_stuff_count_kernel(
-    const uint32_t *__restrict__ raw, int64_t nchunks, const int64_t *__restrict__ chunk0,
-    const int64_t *__restrict__ ibytes, int n, uint32_t *__restrict__ counts) {
-    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
-    if (c >= nchunks) return;
-    const int i = enc_find(chunk0, n, c);
-    counts[c] = (uint32_t)enc_chunk_bytes(chunk0, ibytes, i, c) + enc_chunk_ffs(raw, c);
-}
-
-// out: int64 offsets[n + 1] of the images' streams, then (at out + head) the streams
-__global__ __launch_bounds__(ENC_BLOCK) void jpeg_enc_batch_stuff_write_kernel(
-    const uint8_t *__restrict__ raw, int64_t nchunks, const int64_t *__restrict__ chunk0,
-    const int64_t *__restrict__ ibytes, int n, const int64_t *__restrict__ off,
-    const int64_t *__restrict__ part, uint8_t *__restrict__ out, int64_t head) {
-    const int64_t c = (int64_t)blockIdx.x * ENC_BLOCK + threadIdx.x;
-    if (c >= nchunks) return;
-    const int i = enc_find(chunk0, n, c);
-    const int64_t a = c * ENC_CHUNK, o = enc_offset(off, part, c);
-    const int64_t end = enc_stuff_bytes(raw, a, a + enc_chunk_bytes(chunk0, ibytes, i, c), out + head, o);
-    int64_t *offsets = (int64_t *)out;
-    if (c == chunk0[i]) offsets[i] = o;
-    if (c == nchunks - 1) offsets[n] = end;
-}
-
 // the scratch of pano_jpeg_encode_batch: EncWork, then the first-block table, the descriptors (the
 // two are uploaded as one), the images' bytes and their chunks (scanned in place)
 struct EncBatchWork {
@@ -755,37 +655,176 @@ extern "C" size_t pano_jpeg_encode_batch_work_bytes(int64_t blocks, int n) {
     return (size_t)enc_batch_work(blocks, n).bytes;
 }
 
+// What both entry points check (who: the one that was called, for the messages).  Image i:
+// its geometry into E.
+static int enc_check_image(const char *who, int i, const uint8_t *img, int h, int w, int64_t pitch,
+                           int subsampling, EncImage &E) {
+    PANO_REQUIRE(img && enc_geometry(h, w, subsampling, E),
+                 "%s: image %d: %d x %d at %p, subsampling %d (1..%d per side, 0..2)", who, i, w, h,
+                 (const void *)img, subsampling, PANO_JPEG_MAX_SIDE);
+    PANO_REQUIRE(pitch >= 3 * (int64_t)w, "%s: image %d: pitch %lld for %d pixels", who, i,
+                 (long long)pitch, w);
+    return PANO_OK;
+}
+// The settings, into S, and the scratch's size.
+static int enc_check_call(const char *who, int flags, const uint8_t *qt, int64_t work_bytes,
+                          int64_t needed, EncImage &S) {
+    PANO_REQUIRE((flags & ~PANO_JPEG_BGR) == 0, "%s: flags %d", who, flags);
+    for (int i = 0; i < 128; ++i) PANO_REQUIRE(qt[i] >= 1, "%s: quantiser %d is 0", who, i);
+    PANO_REQUIRE(work_bytes >= needed, "%s: work of %lld bytes, %lld needed", who,
+                 (long long)work_bytes, (long long)needed);
+    S.bgr = flags & PANO_JPEG_BGR;
+    for (int i = 0; i < 128; ++i) S.q[i >> 6][i & 63] = qt[i];
+    return PANO_OK;
+}
+
+static int enc_wait(hipStream_t s, const int64_t *dev, int64_t &v) {
+    PANO_HIP(hipMemcpyAsync(&v, dev, 8, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipStreamSynchronize(s));
+    return PANO_OK;
+}
+
+// ---- the driver of both entry points ---------------------------------------------------------------
+// S: what the images share, nblocks the blocks of all of them; work, L: the scratch (checked).
+// Leaves in pinned memory at *host, where.head bytes in (the batch's offsets come first), the
+// *out_bytes bytes of the stuffed streams.  Waits on the stream three times.
+template <class W>
+static int enc_run(pano_ctx *ctx, hipStream_t s, const char *who, const EncImage &S, const W &where,
+                   void *work, const EncWork &L, const uint8_t **host, int64_t *out_bytes) {
+    uint8_t *w8 = (uint8_t *)work;
+    int16_t *coef = (int16_t *)(w8 + L.coef);
+    uint32_t *counts = (uint32_t *)(w8 + L.counts);
+    int64_t *offs = (int64_t *)(w8 + L.offs), *parts = (int64_t *)(w8 + L.parts);
+    const int64_t nb = S.nblocks, nbparts = ceil_div(nb, ENC_SCAN_TILE);
+
+    // 1. blocks, 2. bit counts, 3. their scan
+    PANO_TIMED(PK_JPEG_ENC_BLOCKS, s,
+               hipLaunchKernelGGL(jpeg_enc_blocks_kernel<W>, enc_groups(nb, ENC_TILE), dim3(ENC_BLOCK),
+                                  0, s, S, where, coef));
+    PANO_LAUNCH_CHECK("jpeg_enc_blocks_kernel");
+    PANO_TIMED(PK_JPEG_ENC_COUNT, s,
+               hipLaunchKernelGGL(jpeg_enc_count_kernel<W>, enc_groups(nb, ENC_WAVES), dim3(ENC_BLOCK),
+                                  0, s, S, where, (const int16_t *)coef, counts));
+    PANO_LAUNCH_CHECK("jpeg_enc_count_kernel");
+    if (int rc = enc_scan(ctx, s, counts, nb, offs, parts)) return rc;
+
+    // wait for the size of raw: nchunks chunks, nbytes to its end
+    int64_t nbytes = 0, nchunks = 0;
+    if constexpr (W::kBatch) {      // the images' bytes and chunks, each image on chunks of its own
+        PANO_TIMED(PK_JPEG_ENC_SCAN, s,
+                   hipLaunchKernelGGL(jpeg_enc_batch_images_kernel, dim3(ceil_div(where.n, ENC_BLOCK)),
+                                      dim3(ENC_BLOCK), 0, s, where.first, where.n, (const int64_t *)offs,
+                                      (const int64_t *)parts, nbparts, where.ibytes, where.chunk0));
+        PANO_LAUNCH_CHECK("jpeg_enc_batch_images_kernel");
+        PANO_TIMED(PK_JPEG_ENC_SCAN, s,
+                   hipLaunchKernelGGL((scan_exclusive_kernel<ENC_SCAN, int64_t>), dim3(1), dim3(ENC_SCAN),
+                                      0, s, (const int64_t *)where.chunk0, (int64_t)where.n,
+                                      where.chunk0));
+        PANO_LAUNCH_CHECK("scan_exclusive_kernel");
+        if (int rc = enc_wait(s, where.chunk0 + where.n, nchunks)) return rc;
+        PANO_REQUIRE(nchunks >= where.n && nchunks < ((int64_t)1 << 34), "%s: %lld chunks", who,
+                     (long long)nchunks);
+        nbytes = nchunks * ENC_CHUNK;
+    } else {                        // the bits of the one stream
+        int64_t total_bits = 0;
+        if (int rc = enc_wait(s, parts + nbparts, total_bits)) return rc;
+        PANO_REQUIRE(total_bits > 0 && total_bits < ((int64_t)1 << 40), "%s: %lld bits", who,
+                     (long long)total_bits);
+        nbytes = ceil_div(total_bits, 8);
+        nchunks = ceil_div(nbytes, ENC_CHUNK);
+    }
+
+    // the stream buffer: raw words (whole chunks, zeroed), the chunks' counts and offsets
+    const int64_t raw_bytes = align_up(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
+                  off_at = cnt_at + align_up(4 * nchunks), part_at = off_at + align_up(8 * nchunks),
+                  ncparts = ceil_div(nchunks, ENC_SCAN_TILE),
+                  dev_bytes = part_at + align_up(8 * (ncparts + 1));
+    // (the context's buffers grow with a quarter to spare; the stream is idle, nothing reads them)
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_DEV], dev_bytes, false, dev_bytes / 4)) return rc;
+    uint8_t *const dev = (uint8_t *)ctx->buf[BUF_ENC_DEV].p;
+    uint32_t *raw = (uint32_t *)dev;
+    uint32_t *ccount = (uint32_t *)(dev + cnt_at);
+    int64_t *coff = (int64_t *)(dev + off_at), *cpart = (int64_t *)(dev + part_at);
+    PANO_HIP(hipMemsetAsync(raw, 0, raw_bytes, s));
+
+    // 4. emission, 5. the chunks' counts and their scan; wait for the stuffed size
+    PANO_TIMED(PK_JPEG_ENC_EMIT, s,
+               hipLaunchKernelGGL(jpeg_enc_emit_kernel<W>, enc_groups(nb, ENC_WAVES), dim3(ENC_BLOCK),
+                                  0, s, S, where, (const int16_t *)coef, (const uint32_t *)counts,
+                                  (const int64_t *)offs, (const int64_t *)parts, raw));
+    PANO_LAUNCH_CHECK("jpeg_enc_emit_kernel");
+    const dim3 cgrid((unsigned)ceil_div(nchunks, ENC_BLOCK));
+    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
+               hipLaunchKernelGGL(jpeg_enc_stuff_count_kernel<W>, cgrid, dim3(ENC_BLOCK), 0, s, where,
+                                  (const uint32_t *)raw, nchunks, ccount));
+    PANO_LAUNCH_CHECK("jpeg_enc_stuff_count_kernel");
+    if (int rc = enc_scan(ctx, s, ccount, nchunks, coff, cpart)) return rc;
+    int64_t sum = 0;
+    if (int rc = enc_wait(s, cpart + ncparts, sum)) return rc;
+    const int64_t stuffed = W::stuffed(nbytes, sum), all_bytes = where.head + stuffed;
+    PANO_REQUIRE(sum >= 0 && stuffed >= where.n && stuffed <= 2 * nbytes,
+                 "%s: %lld bytes after stuffing %lld", who, (long long)stuffed, (long long)nbytes);
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_OUT], all_bytes, false, all_bytes / 4)) return rc;
+    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], all_bytes, true, all_bytes / 4)) return rc;
+    uint8_t *const out = (uint8_t *)ctx->buf[BUF_ENC_OUT].p;
+    uint8_t *const pinned = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
+    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
+               hipLaunchKernelGGL(jpeg_enc_stuff_write_kernel<W>, cgrid, dim3(ENC_BLOCK), 0, s, where,
+                                  (const uint8_t *)raw, nbytes, nchunks, (const int64_t *)coff,
+                                  (const int64_t *)cpart, out));
+    PANO_LAUNCH_CHECK("jpeg_enc_stuff_write_kernel");
+
+    // the download (a batch's offsets and streams in one copy)
+    PANO_HIP(hipMemcpyAsync(pinned, out, all_bytes, hipMemcpyDeviceToHost, s));
+    PANO_HIP(hipStreamSynchronize(s));
+    *host = pinned;
+    *out_bytes = stuffed;
+    return PANO_OK;
+}
+
+// ---- the entry points ------------------------------------------------------------------------------
+extern "C" int pano_jpeg_encode(pano_ctx *ctx, const uint8_t *img, int h, int w, int64_t pitch,
+                                int flags, int subsampling, const uint8_t *qt, void *work,
+                                int64_t work_bytes, const uint8_t **stream_out,
+                                int64_t *stream_bytes) {
+    const char *const who = "pano_jpeg_encode";
+    PANO_ENTER(ctx, who);
+    PANO_REQUIRE(img && qt && work && stream_out && stream_bytes, "%s: null pointer", who);
+    *stream_out = nullptr;
+    *stream_bytes = 0;
+    EncImage S;
+    if (int rc = enc_check_image(who, 0, img, h, w, pitch, subsampling, S)) return rc;
+    const EncWork L = enc_work(S.nblocks);
+    if (int rc = enc_check_call(who, flags, qt, work_bytes, L.bytes, S)) return rc;
+    S.img = img;
+    S.pitch = pitch;
+    return enc_run(ctx, (hipStream_t)stream, who, S, EncOne{}, work, L, stream_out, stream_bytes);
+}
+
 extern "C" int pano_jpeg_encode_batch(pano_ctx *ctx, const pano_jpeg_image *images, int n, int flags,
                                       int subsampling, const uint8_t *qt, void *work,
                                       int64_t work_bytes, const uint8_t **streams,
                                       const int64_t **offsets) {
-    PANO_ENTER(ctx, "pano_jpeg_encode_batch");
-    PANO_REQUIRE(images && qt && work && streams && offsets, "pano_jpeg_encode_batch: null pointer");
+    const char *const who = "pano_jpeg_encode_batch";
+    PANO_ENTER(ctx, who);
+    PANO_REQUIRE(images && qt && work && streams && offsets, "%s: null pointer", who);
     *streams = nullptr;
     *offsets = nullptr;
-    PANO_REQUIRE(n >= 1 && n <= PANO_JPEG_BATCH_MAX, "pano_jpeg_encode_batch: %d images (1..%d)", n,
+    PANO_REQUIRE(n >= 1 && n <= PANO_JPEG_BATCH_MAX, "%s: %d images (1..%d)", who, n,
                  PANO_JPEG_BATCH_MAX);
-    PANO_REQUIRE((flags & ~PANO_JPEG_BGR) == 0, "pano_jpeg_encode_batch: flags %d", flags);
-    for (int i = 0; i < 128; ++i)
-        PANO_REQUIRE(qt[i] >= 1, "pano_jpeg_encode_batch: quantiser %d is 0", i);
-    EncImage S{};
+    EncImage S{};                   // no image or pitch of its own
     int64_t nb = 0;
     for (int i = 0; i < n; ++i) {
         const pano_jpeg_image &m = images[i];
-        PANO_REQUIRE(m.img && enc_geometry(m.h, m.w, subsampling, S),
-                     "pano_jpeg_encode_batch: image %d: %d x %d at %p, subsampling %d (1..%d per "
-                     "side, 0..2)", i, m.w, m.h, (const void *)m.img, subsampling, PANO_JPEG_MAX_SIDE);
-        PANO_REQUIRE(m.pitch >= 3 * (int64_t)m.w, "pano_jpeg_encode_batch: image %d: pitch %lld for "
-                     "%d pixels", i, (long long)m.pitch, m.w);
+        if (int rc = enc_check_image(who, i, m.img, m.h, m.w, m.pitch, subsampling, S)) return rc;
         nb += S.nblocks;
-        PANO_REQUIRE(nb <= PANO_JPEG_BATCH_MAX_BLOCKS, "pano_jpeg_encode_batch: more than %d blocks",
+        PANO_REQUIRE(nb <= PANO_JPEG_BATCH_MAX_BLOCKS, "%s: more than %d blocks", who,
                      PANO_JPEG_BATCH_MAX_BLOCKS);
     }
     const EncBatchWork L = enc_batch_work(nb, n);
-    PANO_REQUIRE(work_bytes >= L.bytes, "pano_jpeg_encode_batch: work of %lld bytes, %lld needed",
-                 (long long)work_bytes, (long long)L.bytes);
+    if (int rc = enc_check_call(who, flags, qt, work_bytes, L.bytes, S)) return rc;
 
-    // the tables, staged in the pinned buffer (the last call's streams end here)
+    // the tables, staged in the pinned buffer (the last call's streams end here), and their upload
     if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], L.table_bytes, true)) return rc;
     uint8_t *const stage = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
     int *const hfirst = (int *)stage;
@@ -800,95 +839,18 @@ extern "C" int pano_jpeg_encode_batch(pano_ctx *ctx, const pano_jpeg_image *imag
         nb += S.nblocks;
     }
     hfirst[n] = (int)nb;
-    S.img = nullptr;
-    S.pitch = 0;
     S.nblocks = (int)nb;
-    S.bgr = flags & PANO_JPEG_BGR;
-    for (int i = 0; i < 128; ++i) S.q[i >> 6][i & 63] = qt[i];
     const hipStream_t s = (hipStream_t)stream;
     uint8_t *w8 = (uint8_t *)work;
-    int16_t *coef = (int16_t *)(w8 + L.w.coef);
-    uint32_t *counts = (uint32_t *)(w8 + L.w.counts);
-    int64_t *offs = (int64_t *)(w8 + L.w.offs), *parts = (int64_t *)(w8 + L.w.parts);
-    const int *first = (const int *)(w8 + L.first);
-    const EncDesc *desc = (const EncDesc *)(w8 + L.desc);
-    int64_t *ibytes = (int64_t *)(w8 + L.ibytes), *chunk0 = (int64_t *)(w8 + L.ichunks);
-    const int64_t nbparts = ceil_div(nb, ENC_SCAN_TILE);
     PANO_HIP(hipMemcpyAsync(w8 + L.first, stage, L.table_bytes, hipMemcpyHostToDevice, s));
-
-    // 1. blocks, 2. bit counts, 3. their scan, the images' bytes and chunks; wait for the chunks
-    PANO_TIMED(PK_JPEG_ENC_BLOCKS, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_blocks_kernel, enc_groups(nb, ENC_TILE),
-                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, coef));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_blocks_kernel");
-    PANO_TIMED(PK_JPEG_ENC_COUNT, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_count_kernel, enc_groups(nb, ENC_WAVES),
-                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, (const int16_t *)coef,
-                                  counts));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_count_kernel");
-    if (int rc = enc_scan(ctx, s, counts, nb, offs, parts)) return rc;
-    PANO_TIMED(PK_JPEG_ENC_SCAN, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_images_kernel, dim3(ceil_div(n, ENC_BLOCK)),
-                                  dim3(ENC_BLOCK), 0, s, first, n, (const int64_t *)offs,
-                                  (const int64_t *)parts, nbparts, ibytes, chunk0));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_images_kernel");
-    PANO_TIMED(PK_JPEG_ENC_SCAN, s,
-               hipLaunchKernelGGL((scan_exclusive_kernel<ENC_SCAN, int64_t>), dim3(1), dim3(ENC_SCAN),
-                                  0, s, (const int64_t *)chunk0, (int64_t)n, chunk0));
-    PANO_LAUNCH_CHECK("scan_exclusive_kernel");
-    int64_t nchunks = 0;
-    PANO_HIP(hipMemcpyAsync(&nchunks, chunk0 + n, 8, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
-    PANO_REQUIRE(nchunks >= n && nchunks < ((int64_t)1 << 34), "pano_jpeg_encode_batch: %lld chunks",
-                 (long long)nchunks);
-
-    // the stream buffer: raw words (whole chunks, zeroed), the chunks' counts and offsets
-    const int64_t raw_bytes = align_up(nchunks * ENC_CHUNK), cnt_at = raw_bytes,
-                  off_at = cnt_at + align_up(4 * nchunks), part_at = off_at + align_up(8 * nchunks),
-                  ncparts = ceil_div(nchunks, ENC_SCAN_TILE),
-                  dev_bytes = part_at + align_up(8 * (ncparts + 1));
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_DEV], dev_bytes, false, dev_bytes / 4)) return rc;
-    uint8_t *const dev = (uint8_t *)ctx->buf[BUF_ENC_DEV].p;
-    uint32_t *raw = (uint32_t *)dev;
-    uint32_t *ccount = (uint32_t *)(dev + cnt_at);
-    int64_t *coff = (int64_t *)(dev + off_at), *cpart = (int64_t *)(dev + part_at);
-    PANO_HIP(hipMemsetAsync(raw, 0, raw_bytes, s));
-
-    // 4. emission, 5. the chunks' output bytes and their scan; wait for the stuffed size
-    PANO_TIMED(PK_JPEG_ENC_EMIT, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_emit_kernel, enc_groups(nb, ENC_WAVES),
-                                  dim3(ENC_BLOCK), 0, s, S, desc, first, n, (const int16_t *)coef,
-                                  (const uint32_t *)counts, (const int64_t *)offs,
-                                  (const int64_t *)parts, (const int64_t *)chunk0, raw));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_emit_kernel");
-    const dim3 cgrid((unsigned)ceil_div(nchunks, ENC_BLOCK));
-    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_stuff_count_kernel, cgrid, dim3(ENC_BLOCK), 0, s,
-                                  (const uint32_t *)raw, nchunks, (const int64_t *)chunk0,
-                                  (const int64_t *)ibytes, n, ccount));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_stuff_count_kernel");
-    if (int rc = enc_scan(ctx, s, ccount, nchunks, coff, cpart)) return rc;
+    const EncBatch where{(const EncDesc *)(w8 + L.desc), (const int *)(w8 + L.first), n,
+                         (int64_t *)(w8 + L.ichunks), (int64_t *)(w8 + L.ibytes),
+                         align_up(8 * ((int64_t)n + 1))};
+    const uint8_t *host = nullptr;
     int64_t out_bytes = 0;
-    PANO_HIP(hipMemcpyAsync(&out_bytes, cpart + ncparts, 8, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
-    PANO_REQUIRE(out_bytes >= n && out_bytes <= 2 * nchunks * ENC_CHUNK,
-                 "pano_jpeg_encode_batch: %lld stuffed bytes", (long long)out_bytes);
-    const int64_t head = align_up(8 * ((int64_t)n + 1)), all_bytes = head + out_bytes;
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_OUT], all_bytes, false, all_bytes / 4)) return rc;
-    if (int rc = pano_buf_reserve(ctx->buf[BUF_ENC_HOST], all_bytes, true, all_bytes / 4)) return rc;
-    uint8_t *const out = (uint8_t *)ctx->buf[BUF_ENC_OUT].p;
-    uint8_t *const host = (uint8_t *)ctx->buf[BUF_ENC_HOST].p;
-    PANO_TIMED(PK_JPEG_ENC_STUFF, s,
-               hipLaunchKernelGGL(jpeg_enc_batch_stuff_write_kernel, cgrid, dim3(ENC_BLOCK), 0, s,
-                                  (const uint8_t *)raw, nchunks, (const int64_t *)chunk0,
-                                  (const int64_t *)ibytes, n, (const int64_t *)coff,
-                                  (const int64_t *)cpart, out, head));
-    PANO_LAUNCH_CHECK("jpeg_enc_batch_stuff_write_kernel");
-
-    // the download: the offsets and the streams in one copy
-    PANO_HIP(hipMemcpyAsync(host, out, all_bytes, hipMemcpyDeviceToHost, s));
-    PANO_HIP(hipStreamSynchronize(s));
+    if (int rc = enc_run(ctx, s, who, S, where, work, L.w, &host, &out_bytes)) return rc;
     *offsets = (const int64_t *)host;
-    *streams = host + head;
+    *streams = host + where.head;
     return PANO_OK;
 }
+

@@ -609,6 +609,37 @@ def encodable(img, quality=75, subsampling=-1):
             and subsampling in SUBSAMPLING)
 
 
+def _encode_setup(images, quality, subsampling, order, eng, numbered):
+    """What both encodes do around their native call.  Raises their ValueErrors (``numbered``:
+    "image i: " in front); None for no images, before an engine is needed.  Else the engine, the
+    calls' flags, subsampling and quantiser table, ``scratch(nbytes)`` (a fresh device tensor, the
+    calls' arguments for it) and ``to_file(h, w, address, nbytes)`` (header, stream, EOI)."""
+    import torch
+    from . import _lib
+    if order not in ("bgr", "rgb"):
+        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
+    for i, img in enumerate(images):
+        if not hasattr(img, "shape") or not encodable(img, quality, subsampling):
+            raise ValueError(f"image {i}: " * numbered + f"{tuple(getattr(img, 'shape', ()))} "
+                             f"{getattr(img, 'dtype', type(img))} at quality {quality}, "
+                             f"subsampling {subsampling}: not a case the device encodes")
+    if not images:
+        return None
+    eng = _lib._engine(eng)
+    qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
+    settings = (int(order == "bgr"), 2 if subsampling == -1 else subsampling,
+                qt.ctypes.data_as(C.c_void_p))
+
+    def scratch(nbytes):
+        work = torch.empty(int(nbytes), dtype=torch.uint8, device=torch.device(eng.device))
+        return work, (_lib._ptr(work), C.c_int64(int(nbytes)))
+
+    def to_file(h, w, address, nbytes):
+        return encode_header(w, h, quality, subsampling) + C.string_at(address, nbytes) + b"\xff\xd9"
+
+    return eng, settings, scratch, to_file
+
+
 def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_coefs=False):
     """The JPEG file of a uint8 [h][w][3] image (a device tensor, or a host array that is
     uploaded), byte for byte what ``Image.fromarray(rgb).save(f, "JPEG", quality=quality,
@@ -620,35 +651,21 @@ def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_c
     order, DC not differenced, MCU order).  Raises ValueError for what ``encodable`` rejects."""
     import torch
     from . import _lib
-    from . import engine as _eng
-    if order not in ("bgr", "rgb"):
-        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
-    if not encodable(img, quality, subsampling):
-        raise ValueError(f"{tuple(img.shape)} {img.dtype} at quality {quality}, subsampling "
-                         f"{subsampling}: not a case the device encodes")
-    eng = _lib._engine(eng)
-    dev = torch.device(eng.device)
+    eng, settings, scratch, to_file = _encode_setup([img], quality, subsampling, order, eng, False)
     img = _lib.rgb_on_device(img, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
-    sub = 2 if subsampling == -1 else subsampling
-    lib = eng.lib
-    work_bytes = int(lib.pano_jpeg_encode_work_bytes(h, w, sub))
-    work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
-    qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
+    work, work_args = scratch(eng.lib.pano_jpeg_encode_work_bytes(h, w, settings[1]))
     stream, nbytes = C.c_void_p(), C.c_int64()
-    _lib.check(lib.pano_jpeg_encode(
-        eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)),
-        1 if order == "bgr" else 0, sub, qt.ctypes.data_as(C.c_void_p), _eng._ptr(work),
-        C.c_int64(work_bytes), C.byref(stream), C.byref(nbytes)), "pano_jpeg_encode")
-    data = encode_header(w, h, quality, subsampling) + C.string_at(stream.value, nbytes.value) \
-        + b"\xff\xd9"
+    _lib.check(eng.lib.pano_jpeg_encode(
+        eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)), *settings,
+        *work_args, C.byref(stream), C.byref(nbytes)), "pano_jpeg_encode")
+    data = to_file(h, w, stream.value, nbytes.value)
     if not want_coefs:
         return data
-    hm, vm = SUBSAMPLING[subsampling]
-    nblocks = -(-w // (8 * hm)) * -(-h // (8 * vm)) * (hm * vm + 2)
+    nblocks = encode_blocks(h, w, subsampling)
     zz = work[:128 * nblocks].view(torch.int16).view(nblocks, 64)
     coefs = torch.empty_like(zz)
-    coefs[:, torch.from_numpy(ZIGZAG.astype(np.int64)).to(dev)] = zz
+    coefs[:, torch.from_numpy(ZIGZAG.astype(np.int64)).to(work.device)] = zz
     return data, coefs
 
 
@@ -695,49 +712,31 @@ def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=Non
     together and waits on the stream twice and downloads once, however many they are.  An empty
     list gives [].  Raises ValueError, before anything is queued, for an image ``encodable``
     rejects."""
-    import torch
     from . import _lib
-    from . import engine as _eng
     images = list(images)
-    if order not in ("bgr", "rgb"):
-        raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
-    for i, img in enumerate(images):
-        if not hasattr(img, "shape") or not encodable(img, quality, subsampling):
-            raise ValueError(f"image {i}: {tuple(getattr(img, 'shape', ()))} "
-                             f"{getattr(img, 'dtype', type(img))} at quality {quality}, "
-                             f"subsampling {subsampling}: not a case the device encodes")
-    if not images:
+    setup = _encode_setup(images, quality, subsampling, order, eng, True)
+    if setup is None:
         return []
+    eng, settings, scratch, to_file = setup
     shapes = [(int(img.shape[0]), int(img.shape[1])) for img in images]
     blocks = [encode_blocks(h, w, subsampling) for h, w in shapes]
-    batches = plan_encode_batches(blocks, max_work)
-    eng = _lib._engine(eng)
-    dev = torch.device(eng.device)
-    lib = eng.lib
-    sub = 2 if subsampling == -1 else subsampling
-    qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
     files = []
-    for batch in batches:
+    for batch in plan_encode_batches(blocks, max_work):
         held = []                                       # uploads and copies live until the call ends
         table = (_lib.JpegImage * len(batch))()
         for rec, i in zip(table, batch):
             img = _lib.rgb_on_device(images[i], eng)
-            h, w = shapes[i]
             held.append(img)
-            rec.img, rec.pitch, rec.h, rec.w = img.data_ptr(), img.stride(0), h, w
-        total = sum(blocks[i] for i in batch)
-        work_bytes = int(lib.pano_jpeg_encode_batch_work_bytes(C.c_int64(total), len(batch)))
-        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+            rec.img, rec.pitch, (rec.h, rec.w) = img.data_ptr(), img.stride(0), shapes[i]
+        total = C.c_int64(sum(blocks[i] for i in batch))
+        work, work_args = scratch(eng.lib.pano_jpeg_encode_batch_work_bytes(total, len(batch)))
         streams, offsets = C.c_void_p(), C.c_void_p()
-        _lib.check(lib.pano_jpeg_encode_batch(
-            eng.ctx(), table, len(batch), 1 if order == "bgr" else 0, sub,
-            qt.ctypes.data_as(C.c_void_p), _eng._ptr(work), C.c_int64(work_bytes),
-            C.byref(streams), C.byref(offsets)), "pano_jpeg_encode_batch")
+        _lib.check(eng.lib.pano_jpeg_encode_batch(
+            eng.ctx(), table, len(batch), *settings, *work_args, C.byref(streams),
+            C.byref(offsets)), "pano_jpeg_encode_batch")
         offs = (C.c_int64 * (len(batch) + 1)).from_address(offsets.value)
         for k, i in enumerate(batch):
-            h, w = shapes[i]
-            files.append(encode_header(w, h, quality, subsampling)
-                         + C.string_at(streams.value + offs[k], offs[k + 1] - offs[k]) + b"\xff\xd9")
+            files.append(to_file(*shapes[i], streams.value + offs[k], offs[k + 1] - offs[k]))
     return files
 
 
