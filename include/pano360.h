@@ -761,10 +761,15 @@ int pano_sift_detect_replaying(const pano_ctx *ctx);
  * four best per query are re-evaluated in float32 (sum of squared differences) and a bound
  * on the ranking error proves that no other row can be among the best two - a query whose
  * proof fails is rescanned exactly (counted in *rescans, optional dev int).
- * query: dev float [nq][d], train: dev float [nt][d], nt >= 2, d <= 128; scale: a power of
- * two with max |value| * scale <= 2048 (keeps the float16 halves normal); work: dev scratch
- * of pano_knn2_work_bytes(nq, nt, d) bytes.  idx: dev int32 [nq][2], dist: dev float [nq][2],
- * nearest first (equal distances: lower index first). */
+ * A distance is the float32 sum of squared differences in one fixed order, then sqrtf.
+ * query: dev float [nq][d], train: dev float [nt][d], nt >= 2, d <= 128; scale: a finite
+ * power of two with max |value| * scale <= 2048 over both sets (the float16 high halves stay
+ * finite, the products far below float32's range) and max |train value| * scale >= 2^-3
+ * (below that the low halves are float16 denormals whose rounding the error bound no longer
+ * covers; the values are not inspected, so a scale outside this interval is not refused and
+ * the answer may then be inexact); work: dev scratch of pano_knn2_work_bytes(nq, nt, d)
+ * bytes, contents ignored.  idx: dev int32 [nq][2], dist: dev float [nq][2], nearest first
+ * (equal distances: lower index first). */
 size_t pano_knn2_work_bytes(int nq, int nt, int d);
 int pano_knn2(pano_ctx *ctx, const float *query, int nq, const float *train, int nt, int d,
               float scale, void *work, int32_t *idx, float *dist, int *rescans);

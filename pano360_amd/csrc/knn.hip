@@ -352,7 +352,7 @@ extern "C" int pano_knn2(pano_ctx *ctx, const float *query, int nq, const float 
     PANO_REQUIRE(nq >= 0 && nt >= 2, "pano_knn2: %d queries against %d rows (at least 2)", nq, nt);
     PANO_REQUIRE(d >= 1 && d <= 16 * KNN_MAX_KS, "pano_knn2: %d features (at most %d)", d,
                  16 * KNN_MAX_KS);
-    PANO_REQUIRE(scale > 0.0f, "pano_knn2: scale %g", (double)scale);
+    PANO_REQUIRE(scale > 0.0f && scale < __builtin_inff(), "pano_knn2: scale %g", (double)scale);
     if (nq == 0) return PANO_OK;
     const hipStream_t s = (hipStream_t)stream;
     const KnnWork w = knn_layout(nq, nt, d);

@@ -804,7 +804,10 @@ class DMatch:
 
 
 def _knn_scale(peak):
-    """A power of two that brings the largest magnitude to ~1024: float16 halves stay normal."""
+    """A power of two that brings the largest magnitude of both sets into (512, 1024]: inside
+    the interval ``pano_knn2`` states for it (at most 2048, and the train set's largest times the
+    scale at least 2^-3) whenever the train set's peak is within 2^12 of the joint one, as the
+    descriptors of one detector are (DESIGN, "The scale rule of pano_knn2")."""
     return float(2.0 ** np.floor(np.log2(1024.0 / peak))) if peak > 0 else 1.0
 
 
@@ -815,7 +818,10 @@ def knn2_device(des1, des2, eng=None, want_rescans=False, scale=None):
     float16) rank the rows, the four best per query are re-evaluated exactly in float32 and
     an error bound proves the rest cannot beat them (else that query is rescanned exactly).
     ``scale``: ``_knn_scale`` of the largest magnitude of both sets when the caller knows it
-    (no wait for the device's maximum)."""
+    (no wait for the device's maximum).  That joint peak is also what is taken when ``scale`` is
+    not given; the answer is guaranteed exact while ``des2``'s largest magnitude times the scale
+    is at least 2^-3 (``pano_knn2``), i.e. while ``des2``'s peak is within 2^12 of the joint one:
+    large ``des1`` against tiny ``des2`` falls outside the rule, and nothing reports it."""
     idx, dist, rescans = _knn2_raw(des1, des2, eng or _eng.engine(), scale)
     if want_rescans:
         return idx.long(), dist, int(rescans.item())
