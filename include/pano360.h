@@ -1449,6 +1449,69 @@ int pano_photo_stats(pano_ctx *ctx, const pano_photo_frame *frames, int n_frames
                      const double *log_gains, const double *alpha, double tau, double *sums);
 int pano_photo_apply_u8(pano_ctx *ctx, const pano_photo_apply *frames, int n);
 
+/* Exposure fusion of bracketed frames at the ingest          (the reference takes one image per
+ * position; Mertens, Kautz, Van Reeth 2007, OpenCV's MergeMertens; csrc/fuse.hip, NumPy statement:
+ * tests/fuse_model.py)
+ * A stack is k exposures (2 .. PANO_FUSE_MAX_EXPOSURES) of one view: uint8 [h][w][3] BGR frames of
+ * one size, sides 1 .. PANO_FUSE_MAX_SIDE, rows `pitch` bytes apart; one fused uint8 [h][w][3]
+ * frame comes out.  Everything is float32, one rounding per operation in the order written (no
+ * fused multiply-add), pyrDown / pyrUp are cv2's as oracle/cv2_shim.py restates them.
+ *   A, raw weights, per exposure and pixel:
+ *       B, G, R = (float)byte / 255.0f
+ *       g = (0.114f B + 0.587f G) + 0.299f R
+ *       lap = ((g[y][x-1] + g[y][x+1]) + (g[y-1][x] + g[y+1][x])) - 4 g, indices reflected as
+ *             BORDER_REFLECT_101 (on a side of length 1 the neighbour is the pixel itself)
+ *       C = |lap|
+ *       m = ((B + G) + R) / 3, S = sqrtf((((B-m)^2 + (G-m)^2) + (R-m)^2) / 3)
+ *       E = expf(-((((B-.5f)^2 + (G-.5f)^2) + (R-.5f)^2) / 0.08f))       (sigma = 0.2, one exponential)
+ *       W = ((C^contrast S^saturation) E^exposure) + 1e-12f: an exponent of exactly 1 multiplies
+ *           the factor as it is, of exactly 0 leaves it out, anything else is powf.  (1, 1, 1) is
+ *           the paper's choice; OpenCV's default is (1, 1, 0).
+ *   B, normalise and pack: T = ((W_0 + W_1) + ...) + W_k-1, N_i = W_i / T, the packed pixel of
+ *       exposure i is the float4 (B, G, R, N_i).
+ *   C, pyramids: L = max(0, bit_length(min(h, w)) - 2) levels below the frame, so that the coarsest
+ *       level is at least 2 x 2 (where pyrUp is defined; one level fewer than OpenCV's
+ *       int(log2(min side))); params->n_levels in 0 .. L overrides it, -1 is the default.
+ *       P_i,0 = the packed image, P_i,l+1 = pyrDown(P_i,l) on all four channels.
+ *   D, fused levels: for l < L, R_l = sum_i N_i,l (P_i,l[BGR] - pyrUp(P_i,l+1[BGR])[:h_l, :w_l]);
+ *       R_L = sum_i N_i,L P_i,L[BGR]; N_i,l is channel 3 of P_i,l; a sum starts from the i = 0
+ *       product and adds the others in order of i.  The Laplacian pyramids are never stored.
+ *   E, collapse and quantise: from l = L - 1 down to 0, R_l = R_l + pyrUp(R_l+1)[:h_l, :w_l];
+ *       out = rint(min(max(R_0 255, 0), 255)), ties to even.
+ * pano_fuse_work_bytes(h, w, k): the workspace of one stack, callable without a GPU: with h_0 = h,
+ *     w_0 = w, h_l+1 = (h_l + 1) / 2 (w alike) and a256 rounding up to a multiple of 256,
+ *       sum over l = 0 .. L of a256(16 k h_l w_l) + a256(16 h_l w_l)
+ *     (the k packed images and the fused level, float4 per pixel).  0 for a side or k out of range.
+ * pano_fuse_u8: ONE call fuses n stacks of mixed sizes and k, one after another on the context's
+ *     stream through the one workspace `work` (dev, work_bytes long, at least pano_fuse_work_bytes
+ *     of the call's largest stack).  stacks: HOST records; src, dst, raw, fused: dev.  raw
+ *     (float32 [k][h][w], stage A's W) and fused (float32 [h][w][3], stage E's R_0 before it is
+ *     quantised) are optional outputs of the kernels that feed the next stage; NULL: not written.
+ *     3 L + 2 launches per stack (3 when L = 0), asynchronous, no host wait, no atomics: two calls
+ *     give the same bytes, and a stack's result does not depend on what else is in the call.
+ *     PANO_EINVAL, with nothing launched: a null pointer, n < 1, k outside 2 .. 8, a side outside
+ *     1 .. 32767, a pitch below 3 w, n_levels outside -1 .. L of any stack, an exponent that is
+ *     negative or not finite, work_bytes too small, a dst that overlaps a source frame of its
+ *     stack or the workspace. */
+#define PANO_FUSE_MAX_EXPOSURES 8
+#define PANO_FUSE_MAX_SIDE 32767
+typedef struct pano_fuse_stack {
+    const uint8_t *src[PANO_FUSE_MAX_EXPOSURES];   /* dev uint8 [h][w][3]; the first k are read   */
+    int64_t src_pitch[PANO_FUSE_MAX_EXPOSURES];    /* bytes between their rows                    */
+    uint8_t *dst;              /* dev uint8 [h][w][3], rows dst_pitch bytes apart   */
+    int64_t dst_pitch;
+    float *raw;                /* dev float32 [k][h][w] or NULL                     */
+    float *fused;              /* dev float32 [h][w][3] or NULL                     */
+    int32_t w, h, k, reserved;
+} pano_fuse_stack;
+typedef struct pano_fuse_params {
+    float contrast, saturation, exposure;          /* the exponents, finite and >= 0              */
+    int32_t n_levels;          /* -1: the default L of each stack                   */
+} pano_fuse_params;
+size_t pano_fuse_work_bytes(int h, int w, int k);
+int pano_fuse_u8(pano_ctx *ctx, const pano_fuse_stack *stacks, int n, const pano_fuse_params *params,
+                 void *work, int64_t work_bytes);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

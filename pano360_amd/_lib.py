@@ -105,6 +105,9 @@ LENS_CUBIC, LENS_LINEAR = 0, 1
 PHOTO_MAX_SIDE = 32767
 PHOTO_SUMS = 25
 PHOTO_TABLE = 1026
+# pano_fuse_u8: PANO_FUSE_MAX_EXPOSURES, PANO_FUSE_MAX_SIDE
+FUSE_MAX_EXPOSURES = 8
+FUSE_MAX_SIDE = 32767
 JPEG_BATCH_MAX = 16384
 JPEG_BATCH_MAX_BLOCKS = 1 << 28
 
@@ -152,6 +155,20 @@ class PhotoApply(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("table", C.c_void_p),
                 ("src_pitch", C.c_int64), ("dst_pitch", C.c_int64),
                 ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class FuseStack(C.Structure):
+    """``pano_fuse_stack`` of include/pano360.h (176 bytes)."""
+    _fields_ = [("src", C.c_void_p * FUSE_MAX_EXPOSURES), ("src_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
+                ("dst", C.c_void_p), ("dst_pitch", C.c_int64),
+                ("raw", C.c_void_p), ("fused", C.c_void_p),
+                ("w", C.c_int32), ("h", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FuseParams(C.Structure):
+    """``pano_fuse_params`` of include/pano360.h (16 bytes)."""
+    _fields_ = [("contrast", C.c_float), ("saturation", C.c_float), ("exposure", C.c_float),
+                ("n_levels", C.c_int32)]
 
 
 class Pair(C.Structure):
@@ -288,6 +305,8 @@ _SIGNATURES = {
     "pano_photo_stats": (_i, [_vp, C.POINTER(PhotoFrame), _i, C.POINTER(PhotoPair), _i, _i, _i, _i,
                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _vp]),
     "pano_photo_apply_u8": (_i, [_vp, C.POINTER(PhotoApply), _i]),
+    "pano_fuse_work_bytes": (C.c_size_t, [_i, _i, _i]),
+    "pano_fuse_u8": (_i, [_vp, C.POINTER(FuseStack), _i, C.POINTER(FuseParams), _vp, C.c_int64]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

@@ -12,7 +12,7 @@
 // Images are interleaved [h][w][c] exactly as the reference holds them, c <= 4.  Every
 // kernel is streaming (HBM bound): one thread per output element, neighbouring threads
 // on neighbouring addresses.
-#include "common.h"
+#include "pyr.h"
 
 // 0 plain pyrUp, 1 other - pyrUp (a Laplacian level, blend.py:126), 2 other + pyrUp
 // (collapse, blend.py:138)
@@ -35,25 +35,16 @@ __global__ __launch_bounds__(256) void lap_pyr_down_kernel(const T *__restrict__
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
         const T *s = src + (size_t)cy[k] * w * c;
-        rowv[k] = s[cx[2]] * (T)6 + (s[cx[1]] + s[cx[3]]) * (T)4 + s[cx[0]] + s[cx[4]];
+        rowv[k] = pyr_down_taps(s[cx[0]], s[cx[1]], s[cx[2]], s[cx[3]], s[cx[4]]);
     }
     dst[(size_t)y * ow * c + xc] =
-        (rowv[2] * (T)6 + (rowv[1] + rowv[3]) * (T)4 + rowv[0] + rowv[4]) * (T)(1.0 / 256.0);
+        pyr_down_taps(rowv[0], rowv[1], rowv[2], rowv[3], rowv[4]) * (T)(1.0 / 256.0);
 }
 
-// Horizontal pass of pyrUp at output column dx of source row s (n samples, stride c):
-// even dx: s[i-1] + s[i]*6 + s[i+1], odd: (s[i] + s[i+1])*4, with s[-1] := s[1] and
-// s[n] := s[n-1] written the way OpenCV's pyrUp_ writes its two edge columns.
+// Horizontal pass of pyrUp (pyr.h) at output column dx of source row s (n samples, stride c).
 template <typename T>
 __device__ __forceinline__ T up_row(const T *__restrict__ s, int n, int c, int dx) {
-    const int i = dx >> 1;
-    if (dx & 1) {
-        if (i == n - 1) return s[(size_t)i * c] * (T)8;
-        return (s[(size_t)i * c] + s[(size_t)(i + 1) * c]) * (T)4;
-    }
-    if (i == 0) return s[0] * (T)6 + s[c] * (T)2;
-    if (i == n - 1) return s[(size_t)(i - 1) * c] + s[(size_t)i * c] * (T)7;
-    return s[(size_t)(i - 1) * c] + s[(size_t)i * c] * (T)6 + s[(size_t)(i + 1) * c];
+    return pyr_up_row<T>([=](int i) { return s[(size_t)i * c]; }, n, dx);
 }
 
 // pyrUp(src)[:oh, :ow] combined with `other` ([oh][ow][c]) according to MODE.
@@ -73,10 +64,10 @@ __global__ __launch_bounds__(256) void lap_pyr_up_kernel(const T *__restrict__ s
     const T v2 = up_row(base + (size_t)r2 * sw * c, sw, c, x);
     T up;
     if (y & 1) {
-        up = ((v1 + v2) * (T)4) * (T)(1.0 / 64.0);
+        up = pyr_up_col_odd(v1, v2);
     } else {
         const T v0 = up_row(base + (size_t)r0 * sw * c, sw, c, x);
-        up = (v0 + v1 * (T)6 + v2) * (T)(1.0 / 64.0);
+        up = pyr_up_col_even(v0, v1, v2);
     }
     const size_t o = (size_t)y * ow * c + xc;
     if (MODE == UP_SUB)

@@ -1065,6 +1065,7 @@ def _assemble(kpts, found):
 
 def parse_args(argv=None):
     """The command line of ``main``."""
+    from . import fuse as _fuse
     from . import lens as _lens
     parser = argparse.ArgumentParser(description="Extract features.")
     parser.add_argument("--path", type=str, default="../data/ppwwyyxx/CMU2",
@@ -1072,17 +1073,22 @@ def parse_args(argv=None):
     parser.add_argument("--detector", default="sift", choices=["sift", "msop"],
                         help="feature detector (msop writes matches_<name>_msop.npz).")
     _lens.add_arguments(parser)
+    _fuse.add_arguments(parser)
     args = parser.parse_args(argv)
     _lens.check_arguments(parser, args)
+    _fuse.check_arguments(parser, args)
     return args
 
 
 def cache_name(args):
-    """``<name>`` of ``matches_<name>.npz``: the directory, ``_msop`` for that detector, ``_lens``
-    with ``--lens``."""
+    """``<name>`` of ``matches_<name>.npz``: the directory, ``_msop`` for that detector, ``_b<K>``
+    with ``--bracket K``, ``_lens`` with ``--lens``."""
+    from . import fuse as _fuse
     name = os.path.basename(args.path)
     if args.detector == "msop":
         name += "_msop"
+    if _fuse.bracket_of(args) is not None:
+        name += f"_b{_fuse.bracket_of(args)}"
     if args.lens is not None:
         name += "_lens"
     return name
@@ -1091,13 +1097,15 @@ def cache_name(args):
 def main(argv=None):
     """Script entry point (features.py:300-320): the images of ``--path``, shrunk by half,
     matched; writes ``matches_<name>.npz`` (``--detector msop``: ``matches_<name>_msop.npz``;
-    ``--lens FILE``: the images' lens distortion corrected first, ``matches_<name>_lens.npz``).
+    ``--lens FILE``: the images' lens distortion corrected first, ``matches_<name>_lens.npz``;
+    ``--bracket K``: every K files fused into one frame first, ``matches_<name>_b<K>.npz``).
     Read with Pillow, resized on the device."""
+    from . import fuse as _fuse
     from . import lens as _lens
     from .stitcher import ingest
     args = parse_args(argv)
     name = cache_name(args)
-    imgs = ingest(args.path, 2, lens=_lens.from_args(args))
+    imgs = ingest(args.path, 2, lens=_lens.from_args(args), bracket=_fuse.from_args(args))
     kpts, matches = matching(imgs, **detector_kwargs(args.detector))
     np.savez(f"matches_{name}.npz", kpts=kpts, matches=matches)
     return kpts, matches

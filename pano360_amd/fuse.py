@@ -1,0 +1,221 @@
+"""Exposure fusion of bracketed frames at the ingest, on the device (``pano_fuse_u8``,
+csrc/fuse.hip).
+
+A full sphere rarely fits one exposure - an interior with windows, a sun in the frame - and is
+shot as exposure brackets: K exposures per tripod position.  ``fuse_device`` merges the K frames
+of a position into one ordinary 8-bit frame before detection sees it, by the exposure fusion of
+Mertens, Kautz and Van Reeth (2007; OpenCV's ``MergeMertens``): every pixel of every exposure gets
+a weight from its local contrast, its saturation and its closeness to mid-grey, the weights are
+normalised over the exposures, and the frames' Laplacian pyramids are summed under the weights'
+Gaussian pyramids and collapsed.  No exposure times, no response curve and no EXIF are needed, and
+nothing downstream changes: the result is a uint8 BGR frame.
+
+Two choices differ from OpenCV's defaults.  The exponents default to the paper's ``(1, 1, 1)``
+(contrast, saturation, well-exposedness); OpenCV's ``createMergeMertens`` defaults to
+``(1, 1, 0)``, which ``FuseParams(exposure=0)`` gives.  And the pyramids have
+``levels_for(h, w) = max(0, bit_length(min(h, w)) - 2)`` levels below the frame, one fewer than
+OpenCV's ``int(log2(min side))``: the coarsest level stays at least 2 x 2, where ``pyrUp`` is
+defined.  The arithmetic is stated in include/pano360.h and, in NumPy, in tests/fuse_model.py.
+There is no CPU fallback.
+
+The brackets are taken as aligned (a tripod).  Not covered: aligning hand-held brackets, removing
+what moved between the exposures, a radiance (HDR) output and tone mapping.
+"""
+import argparse
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+
+MAX_EXPOSURES = _lib.FUSE_MAX_EXPOSURES
+MAX_SIDE = _lib.FUSE_MAX_SIDE
+
+
+def levels_for(h, w):
+    """The pyramid levels below an h x w frame: ``max(0, bit_length(min(h, w)) - 2)``."""
+    return max(0, int(min(h, w)).bit_length() - 2)
+
+
+class FuseParams:
+    """The exponents of the three quality measures (finite, >= 0; 1 takes the measure as it is, 0
+    leaves it out) and ``n_levels``: None for ``levels_for`` of each stack, or 0 .. that."""
+    __slots__ = ("contrast", "saturation", "exposure", "n_levels")
+
+    def __init__(self, contrast=1.0, saturation=1.0, exposure=1.0, n_levels=None):
+        self.contrast, self.saturation, self.exposure = float(contrast), float(saturation), float(exposure)
+        for name in ("contrast", "saturation", "exposure"):
+            value = getattr(self, name)
+            if not (np.isfinite(value) and value >= 0):
+                raise ValueError(f"{name} {value}: a finite exponent >= 0")
+        if n_levels is not None and int(n_levels) < 0:
+            raise ValueError(f"n_levels {n_levels}: None or >= 0")
+        self.n_levels = None if n_levels is None else int(n_levels)
+
+    def __repr__(self):
+        return (f"FuseParams({self.contrast}, {self.saturation}, {self.exposure}, "
+                f"n_levels={self.n_levels})")
+
+
+def _check_stack(i, stack):
+    stack = list(stack)
+    if not 2 <= len(stack) <= MAX_EXPOSURES:
+        raise ValueError(f"stack {i}: {len(stack)} exposures (2 .. {MAX_EXPOSURES})")
+    for e, frame in enumerate(stack):
+        shape = tuple(frame.shape)
+        if len(shape) != 3 or shape[2] != 3 or str(frame.dtype) not in ("uint8", "torch.uint8"):
+            raise ValueError(f"stack {i}, exposure {e}: {frame.dtype} {shape}, not uint8 [h][w][3]")
+        if shape != tuple(stack[0].shape):
+            raise ValueError(f"stack {i}: exposure {e} is {shape[1]} x {shape[0]}, exposure 0 "
+                             f"{stack[0].shape[1]} x {stack[0].shape[0]}")
+    h, w = stack[0].shape[:2]
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f"stack {i}: {w} x {h} (sides 1 .. {MAX_SIDE})")
+    return stack
+
+
+def fuse_device(stacks, params=None, eng=None, want_stages=False):
+    """Fuses every stack of ``stacks`` - a list of lists of 2 .. 8 uint8 [h][w][3] BGR device
+    tensors of one size per stack, any sizes and counts across stacks - in ONE native call, through
+    one workspace sized for the largest.  Rows may be further apart than 3 w bytes (a rectangle of
+    a larger tensor is passed by its pitch, not copied).  Returns the fused uint8 [h][w][3] device
+    tensors; with ``want_stages`` a second list of ``(raw, fused_f32)`` per stack: the raw weights
+    float32 [k][h][w] and the collapsed pyramid float32 [h][w][3] before it is quantised, written
+    by the kernels that feed the next stage.  ``ValueError`` for mixed sizes in a stack, a count
+    outside 2 .. 8, a wrong dtype or shape, or ``n_levels`` above a stack's ``levels_for``.
+    Queued on the engine's stream."""
+    import torch
+    params = params or FuseParams()
+    stacks = [_check_stack(i, stack) for i, stack in enumerate(stacks)]
+    for i, stack in enumerate(stacks):
+        h, w = stack[0].shape[:2]
+        if params.n_levels is not None and params.n_levels > levels_for(h, w):
+            raise ValueError(f"stack {i}: n_levels {params.n_levels}, {w} x {h} has at most "
+                             f"{levels_for(h, w)}")
+    if not stacks:
+        return ([], []) if want_stages else []
+    eng = _lib._engine(eng)
+    records = (_lib.FuseStack * len(stacks))()
+    keep, outs, stages = [], [], []
+    need = 0
+    for rec, stack in zip(records, stacks):
+        stack = [_lib.rgb_on_device(frame, eng) for frame in stack]
+        keep.append(stack)
+        h, w, k = int(stack[0].shape[0]), int(stack[0].shape[1]), len(stack)
+        device = stack[0].device
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+        for e, frame in enumerate(stack):
+            rec.src[e], rec.src_pitch[e] = frame.data_ptr(), frame.stride(0)
+        rec.dst, rec.dst_pitch = out.data_ptr(), out.stride(0)
+        rec.w, rec.h, rec.k = w, h, k
+        if want_stages:
+            raw = torch.empty((k, h, w), dtype=torch.float32, device=device)
+            fused = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+            rec.raw, rec.fused = raw.data_ptr(), fused.data_ptr()
+            stages.append((raw, fused))
+        outs.append(out)
+        need = max(need, int(eng.lib.pano_fuse_work_bytes(h, w, k)))
+    work = torch.empty(need, dtype=torch.uint8, device=outs[0].device)
+    native = _lib.FuseParams(params.contrast, params.saturation, params.exposure,
+                             -1 if params.n_levels is None else params.n_levels)
+    _lib.check(eng.lib.pano_fuse_u8(eng.ctx(), records, len(stacks), C.byref(native), work.data_ptr(),
+                                    need), "pano_fuse_u8")
+    # (the kernels are queued on the stream the tensors belong to: the frames and `work` may go)
+    return (outs, stages) if want_stages else outs
+
+
+def fuse(stacks, params=None):
+    """``fuse_device`` on host arrays: a list of lists of uint8 [h][w][3] NumPy arrays in, the
+    fused NumPy arrays out."""
+    return [t.cpu().numpy() for t in fuse_device([[np.asarray(f) for f in s] for s in stacks], params)]
+
+
+def group_files(files, k):
+    """The file names sorted and cut into consecutive groups of ``k``: the brackets of one
+    position after another, as cameras number them.  ``ValueError`` when the count is no multiple
+    of ``k``."""
+    files, k = sorted(files), int(k)
+    if not 2 <= k <= MAX_EXPOSURES:
+        raise ValueError(f"brackets of {k} (2 .. {MAX_EXPOSURES})")
+    if len(files) % k:
+        raise ValueError(f"{len(files)} images cannot be grouped into brackets of {k}")
+    return [files[i:i + k] for i in range(0, len(files), k)]
+
+
+class Bracket:
+    """What ``--bracket`` asked for: ``k`` exposures per position and the ``FuseParams``."""
+    __slots__ = ("k", "params")
+
+    def __init__(self, k, params=None):
+        self.k = int(k)
+        if not 2 <= self.k <= MAX_EXPOSURES:
+            raise ValueError(f"brackets of {self.k} (2 .. {MAX_EXPOSURES})")
+        self.params = params or FuseParams()
+
+    def fuse_groups(self, frames, groups, eng=None):
+        """``frames``: the decoded device tensors in the order of the groups' files.  Every group
+        fused by ONE ``fuse_device`` call; a group whose frames differ in size is a ``ValueError``
+        that names its files."""
+        stacks, at = [], 0
+        for group in groups:
+            stack = frames[at:at + len(group)]
+            at += len(group)
+            if len({tuple(f.shape) for f in stack}) != 1:
+                sizes = ", ".join(f"{os.path.basename(n)} {f.shape[1]} x {f.shape[0]}"
+                                  for n, f in zip(group, stack))
+                raise ValueError(f"the exposures of a bracket differ in size: {sizes}")
+            stacks.append(stack)
+        return fuse_device(stacks, self.params, eng)
+
+
+# ------------------------------------------------------------- command line
+def _weights(text):
+    try:
+        values = [float(v) for v in text.split(",")]
+    except ValueError:
+        values = []
+    if len(values) != 3 or not all(np.isfinite(v) and v >= 0 for v in values):
+        raise argparse.ArgumentTypeError(f"{text!r}: three finite exponents >= 0, as C,S,E")
+    return tuple(values)
+
+
+def _count(text):
+    try:
+        k = int(text)
+    except ValueError:
+        k = 0
+    if not 2 <= k <= MAX_EXPOSURES:
+        raise argparse.ArgumentTypeError(f"{text!r}: 2 .. {MAX_EXPOSURES} exposures per position")
+    return k
+
+
+def add_arguments(parser):
+    """``--bracket`` and ``--bracket-weights`` of stitcher.py and features.py.  Without the flags
+    the parsed namespace is what it was (no attribute: ``bracket_of`` reads them)."""
+    parser.add_argument("--bracket", type=_count, metavar="K", default=argparse.SUPPRESS,
+                        help="the directory holds exposure brackets, K (2 .. 8) consecutive files "
+                             "(in sorted order) per position: each bracket is fused into one frame "
+                             "on the device as it is read (exposure fusion, Mertens et al.); the "
+                             "caches get a _b<K> suffix.")
+    parser.add_argument("--bracket-weights", type=_weights, metavar="C,S,E", default=argparse.SUPPRESS,
+                        help="--bracket: the exponents of contrast, saturation and well-exposedness "
+                             "(default 1,1,1, the paper's; OpenCV's default is 1,1,0).")
+
+
+def bracket_of(args):
+    """K of ``--bracket``, or None."""
+    return getattr(args, "bracket", None)
+
+
+def check_arguments(parser, args):
+    if bracket_of(args) is None and getattr(args, "bracket_weights", None) is not None:
+        parser.error("--bracket-weights needs --bracket")
+
+
+def from_args(args):
+    """The ``Bracket`` the command line asks for (None without ``--bracket``)."""
+    if bracket_of(args) is None:
+        return None
+    weights = getattr(args, "bracket_weights", None) or (1.0, 1.0, 1.0)
+    return Bracket(bracket_of(args), FuseParams(*weights))

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import bundle_adj as _ba
 from . import engine as _eng
+from . import fuse as _fuse
 from . import lens as _lens
 from . import photo as _photo
 from .engine import CylProj, SphProj  # noqa: F401  (re-exported API)
@@ -331,7 +332,7 @@ def _download_cropped(mosaic, rect):
 IMAGE_EXTENSIONS = (".jpg", ".png", ".bmp", ".JPG", ".PNG", ".BMP")     # stitcher.py:411-412
 
 
-def ingest(path, shrink, decode="device", lens=None):
+def ingest(path, shrink, decode="device", lens=None, bracket=None):
     """The head of the reference's ``main`` (stitcher.py:415-421): every image of the
     directory, in ``os.listdir`` order, as ``cv2.imread`` would return it (uint8 BGR), shrunk by
     ``cv2.resize(im, None, fx=1/shrink, fy=1/shrink)`` when shrink > 1 - on the device.
@@ -339,23 +340,37 @@ def ingest(path, shrink, decode="device", lens=None):
     (``jpeg.read_images``), everything else by Pillow; "host": every file by Pillow.  The frames
     are the same either way.  ``lens`` (a ``lens.Calibration``): every decoded frame's lens
     distortion is corrected on the device, at the file's own resolution, before the shrink.
+    ``bracket`` (a ``fuse.Bracket``, or the number of exposures per position): the images are
+    taken in sorted file-name order instead, K consecutive files are one position's exposures
+    (``fuse.group_files``), and after the one decode every group is fused into one frame by one
+    ``fuse.fuse_device`` call; the fused frames take the images' place, in group order, the lens
+    correction then runs under each group's first file name: decode, fuse, lens, shrink.
     Returns uint8 [h][w][3] device tensors."""
     from . import blend as _blend
     from . import jpeg as _jpeg
     if decode not in ("device", "host"):
         raise ValueError(f"decode={decode!r}: 'device' or 'host'")
     files = [f for f in os.listdir(path) if any(f.endswith(ext) for ext in IMAGE_EXTENSIONS)]
+    groups = None
+    if bracket is not None:
+        if not isinstance(bracket, _fuse.Bracket):
+            bracket = _fuse.Bracket(bracket)
+        groups = _fuse.group_files(files, bracket.k)
+        files = [f for group in groups for f in group]
     paths = [os.path.join(path, f) for f in files]
     if decode == "host":
         # cv2.imread's defaults: the EXIF orientation applied (a phone's rotated JPEG arrives
         # upright, with its shape swapped), 8 bits, three channels: 16-bit images are scaled
         # down to 8 bits and an alpha channel is dropped, as IMREAD_COLOR does
         images = [_jpeg._pillow_read(p) for p in paths]
-        if lens is None:
+        if lens is None and groups is None:
             return _blend.shrink_images(images, shrink)
         frames = _blend.shrink_images(images, 1)            # (the upload alone)
     else:
         frames, _ = _jpeg.read_images(paths)
+    if groups is not None:
+        frames = bracket.fuse_groups(frames, groups)
+        files = [group[0] for group in groups]
     if lens is not None:
         frames = lens.correct_device(frames, files)
     if shrink > 1:
@@ -550,6 +565,7 @@ def parse_args(argv=None):
                              "the stitch (not with --lens).")
     _lens.add_arguments(parser)
     _photo.add_arguments(parser)
+    _fuse.add_arguments(parser)
     args = parser.parse_args(argv)
     if refine_of(args)[1] is not None:
         if args.lens is not None:
@@ -557,6 +573,7 @@ def parse_args(argv=None):
         args.refine = True
     _lens.check_arguments(parser, args)
     _photo.check_arguments(parser, args)
+    _fuse.check_arguments(parser, args)
     if args.ghost_tol is not None and args.blend != "median":
         parser.error("--ghost-tol needs -b median")
     if args.fill and args.crop:
@@ -574,11 +591,14 @@ def parse_args(argv=None):
 
 def cache_name(args):
     """``<name>`` of ``matches_<name>.npz`` and ``ba_<name>.pkl``: the directory and the shrink
-    as in the reference, ``_msop`` for that detector, ``_lens`` with ``--lens``: matches and
-    cameras of corrected and uncorrected frames never mix."""
+    as in the reference, ``_msop`` for that detector, ``_b<K>`` with ``--bracket K``, ``_lens``
+    with ``--lens``: matches and cameras of corrected and uncorrected, fused and plain frames
+    never mix."""
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
     if args.detector == "msop":
         name += "_msop"
+    if _fuse.bracket_of(args) is not None:
+        name += f"_b{_fuse.bracket_of(args)}"
     if args.lens is not None:
         name += "_lens"
     return name
@@ -590,6 +610,7 @@ def main(argv=None):
 
     name = cache_name(args)
     lens = _lens.from_args(args)
+    bracket = _fuse.from_args(args)
     cache = f"ba_{name}.pkl"
     try:
         with open(cache, "rb") as fid:
@@ -613,11 +634,12 @@ def main(argv=None):
             "the reference (the pickle written at stitcher.py:438-439) and re-run")
     index = None                    # of a cache: camera k is image k, if their numbers agree
     if regions is None:
-        frames = ingest(args.path, args.shrink, lens=lens)
+        frames = ingest(args.path, args.shrink, lens=lens, bracket=bracket)
         regions = _register(args.path, name, frames, args.ba, args.detector)
         index = _image_index(regions, frames)
     if any(reg.img is None for reg in regions):
-        frames = ingest(args.path, args.shrink, lens=lens) if os.path.isdir(args.path) else []
+        frames = ingest(args.path, args.shrink, lens=lens, bracket=bracket) \
+            if os.path.isdir(args.path) else []
         if len(frames) != len(regions):
             raise SystemExit(f"{cache} holds {len(regions)} cameras, {args.path} "
                              f"{len(frames)} images")
