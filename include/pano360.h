@@ -1512,6 +1512,77 @@ size_t pano_fuse_work_bytes(int h, int w, int k);
 int pano_fuse_u8(pano_ctx *ctx, const pano_fuse_stack *stacks, int n, const pano_fuse_params *params,
                  void *work, int64_t work_bytes);
 
+/* Alignment of hand-held exposure brackets before they are fused   (the reference takes one image
+ * per position; G. Ward 2003, median threshold bitmaps, OpenCV's AlignMTB; csrc/align.hip, NumPy
+ * statement: tests/align_model.py)
+ * A stack is k exposures (2 .. PANO_FUSE_MAX_EXPOSURES) of one view: uint8 [h][w][3] BGR frames of
+ * one size, sides 1 .. PANO_FUSE_MAX_SIDE, rows `pitch` bytes apart; `reference` (0 .. k - 1) is the
+ * exposure the others are moved onto.  Integers throughout; params: max_bits 0 .. 7 (the usual 6),
+ * exclude 0 .. 127 (the usual 4).
+ *   A, grey: g = (29 B + 150 G + 77 R + 128) >> 8, uint8.
+ *   B, pyramid: L = min(max_bits, max(0, bit_length(min(h, w)) - 5)) levels above the frame: the
+ *       coarsest keeps a short side of at least 16.  Level l + 1 is h_l / 2 by w_l / 2 (rounded
+ *       down: h_l = h >> l), each pixel (a + b + c + d + 2) >> 2 of its 2 x 2 block of level l; an
+ *       odd last row or column is dropped.  The levels nest: a 128 x 128-aligned tile of level 0
+ *       determines its part of every level up to 7.
+ *   C, median, per frame and level: m = the smallest v with #{g <= v} >= (N + 1) / 2, N = h_l w_l.
+ *   D, bitmaps, per frame and level: tb = g > m, eb = |g - m| > exclude, both packed 32 pixels a
+ *       uint32 along the row, wpr_l = ceil(w_l / 32) words per row: bit x & 31 of word x >> 5 is
+ *       pixel x; the bits from w_l on are 0.
+ *   E, search, for every frame i other than the reference r: s = (0, 0) at level L; going down a
+ *       level s <- 2 s.  At each level the nine candidates c = s + d are counted, numbered
+ *       d = (0, 0) first, then dy = -1, 0, 1 outer and dx = -1, 0, 1 inner without (0, 0):
+ *       err(c) = the number of pixels (x, y) of the reference with (x - c.x, y - c.y) inside frame
+ *       i and (tb_r[y][x] ^ tb_i[y - c.y][x - c.x]) & eb_r[y][x] & eb_i[y - c.y][x - c.x] set.
+ *       s <- the first candidate with the smallest err (strict <: identical or featureless frames
+ *       give (0, 0)).  The result (dx, dy) = s of level 0, |dx|, |dy| <= 2^(L+1) - 1, means
+ *       aligned[y][x] = src[y - dy][x - dx]; the reference's is (0, 0).
+ *   F, apply: aligned[y][x] = src[clamp(y - dy, 0, h - 1)][clamp(x - dx, 0, w - 1)], all three
+ *       bytes, for the frames that have a dst and a shift other than (0, 0).  The reference and
+ *       frames with a zero shift are NOT copied: their dst is left as it was, the caller takes
+ *       their src.  (The shifts stay on the device: the call waits for nothing, and the tiles of
+ *       an unmoved frame leave at once.)
+ * pano_align_work_bytes(h, w, k): the workspace of one stack, callable without a GPU: with
+ *     Lm = min(7, max(0, bit_length(min(h, w)) - 5)), h_l = h >> l, w_l = w >> l, p_l = w_l rounded
+ *     up to a multiple of 4, wpr_l as above and a256 rounding up to a multiple of 256,
+ *       a256(1024 k (Lm + 1)) + a256(36 k (Lm + 1)) + a256(4 k (Lm + 1))
+ *       + k * sum over l = 0 .. Lm of (a256(h_l p_l) + a256(8 h_l wpr_l))
+ *     (histograms, error counts, medians; per frame the grey levels and the two bitmaps of every
+ *     level).  0 for a side or k out of range.
+ * pano_align_mtb: ONE call aligns n stacks of mixed sizes and k: one table of tiles over all their
+ *     frames, 6 + L_max launches for up to 256 frames, queued on the context's stream, no host wait.
+ *     `work` (dev, work_bytes long) holds ALL stacks of the call at once: at least the sum of their
+ *     pano_align_work_bytes; it need not be cleared.  stacks: HOST records; src, dst, shifts and
+ *     the stage outputs: dev.  shifts: int32 [k][2] = (dx, dy) per exposure, always written.
+ *     dst[e] NULL: exposure e is not applied (shifts only).  Stage outputs, NULL in production,
+ *     dense, frame after frame and within a frame level 0 .. L: grey uint8 [h_l][w_l]; medians
+ *     int32 [k][L + 1]; bitmaps uint32, per level tb [h_l][wpr_l] then eb [h_l][wpr_l]; errs uint32
+ *     [k][L + 1][9] (the reference's are 0).  The counts are integer sums: two calls give the same
+ *     bytes, and a stack's result does not depend on what else is in the call.
+ *     PANO_EINVAL, with nothing launched or written: a null pointer (stacks, params, work, a src,
+ *     shifts), n < 1, k outside 2 .. 8, a side outside 1 .. 32767, reference outside 0 .. k - 1,
+ *     max_bits outside 0 .. 7, exclude outside 0 .. 127, a pitch below 3 w, work_bytes too small,
+ *     a dst that overlaps a source frame of its stack or the workspace. */
+typedef struct pano_align_stack {
+    const uint8_t *src[PANO_FUSE_MAX_EXPOSURES];   /* dev uint8 [h][w][3]; the first k are read   */
+    int64_t src_pitch[PANO_FUSE_MAX_EXPOSURES];    /* bytes between their rows                    */
+    uint8_t *dst[PANO_FUSE_MAX_EXPOSURES];         /* dev uint8 [h][w][3] per exposure, or NULL   */
+    int64_t dst_pitch[PANO_FUSE_MAX_EXPOSURES];
+    int32_t *shifts;           /* dev int32 [k][2]: (dx, dy)                        */
+    uint8_t *grey;             /* stage outputs, dev or NULL                        */
+    int32_t *medians;
+    uint32_t *bitmaps;
+    uint32_t *errs;
+    int32_t w, h, k, reference;
+} pano_align_stack;
+typedef struct pano_align_params {
+    int32_t max_bits;          /* 0 .. 7: at most this many levels above the frame  */
+    int32_t exclude;           /* 0 .. 127: pixels this close to the median are ignored */
+} pano_align_params;
+size_t pano_align_work_bytes(int h, int w, int k);
+int pano_align_mtb(pano_ctx *ctx, const pano_align_stack *stacks, int n, const pano_align_params *params,
+                   void *work, int64_t work_bytes);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -171,6 +171,20 @@ class FuseParams(C.Structure):
                 ("n_levels", C.c_int32)]
 
 
+class AlignStack(C.Structure):
+    """``pano_align_stack`` of include/pano360.h (312 bytes)."""
+    _fields_ = [("src", C.c_void_p * FUSE_MAX_EXPOSURES), ("src_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
+                ("dst", C.c_void_p * FUSE_MAX_EXPOSURES), ("dst_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
+                ("shifts", C.c_void_p), ("grey", C.c_void_p), ("medians", C.c_void_p),
+                ("bitmaps", C.c_void_p), ("errs", C.c_void_p),
+                ("w", C.c_int32), ("h", C.c_int32), ("k", C.c_int32), ("reference", C.c_int32)]
+
+
+class AlignParams(C.Structure):
+    """``pano_align_params`` of include/pano360.h (8 bytes)."""
+    _fields_ = [("max_bits", C.c_int32), ("exclude", C.c_int32)]
+
+
 class Pair(C.Structure):
     """``pano_pair`` of include/pano360.h (80 bytes)."""
     _fields_ = [("minv", C.c_double * 9), ("i", C.c_int32), ("j", C.c_int32)]
@@ -307,6 +321,8 @@ _SIGNATURES = {
     "pano_photo_apply_u8": (_i, [_vp, C.POINTER(PhotoApply), _i]),
     "pano_fuse_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_fuse_u8": (_i, [_vp, C.POINTER(FuseStack), _i, C.POINTER(FuseParams), _vp, C.c_int64]),
+    "pano_align_work_bytes": (C.c_size_t, [_i, _i, _i]),
+    "pano_align_mtb": (_i, [_vp, C.POINTER(AlignStack), _i, C.POINTER(AlignParams), _vp, C.c_int64]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

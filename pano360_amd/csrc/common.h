@@ -92,6 +92,10 @@ enum PanoKernelId {
     PK_DEFLATE_LENGTHS,
     PK_PHOTO_STATS,
     PK_BA_REFINE,
+    PK_ALIGN_GREY,
+    PK_ALIGN_BITMAP,
+    PK_ALIGN_SEARCH,
+    PK_ALIGN_APPLY,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------
@@ -164,6 +168,8 @@ enum PanoBufId {
     // per-workgroup partial sums
     BUF_PHOTO_DEV,
     BUF_PHOTO_PARTIALS,
+    // pano_align_mtb (align.hip): the records of a pass's launches
+    BUF_ALIGN_DEV,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it
@@ -283,6 +289,15 @@ static inline auto ceil_div(A a, B b) -> decltype(a + b) { return (a + b - 1) / 
 // the next multiple of 256 bytes: where a part of a work buffer starts
 template <class T>
 static inline T align_up(T bytes) { return (bytes + 255) / 256 * 256; }
+// whether the byte ranges [a, a + na) and [b, b + nb) meet
+static inline bool pano_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+// an exposure stack (fuse.hip, align.hip): k frames of h x w within the limits of the header
+static inline bool pano_stack_ok(int h, int w, int k) {
+    return h >= 1 && w >= 1 && h <= PANO_FUSE_MAX_SIDE && w <= PANO_FUSE_MAX_SIDE && k >= 2 &&
+           k <= PANO_FUSE_MAX_EXPOSURES;
+}
 // the grid of a kernel that loops beyond `cap` workgroups
 static inline dim3 capped_grid(int64_t groups, int64_t cap) {
     return dim3((unsigned)(groups < cap ? groups : cap));

@@ -266,21 +266,12 @@ static size_t fuse_layout(int h, int w, int k, FuseLevel *lv) {
     return at;
 }
 
-static inline bool fuse_stack_ok(int h, int w, int k) {
-    return h >= 1 && w >= 1 && h <= PANO_FUSE_MAX_SIDE && w <= PANO_FUSE_MAX_SIDE && k >= 2 &&
-           k <= PANO_FUSE_MAX_EXPOSURES;
-}
-
 extern "C" size_t pano_fuse_work_bytes(int h, int w, int k) {
-    return fuse_stack_ok(h, w, k) ? fuse_layout(h, w, k, nullptr) : 0;
-}
-
-static inline bool fuse_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    return pano_stack_ok(h, w, k) ? fuse_layout(h, w, k, nullptr) : 0;
 }
 
 static int fuse_check(const pano_fuse_stack &S, int i, int n_levels, const void *work, int64_t work_bytes) {
-    PANO_REQUIRE(fuse_stack_ok(S.h, S.w, S.k), "pano_fuse_u8: stack %d: %d exposures of %d x %d (2 .. %d, sides 1 .. %d)",
+    PANO_REQUIRE(pano_stack_ok(S.h, S.w, S.k), "pano_fuse_u8: stack %d: %d exposures of %d x %d (2 .. %d, sides 1 .. %d)",
                  i, S.k, S.w, S.h, PANO_FUSE_MAX_EXPOSURES, PANO_FUSE_MAX_SIDE);
     PANO_REQUIRE(S.dst, "pano_fuse_u8: stack %d: null dst", i);
     PANO_REQUIRE(S.dst_pitch >= 3 * (int64_t)S.w, "pano_fuse_u8: stack %d: dst pitch %lld for %d pixels", i,
@@ -291,13 +282,13 @@ static int fuse_check(const pano_fuse_stack &S, int i, int n_levels, const void 
                  "pano_fuse_u8: stack %d needs a workspace of %zu bytes, %lld given", i,
                  fuse_layout(S.h, S.w, S.k, nullptr), (long long)work_bytes);
     const size_t dst_bytes = (size_t)(S.h - 1) * S.dst_pitch + 3 * (size_t)S.w;
-    PANO_REQUIRE(!fuse_overlap(S.dst, dst_bytes, work, (size_t)work_bytes),
+    PANO_REQUIRE(!pano_overlap(S.dst, dst_bytes, work, (size_t)work_bytes),
                  "pano_fuse_u8: stack %d: dst overlaps the workspace", i);
     for (int e = 0; e < S.k; ++e) {
         PANO_REQUIRE(S.src[e], "pano_fuse_u8: stack %d: exposure %d: null pointer", i, e);
         PANO_REQUIRE(S.src_pitch[e] >= 3 * (int64_t)S.w, "pano_fuse_u8: stack %d: exposure %d: pitch %lld for %d pixels",
                      i, e, (long long)S.src_pitch[e], S.w);
-        PANO_REQUIRE(!fuse_overlap(S.dst, dst_bytes, S.src[e], (size_t)(S.h - 1) * S.src_pitch[e] + 3 * (size_t)S.w),
+        PANO_REQUIRE(!pano_overlap(S.dst, dst_bytes, S.src[e], (size_t)(S.h - 1) * S.src_pitch[e] + 3 * (size_t)S.w),
                      "pano_fuse_u8: stack %d: dst overlaps exposure %d", i, e);
     }
     return PANO_OK;

@@ -1082,13 +1082,12 @@ def parse_args(argv=None):
 
 def cache_name(args):
     """``<name>`` of ``matches_<name>.npz``: the directory, ``_msop`` for that detector, ``_b<K>``
-    with ``--bracket K``, ``_lens`` with ``--lens``."""
+    with ``--bracket K`` (``_b<K>a`` with ``--bracket-align``), ``_lens`` with ``--lens``."""
     from . import fuse as _fuse
     name = os.path.basename(args.path)
     if args.detector == "msop":
         name += "_msop"
-    if _fuse.bracket_of(args) is not None:
-        name += f"_b{_fuse.bracket_of(args)}"
+    name += _fuse.cache_suffix(args)
     if args.lens is not None:
         name += "_lens"
     return name

@@ -18,11 +18,14 @@ OpenCV's ``int(log2(min side))``: the coarsest level stays at least 2 x 2, where
 defined.  The arithmetic is stated in include/pano360.h and, in NumPy, in tests/fuse_model.py.
 There is no CPU fallback.
 
-The brackets are taken as aligned (a tripod).  Not covered: aligning hand-held brackets, removing
-what moved between the exposures, a radiance (HDR) output and tone mapping.
+The brackets are taken as aligned (a tripod) unless ``Bracket(k, align=AlignParams())`` /
+``--bracket-align`` asks for the integer alignment of ``pano360_amd.align`` first.  Not covered:
+rotation and parallax between the exposures, removing what moved in the scene between them, a
+radiance (HDR) output and tone mapping.
 """
 import argparse
 import ctypes as C
+import logging
 import os
 
 import numpy as np
@@ -144,19 +147,24 @@ def group_files(files, k):
 
 
 class Bracket:
-    """What ``--bracket`` asked for: ``k`` exposures per position and the ``FuseParams``."""
-    __slots__ = ("k", "params")
+    """What ``--bracket`` asked for: ``k`` exposures per position, the ``FuseParams`` and ``align``:
+    None for brackets that are aligned as they are, or the ``align.AlignParams`` of
+    ``--bracket-align``."""
+    __slots__ = ("k", "params", "align")
 
-    def __init__(self, k, params=None):
+    def __init__(self, k, params=None, align=None):
         self.k = int(k)
         if not 2 <= self.k <= MAX_EXPOSURES:
             raise ValueError(f"brackets of {self.k} (2 .. {MAX_EXPOSURES})")
         self.params = params or FuseParams()
+        self.align = align
 
     def fuse_groups(self, frames, groups, eng=None):
         """``frames``: the decoded device tensors in the order of the groups' files.  Every group
-        fused by ONE ``fuse_device`` call; a group whose frames differ in size is a ``ValueError``
-        that names its files."""
+        fused by ONE ``fuse_device`` call - with ``align``, after ONE ``align.align_device`` call
+        has moved the exposures of every group onto its reference; each bracket's shifts are
+        logged under its first file name, with a warning for a shift at the search's limit.  A
+        group whose frames differ in size is a ``ValueError`` that names its files."""
         stacks, at = [], 0
         for group in groups:
             stack = frames[at:at + len(group)]
@@ -166,6 +174,17 @@ class Bracket:
                                   for n, f in zip(group, stack))
                 raise ValueError(f"the exposures of a bracket differ in size: {sizes}")
             stacks.append(stack)
+        if self.align is not None and stacks:
+            from . import align as _align
+            stacks, shifts = _align.align_device(stacks, self.align, eng)
+            for group, stack, found in zip(groups, stacks, shifts):
+                h, w = stack[0].shape[:2]
+                reach = _align.reach_for(h, w, self.align.max_bits)
+                name = os.path.basename(group[0])
+                logging.info(f"Bracket alignment of {name}: (dx, dy) = {[tuple(int(v) for v in s) for s in found]}")
+                if np.abs(found).max() >= reach:
+                    logging.warning(f"Bracket alignment of {name}: a shift at the limit of {reach} pixels - "
+                                    f"the exposures moved further than the search reaches")
         return fuse_device(stacks, self.params, eng)
 
 
@@ -180,6 +199,16 @@ def _weights(text):
     return tuple(values)
 
 
+def _bits(text):
+    try:
+        bits = int(text)
+    except ValueError:
+        bits = -1
+    if not 0 <= bits <= 7:
+        raise argparse.ArgumentTypeError(f"{text!r}: 0 .. 7 pyramid levels")
+    return bits
+
+
 def _count(text):
     try:
         k = int(text)
@@ -191,8 +220,9 @@ def _count(text):
 
 
 def add_arguments(parser):
-    """``--bracket`` and ``--bracket-weights`` of stitcher.py and features.py.  Without the flags
-    the parsed namespace is what it was (no attribute: ``bracket_of`` reads them)."""
+    """``--bracket``, ``--bracket-weights``, ``--bracket-align`` and ``--bracket-align-bits`` of
+    stitcher.py and features.py.  Without the flags the parsed namespace is what it was (no
+    attribute: ``bracket_of`` and ``align_of`` read them)."""
     parser.add_argument("--bracket", type=_count, metavar="K", default=argparse.SUPPRESS,
                         help="the directory holds exposure brackets, K (2 .. 8) consecutive files "
                              "(in sorted order) per position: each bracket is fused into one frame "
@@ -201,6 +231,13 @@ def add_arguments(parser):
     parser.add_argument("--bracket-weights", type=_weights, metavar="C,S,E", default=argparse.SUPPRESS,
                         help="--bracket: the exponents of contrast, saturation and well-exposedness "
                              "(default 1,1,1, the paper's; OpenCV's default is 1,1,0).")
+    parser.add_argument("--bracket-align", action="store_true", default=argparse.SUPPRESS,
+                        help="--bracket: the brackets were shot hand-held: the exposures of each are "
+                             "moved onto its middle one by an integer shift before they are fused "
+                             "(median threshold bitmaps, Ward 2003); the caches get _b<K>a.")
+    parser.add_argument("--bracket-align-bits", type=_bits, metavar="N", default=argparse.SUPPRESS,
+                        help="--bracket-align: at most N (0 .. 7, default 6) pyramid levels: shifts "
+                             "up to 2^(N+1) - 1 pixels are found.")
 
 
 def bracket_of(args):
@@ -208,9 +245,25 @@ def bracket_of(args):
     return getattr(args, "bracket", None)
 
 
+def align_of(args):
+    """True with ``--bracket-align``."""
+    return bool(getattr(args, "bracket_align", False))
+
+
+def cache_suffix(args):
+    """What the flags add to a cache name: nothing, ``_b<K>`` or, aligned, ``_b<K>a``."""
+    if bracket_of(args) is None:
+        return ""
+    return f"_b{bracket_of(args)}" + ("a" if align_of(args) else "")
+
+
 def check_arguments(parser, args):
     if bracket_of(args) is None and getattr(args, "bracket_weights", None) is not None:
         parser.error("--bracket-weights needs --bracket")
+    if bracket_of(args) is None and align_of(args):
+        parser.error("--bracket-align needs --bracket")
+    if not align_of(args) and getattr(args, "bracket_align_bits", None) is not None:
+        parser.error("--bracket-align-bits needs --bracket-align")
 
 
 def from_args(args):
@@ -218,4 +271,8 @@ def from_args(args):
     if bracket_of(args) is None:
         return None
     weights = getattr(args, "bracket_weights", None) or (1.0, 1.0, 1.0)
-    return Bracket(bracket_of(args), FuseParams(*weights))
+    how = None
+    if align_of(args):
+        from . import align as _align
+        how = _align.AlignParams(max_bits=getattr(args, "bracket_align_bits", 6))
+    return Bracket(bracket_of(args), FuseParams(*weights), how)

@@ -343,7 +343,8 @@ def ingest(path, shrink, decode="device", lens=None, bracket=None):
     ``bracket`` (a ``fuse.Bracket``, or the number of exposures per position): the images are
     taken in sorted file-name order instead, K consecutive files are one position's exposures
     (``fuse.group_files``), and after the one decode every group is fused into one frame by one
-    ``fuse.fuse_device`` call; the fused frames take the images' place, in group order, the lens
+    ``fuse.fuse_device`` call - after one ``align.align_device`` call when the bracket has an
+    ``align`` (hand-held brackets: decode, align, fuse, lens, shrink); the fused frames take the images' place, in group order, the lens
     correction then runs under each group's first file name: decode, fuse, lens, shrink.
     Returns uint8 [h][w][3] device tensors."""
     from . import blend as _blend
@@ -591,14 +592,13 @@ def parse_args(argv=None):
 
 def cache_name(args):
     """``<name>`` of ``matches_<name>.npz`` and ``ba_<name>.pkl``: the directory and the shrink
-    as in the reference, ``_msop`` for that detector, ``_b<K>`` with ``--bracket K``, ``_lens``
-    with ``--lens``: matches and cameras of corrected and uncorrected, fused and plain frames
-    never mix."""
+    as in the reference, ``_msop`` for that detector, ``_b<K>`` with ``--bracket K`` (``_b<K>a``
+    with ``--bracket-align``), ``_lens`` with ``--lens``: matches and cameras of corrected and
+    uncorrected, fused and plain, aligned and unaligned frames never mix."""
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
     if args.detector == "msop":
         name += "_msop"
-    if _fuse.bracket_of(args) is not None:
-        name += f"_b{_fuse.bracket_of(args)}"
+    name += _fuse.cache_suffix(args)
     if args.lens is not None:
         name += "_lens"
     return name
