@@ -15,11 +15,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PANO_LIB: another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("PANO_LIB") or os.path.join(_HERE, "libpano360_hip.so")
 
+# The PANO_X macros of include/pano360.h that the package uses, each as X; the package states them
+# nowhere else (tests/test_host_abi.py compares every one with the C compiler's value)
 MAX_TAPS = 129
 MAX_LEVELS = 8
 TAP_LEAD = 7
 TAP_PAD = 40
-# pano_ctx options (include/pano360.h)
+# pano_ctx options
 OPT_BLUR_KERNEL, OPT_OWN_PRUNE, OPT_BLUR_SEGMENTS, OPT_BLUR_LEAN, OPT_STITCH_STREAMS = 0, 1, 2, 3, 4
 OPT_STITCH_ASYNC = 5
 OPT_BLUR_SEG_LEN = 6
@@ -80,36 +82,52 @@ class StitchArgs(C.Structure):
 
 EINVAL = -1     # PANO_EINVAL
 ESOLVE = -4     # PANO_ESOLVE: pano_poisson_blend did not converge (cap or breakdown)
+EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
 # pano_seam_levels' dtype codes, the resident flood's capacity in cells (wall included)
-SEAM_DTYPES = {"uint8": 0, "int16": 1, "int32": 2, "float32": 3, "float64": 4}
+SEAM_U8, SEAM_I16, SEAM_I32, SEAM_F32, SEAM_F64 = 0, 1, 2, 3, 4
+SEAM_DTYPES = {"uint8": SEAM_U8, "int16": SEAM_I16, "int32": SEAM_I32, "float32": SEAM_F32,
+               "float64": SEAM_F64}
 SEAM_RESIDENT_CELLS = 81408
 # pano_ssc_probe's paths, the on-chip bitmap's capacity in cells
 SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
 SSC_ONCHIP_CELLS = 524288
-# pano_ba_refine: the sums per pair
+# pano_ba_refine: the sums per pair (the header states the figure in prose only)
 BA_REFINE_TERMS = 70
-EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
-# pano_mip_u8 / pano_view_render: PANO_VIEW_MAX_LEVELS, PANO_VIEW_MAX_VIEWS
+# pano_jpeg_decode: int64 fields of a descriptor row, entropy bytes per destuffing thread, bits
+# per Huffman subsequence, bytes of one lookup table
+JPEG_FIELDS = 32
+JPEG_CHUNK = 1024
+JPEG_SUBSEQ = 1024
+JPEG_HUFF_BYTES = 1424
+# pano_jpeg_encode / pano_jpeg_encode_batch: the largest side, the flag "pixels are B, G, R"
+JPEG_MAX_SIDE = 65500
+JPEG_BGR = 1
+JPEG_BATCH_MAX = 16384
+JPEG_BATCH_MAX_BLOCKS = 1 << 28
+# pano_png_filter's flag; pano_deflate: input bytes per block, the first length it refuses
+PNG_BGR = 1
+DEFLATE_CHUNK = 65536
+DEFLATE_MAX_BYTES = 1 << 34
+# pano_mip_u8 / pano_view_render: the limits, the kinds of a view
 VIEW_MAX_LEVELS = 16
 VIEW_MAX_VIEWS = 32
-# pano_median_cameras / pano_median_blend: PANO_MEDIAN_KEEP
+VIEW_MAX_SIDE = 32768
+VIEW_RECTILINEAR, VIEW_EQUIRECT, VIEW_STEREOGRAPHIC = 0, 1, 2
+# pano_median_cameras / pano_median_blend
 MEDIAN_KEEP = 32
-# pano_fill_u8: PANO_FILL_TAIL_PIXELS
+# pano_fill_u8
 FILL_TAIL_PIXELS = 4096
-# pano_jpeg_encode_batch: PANO_JPEG_BATCH_MAX, PANO_JPEG_BATCH_MAX_BLOCKS
-# pano_lens_undistort_u8: PANO_LENS_MAX_SIDE, the models and interpolations
+# pano_lens_undistort_u8: the largest side, the models and interpolations
 LENS_MAX_SIDE = 32767
 LENS_BROWN, LENS_FISHEYE = 0, 1
 LENS_CUBIC, LENS_LINEAR = 0, 1
-# pano_photo_stats / pano_photo_apply_u8: PANO_PHOTO_MAX_SIDE, PANO_PHOTO_SUMS, PANO_PHOTO_TABLE
+# pano_photo_stats / pano_photo_apply_u8
 PHOTO_MAX_SIDE = 32767
 PHOTO_SUMS = 25
 PHOTO_TABLE = 1026
-# pano_fuse_u8: PANO_FUSE_MAX_EXPOSURES, PANO_FUSE_MAX_SIDE
+# pano_fuse_u8 / pano_align_mtb
 FUSE_MAX_EXPOSURES = 8
 FUSE_MAX_SIDE = 32767
-JPEG_BATCH_MAX = 16384
-JPEG_BATCH_MAX_BLOCKS = 1 << 28
 
 
 class JpegImage(C.Structure):
@@ -203,6 +221,16 @@ class Camera(C.Structure):
                 ("sh", C.c_int32), ("sw", C.c_int32),
                 ("y0", C.c_int32), ("x0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
 
+
+# every record of include/pano360.h by its C name
+RECORDS = {
+    "pano_patch": Patch, "pano_layout": Layout, "pano_camera": Camera, "pano_pair": Pair,
+    "pano_sift_keypoint": SiftKeypoint, "pano_sift_args": SiftArgs, "pano_jpeg_image": JpegImage,
+    "pano_view": View, "pano_view_mosaic": ViewMosaic, "pano_lens_frame": LensFrame,
+    "pano_photo_frame": PhotoFrame, "pano_photo_pair": PhotoPair, "pano_photo_apply": PhotoApply,
+    "pano_fuse_stack": FuseStack, "pano_fuse_params": FuseParams, "pano_align_stack": AlignStack,
+    "pano_align_params": AlignParams, "pano_stitch_args": StitchArgs,
+}
 
 _vp, _i = C.c_void_p, C.c_int
 _SIGNATURES = {
@@ -409,6 +437,16 @@ def _engine(eng):
     """``eng``, or the process's engine."""
     from . import engine
     return eng or engine.engine()
+
+
+def is_u8(x):
+    """Whether a host array or a tensor holds uint8."""
+    return str(x.dtype) in ("uint8", "torch.uint8")
+
+
+def is_rgb_u8(img):
+    """Whether a host array or a tensor is uint8 [h][w][3], what ``rgb_on_device`` takes."""
+    return is_u8(img) and len(img.shape) == 3 and img.shape[2] == 3
 
 
 def rgb_on_device(img, eng):

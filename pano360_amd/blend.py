@@ -266,7 +266,7 @@ def poisson_blend(img_source, img_target, img_mask):
 
 
 # ---------------------------------------------------------------- seam (graph_cut, alpha_blend)
-_SEAM_TYPES = ("uint8", "int16", "int32", "float32", "float64")
+_SEAM_TYPES = tuple(_lib.SEAM_DTYPES)
 
 
 def seam_border(shrink):

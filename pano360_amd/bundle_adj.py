@@ -22,6 +22,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import _lib
+
 
 def _zero_range():
     return (np.zeros(2), np.zeros(2))
@@ -369,7 +371,6 @@ class _Device:
 
     def pair_ssq(self, pairs_dev, n_pairs, homs):
         """Per-pair sums of squared residuals (pano_ba_residuals), on the device."""
-        from . import _lib
         from . import engine as _eng
         hom = self.upload(homs.reshape(n_pairs, 9), np.float64)
         ssq = self.torch.empty(n_pairs, dtype=self.torch.float64, device=self.dev)
@@ -380,7 +381,6 @@ class _Device:
 
     def normal(self, pairs_dev, n_pairs, slot_dev, n_active, jtab, hom_r, work):
         """(J^T J + LM_LAMBDA I, J^T r) on the device (pano_ba_normal)."""
-        from . import _lib
         from . import engine as _eng
         torch = self.torch
         tab = self.upload(np.concatenate([jtab.reshape(-1), hom_r.reshape(-1)]), np.float64)
@@ -560,7 +560,7 @@ def traverse(imgs, matches, badjust="incr", use_straighten=True):
 
 
 # ------------------------------------------------------------------ robust refinement
-REFINE_TERMS = 70           # pano_ba_refine's sums per pair (include/pano360.h)
+REFINE_TERMS = _lib.BA_REFINE_TERMS     # pano_ba_refine's sums per pair
 REFINE_LOCAL = 10           # a pair's local parameters: f_b, omega_b, f_a, omega_a, k1, k2
 REFINE_LAMBDA = 1e-3        # the first damping; / 10 after a step that is taken, * 10 otherwise
 REFINE_LAMBDA_MAX = 1e12
@@ -647,8 +647,6 @@ class _Refiner:
     one wait each."""
 
     def __init__(self, pairs, n, huber):
-        from . import _lib
-        self._lib = _lib
         self.dev = _Device(n)
         self.n, self.huber = n, float(huber)
         firsts = [self.dev.append(rows) for _, _, rows in pairs]
@@ -665,7 +663,7 @@ class _Refiner:
         dev = self.dev
         cams = dev.upload(np.concatenate([f[:, None], pp, R.reshape(self.n, 9)], axis=1),
                           np.float64)
-        self._lib.check(dev.eng.lib.pano_ba_refine(
+        _lib.check(dev.eng.lib.pano_ba_refine(
             dev.eng.ctx(), _eng._ptr(dev.rows), dev.n_rows, _eng._ptr(self.pairs), self.n_pairs,
             _eng._ptr(cams), self.n, C.c_double(k[0]), C.c_double(k[1]), C.c_double(self.huber),
             _eng._ptr(self.out)), "pano_ba_refine")

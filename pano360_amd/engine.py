@@ -332,17 +332,9 @@ def _torch():
 
 
 # numpy mirrors of the C records (include/pano360.h), for building tables in bulk
-PATCH_DTYPE = np.dtype([(k, "<u8") for k in ("planes", "mask", "blurred", "scratch")]
-                       + [(k, "<i4") for k in ("y0", "x0", "h", "w", "vy0", "vx0", "vh", "vw",
-                                               "ay0", "ax0", "ah", "aw", "vpitch", "apitch",
-                                               "index", "tiles_off")])
-CAMERA_DTYPE = np.dtype([("proj", "<f8", (9,)), ("frame", "<u8"), ("hat_x", "<u8"),
-                         ("hat_y", "<u8")]
-                        + [(k, "<i4") for k in ("sh", "sw", "y0", "x0", "h", "w")])
-PAIR_DTYPE = np.dtype([("minv", "<f8", (9,)), ("i", "<i4"), ("j", "<i4")])
-assert PAIR_DTYPE.itemsize == C.sizeof(_lib.Pair) == 80
-assert PATCH_DTYPE.itemsize == C.sizeof(Patch) == 96
-assert CAMERA_DTYPE.itemsize == C.sizeof(_lib.Camera) == 120
+PATCH_DTYPE = np.dtype(Patch)
+CAMERA_DTYPE = np.dtype(_lib.Camera)
+PAIR_DTYPE = np.dtype(_lib.Pair)
 
 
 class _PinnedRing:

@@ -197,9 +197,8 @@ def sift_pyramid_device(frame, n_octaves=None, sigma=SIFT_SIGMA, layers=SIFT_LAY
 SIFT_CONTRAST = 0.04        # cv2.xfeatures2d.SIFT_create() defaults
 SIFT_EDGE = 10.0
 SIFT_FIRST_OCTAVE = -1
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                     ("response", "<f4"), ("octave", "<i4"), ("r", "<i4"), ("c", "<i4")])
-assert KP_DTYPE.itemsize == C.sizeof(_lib.SiftKeypoint) == 32
+KP_DTYPE = np.dtype(_lib.SiftKeypoint)
+KP_BYTES = KP_DTYPE.itemsize
 
 
 class KeyPoint:
@@ -320,11 +319,11 @@ class SiftDetection:
             # behind the next frame's kernels.  One staging buffer per engine: the lock keeps
             # two results of this engine from sharing it
             with self.host.lock:
-                pinned = self.host.staging(n_out * 32)
+                pinned = self.host.staging(n_out * KP_BYTES)
                 with torch.cuda.stream(self.host.side):   # pinned: a DMA, no staging kernel
-                    pinned[:n_out * 32].copy_(self.kpts[:n_out * 32], non_blocking=True)
+                    pinned[:n_out * KP_BYTES].copy_(self.kpts[:n_out * KP_BYTES], non_blocking=True)
                 self.host.side.synchronize()
-                kps = pinned[:n_out * 32].numpy().view(KP_DTYPE).copy()
+                kps = pinned[:n_out * KP_BYTES].numpy().view(KP_DTYPE).copy()
             desc = self.desc[:n_out]
             if self.owned:
                 desc = desc.clone()
@@ -386,8 +385,8 @@ class SiftPipeline:
         ws["work"] = torch.empty(5 * self.h * self.w, **f32)
         ws["frame"] = torch.empty((self.h, self.w, 3), dtype=torch.uint8, device=dev)
         n = self.max_keypoints
-        ws["cands"] = torch.empty(n * 32, dtype=torch.uint8, device=dev)
-        ws["kpts"] = torch.empty(n * 32, dtype=torch.uint8, device=dev)
+        ws["cands"] = torch.empty(n * KP_BYTES, dtype=torch.uint8, device=dev)
+        ws["kpts"] = torch.empty(n * KP_BYTES, dtype=torch.uint8, device=dev)
         ws["counts"] = torch.zeros(3, dtype=torch.int32, device=dev)
         ws["sort"] = torch.empty(int(eng.lib.pano_sift_sort_work_bytes(n)), dtype=torch.uint8,
                                  device=dev)
@@ -498,8 +497,8 @@ def sift_detect_async(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
     gptr_host[:len(gauss)] = [g.data_ptr() for g in gauss]
     dims = eng.to_device(dims_host.reshape(-1)).view(torch.int32)
     gptr = eng.to_device(gptr_host).view(torch.int64)
-    cands = torch.empty(max_keypoints * 32, dtype=torch.uint8, device=dev)
-    kpts = torch.empty(max_keypoints * 32, dtype=torch.uint8, device=dev)
+    cands = torch.empty(max_keypoints * KP_BYTES, dtype=torch.uint8, device=dev)
+    kpts = torch.empty(max_keypoints * KP_BYTES, dtype=torch.uint8, device=dev)
     counts = torch.zeros(3, dtype=torch.int32, device=dev)    # candidates, keypoints, kept
     for o, diff in enumerate(dog):
         _, oh, ow = diff.shape

@@ -67,7 +67,7 @@ def _check_stack(i, stack):
         raise ValueError(f"stack {i}: {len(stack)} exposures (2 .. {MAX_EXPOSURES})")
     for e, frame in enumerate(stack):
         shape = tuple(frame.shape)
-        if len(shape) != 3 or shape[2] != 3 or str(frame.dtype) not in ("uint8", "torch.uint8"):
+        if not _lib.is_rgb_u8(frame):
             raise ValueError(f"stack {i}, exposure {e}: {frame.dtype} {shape}, not uint8 [h][w][3]")
         if shape != tuple(stack[0].shape):
             raise ValueError(f"stack {i}: exposure {e} is {shape[1]} x {shape[0]}, exposure 0 "

@@ -20,6 +20,8 @@ import re
 
 import numpy as np
 
+from . import _lib
+
 # natural-order index of the k-th zigzag coefficient (ITU-T T.81 figure A.6)
 ZIGZAG = np.array([
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5,
@@ -33,14 +35,15 @@ ZIGZAG = np.array([
  JD_DATA_OFF, JD_DATA_LEN, JD_TAB_OFF, JD_CHUNK0, JD_INT0, JD_SUB0, JD_BLK0, JD_PIX0,
  JD_DST_OFF, JD_PLANE0, JD_PLANE1, JD_PLANE2, JD_PITCH0, JD_PITCH1, JD_PITCH2, JD_OUT_OFF,
  JD_COMP_U, JD_SAMP, JD_TABSEL) = range(30)
-JD_FIELDS = 32
+JD_FIELDS = _lib.JPEG_FIELDS
 # batch row (after the n image rows): totals and the scratch arrays' offsets in `work`
 (JB_N, JB_CHUNKS, JB_INTS, JB_SUBS, JB_BLOCKS, JB_PIXELS, JB_OUT_BYTES, JB_W_KEPT, JB_W_RST,
  JB_W_KEPTX, JB_W_RSTX, JB_W_DSTLEN, JB_W_ISTART, JB_W_IEND, JB_W_INSUB, JB_W_ISUBX, JB_W_STATE0,
  JB_W_STATE1, JB_W_CNTX, JB_W_FLAG, JB_W_COEF, JB_WORK_BYTES, JB_PACKED_BYTES) = range(23)
-CHUNK = 1024            # raw entropy bytes per destuffing thread
-SUBSEQ = 1024           # bits per Huffman subsequence
-HUFF_BYTES = 1424       # one lookup table: fast[512] u16, maxcode[18] i32, valoff[18] i32, vals[256]
+CHUNK = _lib.JPEG_CHUNK             # raw entropy bytes per destuffing thread
+SUBSEQ = _lib.JPEG_SUBSEQ           # bits per Huffman subsequence
+# one lookup table: fast[512] u16, maxcode[18] i32, valoff[18] i32, vals[256]
+HUFF_BYTES = _lib.JPEG_HUFF_BYTES
 TAB_BYTES = 8 * HUFF_BYTES + 4 * 64 * 2     # 4 DC + 4 AC tables, then 4 quantisation tables
 # Quantisers above 255 (16-bit DQT tables) go to Pillow: with them the dequantised coefficients
 # can leave 16 bits, where libjpeg-turbo's C IDCT (64-bit) and its SIMD IDCT (16-bit products,
@@ -435,7 +438,6 @@ def decode_device(blobs, eng=None, want_coefs=False, _headers=None):
     also returns each image's coefficients (int16 [blocks][64], natural order, DC prediction
     applied, in MCU block order)."""
     import torch
-    from . import _lib
     from . import engine as _eng
     eng = _lib._engine(eng)
     headers = _headers or [parse(b) for b in blobs]
@@ -495,7 +497,6 @@ def read_images(paths, eng=None, max_packed=BATCH_PACKED, max_work=BATCH_WORK,
     ``plan_batches`` cuts to the budgets) or "pillow" (everything else, and a JPEG that fits no
     batch, exactly as before)."""
     import torch
-    from . import _lib
     eng = _lib._engine(eng)
     blobs, headers = [], []
     for p in paths:
@@ -560,7 +561,7 @@ STD_AC_CHROMA = ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77], bytes([
     0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7,
     0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA]))
 # libjpeg's JPEG_MAX_DIMENSION: a larger side goes to Pillow (which then refuses it, as today)
-MAX_ENCODE_SIDE = 65500
+MAX_ENCODE_SIDE = _lib.JPEG_MAX_SIDE
 # Pillow's ``subsampling`` values -> luma (h, v) sampling; the chroma is 1x1
 SUBSAMPLING = {-1: (2, 2), 2: (2, 2), 1: (2, 1), 0: (1, 1)}
 # the extensions Pillow saves as JPEG (``Image.registered_extensions()``; ".jif" is not one)
@@ -603,7 +604,7 @@ def encode_header(width, height, quality=75, subsampling=-1):
 def encodable(img, quality=75, subsampling=-1):
     """Whether ``encode_device`` covers the image and the settings (else Pillow does)."""
     shape = tuple(img.shape)
-    return (str(img.dtype) in ("uint8", "torch.uint8") and len(shape) == 3 and shape[2] == 3
+    return (_lib.is_rgb_u8(img)
             and 1 <= shape[0] <= MAX_ENCODE_SIDE and 1 <= shape[1] <= MAX_ENCODE_SIDE
             and isinstance(quality, (int, np.integer)) and 1 <= quality <= 100
             and subsampling in SUBSAMPLING)
@@ -615,7 +616,6 @@ def _encode_setup(images, quality, subsampling, order, eng, numbered):
     calls' flags, subsampling and quantiser table, ``scratch(nbytes)`` (a fresh device tensor, the
     calls' arguments for it) and ``to_file(h, w, address, nbytes)`` (header, stream, EOI)."""
     import torch
-    from . import _lib
     if order not in ("bgr", "rgb"):
         raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
     for i, img in enumerate(images):
@@ -627,7 +627,7 @@ def _encode_setup(images, quality, subsampling, order, eng, numbered):
         return None
     eng = _lib._engine(eng)
     qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
-    settings = (int(order == "bgr"), 2 if subsampling == -1 else subsampling,
+    settings = (_lib.JPEG_BGR if order == "bgr" else 0, 2 if subsampling == -1 else subsampling,
                 qt.ctypes.data_as(C.c_void_p))
 
     def scratch(nbytes):
@@ -650,7 +650,6 @@ def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_c
     ``want_coefs`` also returns the quantised blocks (int16 [blocks][64] device tensor, natural
     order, DC not differenced, MCU order).  Raises ValueError for what ``encodable`` rejects."""
     import torch
-    from . import _lib
     eng, settings, scratch, to_file = _encode_setup([img], quality, subsampling, order, eng, False)
     img = _lib.rgb_on_device(img, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
@@ -680,7 +679,6 @@ def plan_encode_batches(blocks, max_work=BATCH_WORK, work_bytes=None):
     each within ``max_work`` scratch bytes (``work_bytes(blocks, n)``, by default
     ``pano_jpeg_encode_batch_work_bytes``), ``JPEG_BATCH_MAX`` images and
     ``JPEG_BATCH_MAX_BLOCKS`` blocks.  Raises ValueError for an image that fits no call alone."""
-    from . import _lib
     if work_bytes is None:
         native = _lib.lib().pano_jpeg_encode_batch_work_bytes
         work_bytes = lambda b, n: int(native(C.c_int64(b), n))       # noqa: E731
@@ -712,7 +710,6 @@ def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=Non
     together and waits on the stream twice and downloads once, however many they are.  An empty
     list gives [].  Raises ValueError, before anything is queued, for an image ``encodable``
     rejects."""
-    from . import _lib
     images = list(images)
     setup = _encode_setup(images, quality, subsampling, order, eng, True)
     if setup is None:

@@ -235,7 +235,7 @@ def undistort_device(frames, models, interp="cubic", focal=None, eng=None):
         raise ValueError(f"interp {interp!r}: 'cubic' or 'linear'")
     for i, (frame, model) in enumerate(zip(frames, models)):
         shape = tuple(frame.shape)
-        if len(shape) != 3 or shape[2] != 3 or str(frame.dtype) not in ("uint8", "torch.uint8"):
+        if not _lib.is_rgb_u8(frame):
             raise ValueError(f"frame {i}: {frame.dtype} {shape}, not uint8 [h][w][3]")
         if (shape[1], shape[0]) != model.size:
             raise ValueError(f"frame {i} is {shape[1]} x {shape[0]}, its calibration holds for "

@@ -121,7 +121,7 @@ def default_step(shapes):
 # -------------------------------------------------------------- the statistics
 def _check_frame(i, frame):
     shape = tuple(frame.shape)
-    if len(shape) != 3 or shape[2] != 3 or str(frame.dtype) not in ("uint8", "torch.uint8"):
+    if not _lib.is_rgb_u8(frame):
         raise ValueError(f"frame {i}: {frame.dtype} {shape}, not uint8 [h][w][3]")
 
 

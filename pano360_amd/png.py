@@ -16,9 +16,9 @@ import numpy as np
 
 from . import _lib
 
-CHUNK = 65536               # input bytes per deflate block (PANO_DEFLATE_CHUNK)
+CHUNK = _lib.DEFLATE_CHUNK  # input bytes per deflate block
 MAX_SIDE = (1 << 31) - 1    # what a PNG's IHDR holds
-MAX_DEFLATE = (1 << 34) - 1     # pano_deflate's limit (PANO_DEFLATE_MAX_BYTES - 1)
+MAX_DEFLATE = _lib.DEFLATE_MAX_BYTES - 1    # pano_deflate's limit
 MAX_IDAT = (1 << 31) - 1    # a chunk's length field
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 PNG_EXTENSIONS = (".png",)
@@ -35,7 +35,7 @@ def encodable(img):
     """Whether ``encode_device`` covers the image (else Pillow does): uint8, [h][w][3], sides
     1 .. 2^31 - 1, scanlines within ``pano_deflate``'s limit."""
     shape = tuple(img.shape)
-    return (str(img.dtype) in ("uint8", "torch.uint8") and len(shape) == 3 and shape[2] == 3
+    return (_lib.is_rgb_u8(img)
             and 1 <= shape[0] <= MAX_SIDE and 1 <= shape[1] <= MAX_SIDE
             and shape[0] * (1 + 3 * shape[1]) <= MAX_DEFLATE)
 
@@ -58,7 +58,7 @@ def filter_device(img, order="bgr", eng=None):
     out = torch.empty((h, 1 + 3 * w), dtype=torch.uint8, device=img.device)
     _lib.check(eng.lib.pano_png_filter(
         eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)),
-        1 if order == "bgr" else 0, _eng._ptr(out)), "pano_png_filter")
+        _lib.PNG_BGR if order == "bgr" else 0, _eng._ptr(out)), "pano_png_filter")
     return out
 
 

@@ -17,10 +17,11 @@ import numpy as np
 
 from . import _lib
 
-RECTILINEAR, EQUIRECT, STEREOGRAPHIC = 0, 1, 2
+RECTILINEAR, EQUIRECT, STEREOGRAPHIC = (_lib.VIEW_RECTILINEAR, _lib.VIEW_EQUIRECT,
+                                        _lib.VIEW_STEREOGRAPHIC)
 MAX_LEVELS = _lib.VIEW_MAX_LEVELS
 MAX_VIEWS = _lib.VIEW_MAX_VIEWS
-MAX_SIDE = 1 << 15                  # of a view and of a mosaic (pano_view_render's limit)
+MAX_SIDE = _lib.VIEW_MAX_SIDE       # of a view and of a mosaic (pano_view_render's limit)
 CUBE_FACES = ("front", "right", "back", "left", "up", "down")
 # (right, down) of the faces in that order; forward = right x down: +z, +x, -z, -x, -y, +y
 _FACE_AXES = (((1, 0, 0), (0, 1, 0)), ((0, 0, -1), (0, 1, 0)), ((-1, 0, 0), (0, 1, 0)),
@@ -219,9 +220,9 @@ class Mips:
 
 def _check_mosaic(img):
     shape = tuple(img.shape)
-    if str(img.dtype) not in ("uint8", "torch.uint8"):
+    if not _lib.is_u8(img):
         raise ValueError(f"a mosaic of {img.dtype}: uint8")
-    if len(shape) != 3 or shape[2] != 3:
+    if not _lib.is_rgb_u8(img):
         raise ValueError(f"a mosaic of shape {shape}: [H][W][3]")
     if not (1 <= shape[0] <= MAX_SIDE and 1 <= shape[1] <= MAX_SIDE):
         raise ValueError(f"a mosaic of shape {shape}: sides 1 .. {MAX_SIDE}")

@@ -15,7 +15,6 @@ products.  Over a whole traverse that drift grew to 7e-11 in a loss and 2.8e-9 i
 entry: the latter on ring8, where the gate splits the cameras into three groups with no pair
 between them, so LM's damping alone fixes their relative rotation.  Everywhere else rotations
 agreed to 1e-12 and focals to 2e-13."""
-import ctypes
 import glob
 import os
 import sys
@@ -147,16 +146,6 @@ def test_idx_to_keypoints_round_trips_a_match_file(tmp_path):
             assert np.array_equal(rows[:, 3:5], kpts[q][mm[:, 1]])
             assert np.all(rows[:, [2, 5]] == 1.0)
             assert np.array_equal(hom, hh)
-
-
-def test_bundle_symbols_have_signatures():
-    from pano360_amd import _lib
-    for name in ("pano_ba_work_bytes", "pano_ba_residuals", "pano_ba_normal"):
-        assert name in _lib.EXPORTS
-    res, args = _lib._SIGNATURES["pano_ba_normal"]
-    assert res is ctypes.c_int and len(args) == 12 and args[8] is ctypes.c_double
-    assert len(_lib._SIGNATURES["pano_ba_residuals"][1]) == 6
-    assert _lib._SIGNATURES["pano_ba_work_bytes"][0] is ctypes.c_size_t
 
 
 # ------------------------------------------------------------------ the ordered model

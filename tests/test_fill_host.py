@@ -2,7 +2,6 @@
 fill must have, the host side of pano360_amd/fill.py (levels, workspace, bindings), the stitcher's
 --fill flag, and the condition on the inputs of tests/test_gpu_fill.py."""
 import os
-import re
 import subprocess
 import tempfile
 
@@ -124,23 +123,8 @@ def test_native_layout_equals_the_python_one():
 
 
 def test_header_and_binding_agree():
-    header = open(os.path.join(ROOT, "include", "pano360.h")).read()
-    assert int(re.search(r"#define PANO_FILL_TAIL_PIXELS (\d+)", header).group(1)) \
-        == _lib.FILL_TAIL_PIXELS == fill.TAIL_PIXELS
-    assert int(re.search(r"#define PANO_VIEW_MAX_SIDE (\d+)", header).group(1)) == view.MAX_SIDE
-    c_types = {"pano_ctx *": "c_void_p", "const uint8_t *": "c_void_p", "uint8_t *": "c_void_p",
-               "int64_t ": "c_long", "int ": "c_int"}
-    for name in ("pano_fill_u8", "pano_select_u8"):
-        assert name in _lib.EXPORTS
-        decl = re.search(rf"\nint {name}\(([^;]*)\);", header).group(1)
-        params = [" ".join(p.split()) for p in decl.split(",")]
-        kinds = []
-        for p in params:
-            kind = next(v for k, v in c_types.items() if p.startswith(k))
-            kinds.append(kind)
-        res, args = _lib._SIGNATURES[name]
-        assert res.__name__ == "c_int"
-        assert [a.__name__ for a in args] == kinds, (name, params)
+    assert fill.TAIL_PIXELS == _lib.FILL_TAIL_PIXELS and view.MAX_SIDE == _lib.VIEW_MAX_SIDE
+    assert {"pano_fill_u8", "pano_select_u8"} <= set(_lib.EXPORTS)
 
 
 # ------------------------------------------------------------ argument checks

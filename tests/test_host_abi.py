@@ -1,6 +1,7 @@
 """CPU: the product's host-side geometry against the golden vectors, and the
 C-ABI library: it loads and exports every symbol include/pano360.h declares
-(no compute calls - there is no GPU here)."""
+(no compute calls - there is no GPU here), and the binding (pano360_amd/_lib.py)
+states every record, prototype and constant of the header as the C compiler sees it."""
 import ctypes
 import os
 import pickle
@@ -12,10 +13,70 @@ import pytest
 from conftest import ROOT, SCENES, load_golden, n_patches, scene_inputs
 
 
+HEADER = os.path.join(ROOT, "include", "pano360.h")
+# a prototype's result and scalar parameters: the C type and the ctypes type that passes it
+RESULTS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+           "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+# the PANO_* macros _lib.py does not mirror, and why
+UNMIRRORED = {
+    "PANO_OK": "_lib.check compares a status with 0",
+    "PANO_EHIP": "a failure like any other: _lib.check raises on every status but 0",
+    "PANO_ELIMIT": "as PANO_EHIP",
+    "PANO_OPT_COUNT": "the library bounds the option index itself",
+    "PANO_INTERIOR_BLOCK": "a build may override it: the engine asks pano_interior_block()",
+    "PANO_POISSON_CHUNK": "the library's own batching of the solver's iterations",
+    "PANO_SEAM_BATCH": "the library's own batching of the tiled flood's rounds",
+    "PANO_MSOP_SMOOTH_TAPS": "the library checks the aperture; the package states no limit",
+}
+# sizes and offsets pinned to literals, so that the header and the binding cannot move together
+PINNED = {
+    "pano_patch": 96, "pano_camera": 120, "pano_pair": 80, "pano_sift_keypoint": 32,
+    "pano_jpeg_image": 24, "pano_lens_frame": 128,
+    "pano_photo_frame": 24, "pano_photo_pair": 80, "pano_photo_apply": 48,
+    "pano_view": 136, "pano_view.image": 104, "pano_view.kind": 120,
+    "pano_view_mosaic": 48, "pano_view_mosaic.h": 32,
+    "pano_fuse_stack": 176, "pano_fuse_stack.dst": 128, "pano_fuse_stack.w": 160,
+    "pano_fuse_params": 16, "pano_fuse_params.n_levels": 12,
+    "pano_align_stack": 312, "pano_align_stack.dst": 128, "pano_align_stack.shifts": 256,
+    "pano_align_stack.w": 296, "pano_align_params": 8, "pano_align_params.exclude": 4,
+}
+
+
+@pytest.fixture(scope="session")
+def abi(tmp_path_factory):
+    """What include/pano360.h declares, read off its text without the comments, and what the C
+    compiler makes of it: one generated program prints every record's size, every field's offset
+    and size and every macro's value.  ``records`` {typedef: field names in order}, ``protos``
+    [(result type, name, parameters)], ``macros`` [names], ``seen`` {what: the printed numbers}."""
+    import subprocess
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    records = {name: re.findall(r"(\w+)\s*(?:\[[^\]]*\])?\s*[,;]", body)
+               for body, name in re.findall(r"typedef struct \w+ \{(.*?)\} (\w+);", text, flags=re.S)}
+    protos = [(" ".join(res.split()), name, [" ".join(p.split()) for p in params.split(",")])
+              for res, name, params in re.findall(r"\n((?:const )?\w+ \*?)(pano_\w+)\(([^)]*)\);", text)]
+    macros = re.findall(r"#define (PANO_\w+)", text)
+    body = []
+    for rec, fields in records.items():
+        body.append(f'printf("{rec} %zu\\n", sizeof({rec}));')
+        body += [f'printf("{rec}.{f} %zu %zu\\n", __builtin_offsetof({rec}, {f}), '
+                 f'sizeof((({rec} *)0)->{f}));' for f in fields]
+    body += [f'printf("{m} %lld\\n", (long long)({m}));' for m in macros]
+    tmp = tmp_path_factory.mktemp("abi")
+    src, exe = str(tmp / "abi.c"), str(tmp / "abi")
+    with open(src, "w") as fid:
+        fid.write('#include <stdio.h>\n#include "pano360.h"\nint main(void)\n{\n'
+                  + "\n".join(body) + "\nreturn 0;\n}\n")
+    subprocess.check_call(["gcc", "-I", os.path.dirname(HEADER), src, "-o", exe])
+    seen = {line.split()[0]: [int(v) for v in line.split()[1:]]
+            for line in subprocess.check_output([exe], text=True).splitlines()}
+    return {"records": records, "protos": protos, "macros": macros, "seen": seen}
+
+
 def test_library_exports_every_declared_symbol():
     from pano360_amd import _lib
     _lib.build()
-    header = open(os.path.join(ROOT, "include", "pano360.h")).read()
+    header = open(HEADER).read()
     declared = set(re.findall(r"\b(pano_[a-z0-9_]+)\s*\(", header))
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     handle = ctypes.CDLL(_lib.LIB_PATH)
@@ -24,41 +85,63 @@ def test_library_exports_every_declared_symbol():
     handle.pano_version.restype = ctypes.c_char_p
     assert b"gfx950" in handle.pano_version()
     assert handle.pano_pitch(1941) == 1944
-    # record sizes against the C compiler's view of the header
-    import subprocess
-    import tempfile
-    with tempfile.TemporaryDirectory() as tmp:
-        src = os.path.join(tmp, "sz.c")
-        with open(src, "w") as fid:
-            fid.write('#include <stdio.h>\n#include "pano360.h"\nint main(void){'
-                      'printf("%zu %zu %zu %zu %zu %zu", sizeof(pano_patch), sizeof(pano_camera), '
-                      'sizeof(pano_pair), sizeof(pano_stitch_args), sizeof(pano_layout), '
-                      '__builtin_offsetof(pano_stitch_args, layout));'
-                      'printf(" %zu %zu %zu %zu %zu", sizeof(pano_sift_args), '
-                      '__builtin_offsetof(pano_sift_args, detect), '
-                      '__builtin_offsetof(pano_sift_args, first_octave), '
-                      '__builtin_offsetof(pano_sift_args, gauss_dev), '
-                      '__builtin_offsetof(pano_sift_args, desc));return 0;}')
-        exe = os.path.join(tmp, "sz")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert sizes[:3] == [ctypes.sizeof(_lib.Patch), ctypes.sizeof(_lib.Camera),
-                         ctypes.sizeof(_lib.Pair)] == [96, 120, 80]
-    # the argument record of pano_stitch_multiband, field for field
-    assert sizes[3:6] == [ctypes.sizeof(_lib.StitchArgs), ctypes.sizeof(_lib.Layout),
-                          _lib.StitchArgs.layout.offset]
-    # ... and of pano_sift_detect
-    A = _lib.SiftArgs
-    assert sizes[6:] == [ctypes.sizeof(A), A.detect.offset, A.first_octave.offset,
-                         A.gauss_dev.offset, A.desc.offset]
 
 
-def test_header_constants_match_binding():
+def test_records_match_the_header(abi):
+    """Every record of the header is in ``_lib.RECORDS``, with the header's field names in the
+    header's order, and the compiler's size, field offsets and field sizes are ctypes'."""
     from pano360_amd import _lib
-    header = open(os.path.join(ROOT, "include", "pano360.h")).read()
-    for macro, value in (("PANO_MAX_TAPS", _lib.MAX_TAPS), ("PANO_MAX_LEVELS", _lib.MAX_LEVELS),
-                         ("PANO_TAP_LEAD", _lib.TAP_LEAD), ("PANO_TAP_PAD", _lib.TAP_PAD)):
-        assert int(re.search(rf"#define {macro} (\d+)", header).group(1)) == value
+    records, seen = abi["records"], abi["seen"]
+    assert set(records) == set(_lib.RECORDS), set(records) ^ set(_lib.RECORDS)
+    assert len(set(_lib.RECORDS.values())) == len(_lib.RECORDS)
+    for rec, fields in records.items():
+        cls = _lib.RECORDS[rec]
+        assert [f for f, _ in cls._fields_] == fields, rec
+        assert seen[rec] == [ctypes.sizeof(cls)], rec
+        for f, kind in cls._fields_:
+            assert seen[f"{rec}.{f}"] == [getattr(cls, f).offset, ctypes.sizeof(kind)], f"{rec}.{f}"
+    for what, value in PINNED.items():
+        assert seen[what][0] == value, what
+
+
+def test_signatures_match_the_header(abi):
+    """Every prototype of the header against ``_lib._SIGNATURES``: the result, the arity, a ctypes
+    pointer for every pointer or array (to the record's class where it is typed), and for every
+    scalar the ctypes type of its C type.  A C type this test does not know fails."""
+    from pano360_amd import _lib
+    assert sorted(name for _, name, _ in abi["protos"]) == sorted(_lib._SIGNATURES)
+    for result, name, params in abi["protos"]:
+        res, args = _lib._SIGNATURES[name]
+        assert result in RESULTS, f"{name}: result {result!r} is not a type this test knows"
+        assert res is RESULTS[result], f"{name}: result {result!r} bound as {res.__name__}"
+        params = [] if params == ["void"] else params
+        assert len(args) == len(params), f"{name}: {len(params)} parameters, {len(args)} bound"
+        for k, (param, arg) in enumerate(zip(params, args)):
+            where = f"{name}: parameter {k} {param!r} bound as {arg.__name__}"
+            base = re.match(r"(?:const )?(\w+)", param).group(1)
+            if "*" in param or "[" in param:
+                typed = issubclass(arg, ctypes._Pointer)
+                assert typed or arg in (ctypes.c_void_p, ctypes.c_char_p), where
+                if typed and base in _lib.RECORDS:
+                    assert arg._type_ is _lib.RECORDS[base], where
+            else:
+                assert re.fullmatch(r"(?:const )?\w+ \w+", param) and base in SCALARS, \
+                    f"{name}: parameter {k} {param!r} is not of a type this test knows"
+                assert arg is SCALARS[base], where
+
+
+def test_constants_match_the_header(abi):
+    """Every PANO_X macro, as the compiler evaluates it, equals ``_lib.X`` or is listed in
+    UNMIRRORED with the reason; a macro that is neither fails."""
+    from pano360_amd import _lib
+    assert not set(UNMIRRORED) - set(abi["macros"]), set(UNMIRRORED) - set(abi["macros"])
+    for macro in abi["macros"]:
+        short = macro[len("PANO_"):]
+        if macro in UNMIRRORED:
+            assert not hasattr(_lib, short), f"{macro} is mirrored: take it off UNMIRRORED"
+        else:
+            assert hasattr(_lib, short), f"{macro} is neither _lib.{short} nor in UNMIRRORED"
+            assert getattr(_lib, short) == abi["seen"][macro][0], macro
 
 
 def test_no_product_import_of_the_oracle():

@@ -1,17 +1,13 @@
 """CPU: the host side of the lens correction (pano360_amd/lens.py) - the focal length fit, the
-calibration files, the command lines, the record's layout - and the conditions tests/lens_cases.py
+calibration files, the command lines - and the conditions tests/lens_cases.py
 must meet for tests/test_gpu_lens.py to mean what it says."""
-import ctypes
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import lens_cases
 import lens_model as lm
-from conftest import ROOT
 from pano360_amd import _lib, lens
 
 
@@ -283,21 +279,3 @@ def test_top_level_module_re_exports():
     for name in ("LensModel", "load", "fit_focal", "undistort_device", "undistort"):
         assert getattr(top, name) is getattr(lens, name)
 
-
-# ---------------------------------------------------------------------- ABI
-def test_lens_frame_layout_matches_the_header(tmp_path):
-    assert "pano_lens_undistort_u8" in _lib.EXPORTS
-    fields = [name for name, _ in _lib.LensFrame._fields_]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include "pano360.h"\nint main(void){'
-                   'printf("%zu", sizeof(pano_lens_frame));'
-                   + "".join(f'printf(" %zu", __builtin_offsetof(pano_lens_frame, {f}));' for f in fields)
-                   + 'printf(" %d %d %d %d %d", PANO_LENS_BROWN, PANO_LENS_FISHEYE, PANO_LENS_CUBIC,'
-                   ' PANO_LENS_LINEAR, PANO_LENS_MAX_SIDE);return 0;}')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)]).split()]
-    assert got[0] == ctypes.sizeof(_lib.LensFrame) == 128
-    assert got[1:1 + len(fields)] == [getattr(_lib.LensFrame, f).offset for f in fields]
-    assert got[1 + len(fields):] == [_lib.LENS_BROWN, _lib.LENS_FISHEYE, _lib.LENS_CUBIC,
-                                     _lib.LENS_LINEAR, _lib.LENS_MAX_SIDE]

@@ -1,11 +1,8 @@
 """CPU: the view stage's host side (pano360_amd/view.py, the stitcher's --view / --equirect /
 --cube flags) and its float64 model (tests/view_model.py) against brute force and identities."""
-import ctypes
 import math
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -166,23 +163,12 @@ def test_view_records_fill_the_abi_structures():
     for rec, v in zip(table, views):
         assert (rec.kind, rec.w, rec.h) == (v.kind, v.w, v.h)
         assert np.array_equal(np.array(rec.m[:]).reshape(3, 3), v.mat) and tuple(rec.p) == v.params
-    # the records against the C compiler's view of the header, the constants against the binding
-    with tempfile.TemporaryDirectory() as tmp:
-        src, exe = os.path.join(tmp, "sz.c"), os.path.join(tmp, "sz")
-        with open(src, "w") as fid:
-            fid.write('#include <stdio.h>\n#include "pano360.h"\nint main(void){'
-                      'printf("%zu %zu %zu %zu %zu", sizeof(pano_view), sizeof(pano_view_mosaic), '
-                      '__builtin_offsetof(pano_view, image), __builtin_offsetof(pano_view, kind), '
-                      '__builtin_offsetof(pano_view_mosaic, h));return 0;}')
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert sizes == [ctypes.sizeof(_lib.View), ctypes.sizeof(_lib.ViewMosaic), _lib.View.image.offset,
-                     _lib.View.kind.offset, _lib.ViewMosaic.h.offset] == [136, 48, 104, 120, 32]
+    # the module's names are the binding's constants, and the model's
+    assert (view.MAX_LEVELS, view.MAX_VIEWS, view.MAX_SIDE) == (
+        _lib.VIEW_MAX_LEVELS, _lib.VIEW_MAX_VIEWS, _lib.VIEW_MAX_SIDE)
+    assert (view.RECTILINEAR, view.EQUIRECT, view.STEREOGRAPHIC) == (
+        _lib.VIEW_RECTILINEAR, _lib.VIEW_EQUIRECT, _lib.VIEW_STEREOGRAPHIC)
     header = open(os.path.join(ROOT, "include", "pano360.h")).read()
-    for macro, value in (("PANO_VIEW_MAX_LEVELS", _lib.VIEW_MAX_LEVELS), ("PANO_VIEW_MAX_VIEWS", _lib.VIEW_MAX_VIEWS),
-                         ("PANO_VIEW_MAX_SIDE", view.MAX_SIDE), ("PANO_VIEW_RECTILINEAR", view.RECTILINEAR),
-                         ("PANO_VIEW_EQUIRECT", view.EQUIRECT), ("PANO_VIEW_STEREOGRAPHIC", view.STEREOGRAPHIC)):
-        assert int(re.search(rf"#define {macro} (\d+)", header).group(1)) == value
     assert vm.MAX_LEVELS == view.MAX_LEVELS
     assert (vm.RECTILINEAR, vm.EQUIRECT, vm.STEREOGRAPHIC) == (view.RECTILINEAR, view.EQUIRECT, view.STEREOGRAPHIC)
     for name in ("pano_mip_u8", "pano_view_render"):
