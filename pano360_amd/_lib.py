@@ -11,6 +11,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PANO_LIB: another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("PANO_LIB") or os.path.join(_HERE, "libpano360_hip.so")
@@ -358,6 +360,11 @@ _SIGNATURES = {
     "pano_stitch_verify": (_i, [_vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
+# the exports whose int result is a value, not a status: ``call`` refuses them (and whatever
+# returns no int); they are called through ``lib()``
+VALUE_RESULTS = frozenset((
+    "pano_device_count", "pano_pitch", "pano_interior_block", "pano_kernel_count",
+    "pano_blur_tile_grid", "pano_overlap_blocks", "pano_sift_detect_replaying"))
 
 
 def sources_digest():
@@ -455,7 +462,6 @@ def rgb_on_device(img, eng):
     host array is uploaded (a read-only one is copied first: torch wraps writable memory only); a
     tensor is copied only when its strides are not like that, so a crop view of a dense image is
     returned as it is, the same object when it is on the device already."""
-    import numpy as np
     import torch
     if not isinstance(img, torch.Tensor):
         img = np.ascontiguousarray(img)
@@ -470,3 +476,47 @@ def check(status, what):
     if status != 0:
         msg = lib().pano_last_error().decode("utf-8", "replace")
         raise PanoError(f"{what} failed ({status}): {msg}")
+
+
+def _pointer_kinds(name, fn):
+    """Per argument of the status function ``fn``: None for a scalar, else the pointer type an
+    address is handed over as (``c_void_p``, or the ``POINTER(T)`` / ``c_char_p`` it is cast to)."""
+    if name in VALUE_RESULTS or fn.restype is not C.c_int:
+        raise TypeError(f"{name} returns a value, not a status: call it through lib()")
+    return tuple(t if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer) else None
+                 for t in fn.argtypes)
+
+
+_kinds = {}     # name -> (function, its _pointer_kinds)
+
+
+def call(name, *args, via=None):
+    """``lib().name(*args)`` with the status checked.  The function's argtypes decide what is
+    converted: in a pointer position a tensor (or a view of one) and a NumPy array become their
+    addresses, None stays a null pointer, and everything else - ctypes objects, ``byref``, plain
+    integer addresses - is passed as it is; in a scalar position an array is refused.  Nothing
+    here judges the memory behind an address (device, dtype, contiguity).  ``via``: the object
+    whose attribute ``name`` is called with the converted arguments instead (an engine's ``lib``,
+    which a caller may have wrapped); the declaration is ``lib()``'s either way."""
+    fn = getattr(lib(), name)
+    fn_kinds = _kinds.get(name)
+    if fn_kinds is None or fn_kinds[0] is not fn:
+        fn_kinds = _kinds[name] = (fn, _pointer_kinds(name, fn))
+    kinds = fn_kinds[1]
+    if len(args) != len(kinds):
+        raise TypeError(f"{name} takes {len(kinds)} arguments, {len(args)} were given")
+    args = list(args)
+    for k, kind in enumerate(kinds):
+        x = args[k]
+        if x is None or type(x) is int or type(x) is float:
+            continue
+        tensor = hasattr(x, "data_ptr")
+        if not tensor and not isinstance(x, np.ndarray):
+            continue
+        if kind is None:
+            if x.ndim > 0:
+                raise TypeError(f"{name}: argument {k} is a scalar, an array was given")
+            continue
+        address = C.c_void_p(x.data_ptr() if tensor else x.ctypes.data)
+        args[k] = address if kind is C.c_void_p else C.cast(address, kind)
+    check((fn if via is None else getattr(via, name))(*args), name)

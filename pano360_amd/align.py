@@ -117,8 +117,7 @@ def _run(stacks, params, eng, apply, want_stages):
         need += int(eng.lib.pano_align_work_bytes(h, w, k))
     work = torch.empty(need, dtype=torch.uint8, device=device)
     native = _lib.AlignParams(params.max_bits, params.exclude)
-    _lib.check(eng.lib.pano_align_mtb(eng.ctx(), records, len(stacks), C.byref(native), work.data_ptr(), need),
-               "pano_align_mtb")
+    eng.call("pano_align_mtb", records, len(stacks), C.byref(native), work, need)
     host = shifts.cpu().numpy()                         # (the one wait: the caller needs the shifts)
     out_shifts, at = [], 0
     for stack in keep:

@@ -21,12 +21,9 @@ no CPU fallback.  Outside the scope stay ``warp`` (its ``cv2.remap`` with
 ``poisson_matrix``: it returns a SciPy sparse matrix, the product does not depend on SciPy, and
 the device solver applies the same stencil straight from the mask without building a matrix.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._lib import _ptr
 from . import engine as _eng
 
 
@@ -39,7 +36,7 @@ class _Pyr:
 
     def __init__(self, eng):
         import torch
-        self.eng, self.lib, self.torch = eng, eng.lib, torch
+        self.eng, self.torch = eng, torch
 
     def _wide(self, img):
         return int(img.dtype == self.torch.float64)
@@ -48,9 +45,7 @@ class _Pyr:
         h, w, c = img.shape
         out = self.torch.empty(((h + 1) // 2, (w + 1) // 2, c), dtype=img.dtype,
                                device=img.device)
-        _lib.check(self.lib.pano_pyr_down_image(self.eng.ctx(), _ptr(img), h, w, c,
-                                                self._wide(img), _ptr(out)),
-                   "pano_pyr_down_image")
+        self.eng.call("pano_pyr_down_image", img, h, w, c, self._wide(img), out)
         return out
 
     def up(self, img, like, mode):
@@ -58,9 +53,8 @@ class _Pyr:
         sh, sw, c = img.shape
         oh, ow = like.shape[:2]
         out = self.torch.empty((oh, ow, c), dtype=img.dtype, device=img.device)
-        _lib.check(self.lib.pano_pyr_up_image(self.eng.ctx(), _ptr(img), sh, sw, c,
-                                              self._wide(img), _ptr(like), mode, _ptr(out), oh,
-                                              ow), "pano_pyr_up_image")
+        self.eng.call("pano_pyr_up_image", img, sh, sw, c, self._wide(img), like, mode, out, oh,
+                      ow)
         return out
 
     def reduce_chain(self, img, depth):
@@ -87,8 +81,7 @@ def _as_f32(eng, img):
     if img.dtype == np.uint8:
         dev = torch.from_numpy(img).to(eng.device)
         out = torch.empty(img.shape, dtype=torch.float32, device=eng.device)
-        _lib.check(eng.lib.pano_u8_to_f32(eng.ctx(), _ptr(dev), img.size, _ptr(out)),
-                   "pano_u8_to_f32")
+        eng.call("pano_u8_to_f32", dev, img.size, out)
         return out
     return torch.from_numpy(img.astype(np.float32)).to(eng.device)
 
@@ -136,13 +129,10 @@ def laplacian_blending_device(img1, img2, mask=None, n_levels=6, eng=None):
     # coarsest level first; the weight pyramid is walked from its coarsest end (blend.py:134-138)
     for first, second, weight in zip(details1, details2, reversed(weights)):
         mixed = torch.empty(first.shape, dtype=tdtype, device=eng.device)
-        _lib.check(eng.lib.pano_laplacian_mix(eng.ctx(), _ptr(first), _ptr(second), _ptr(weight),
-                                              first.numel(), int(wide), _ptr(mixed)),
-                   "pano_laplacian_mix")
+        eng.call("pano_laplacian_mix", first, second, weight, first.numel(), int(wide), mixed)
         blended = mixed if blended is None else pyr.up(blended, mixed, 2)
     out = torch.empty(blended.shape, dtype=torch.uint8, device=eng.device)
-    _lib.check(eng.lib.pano_clip_u8(eng.ctx(), _ptr(blended), blended.numel(), int(wide),
-                                    _ptr(out)), "pano_clip_u8")
+    eng.call("pano_clip_u8", blended, blended.numel(), int(wide), out)
     return out
 
 
@@ -152,8 +142,7 @@ def _dev_f32(eng, img):
     img = img.contiguous()
     if img.dtype == torch.uint8:
         out = torch.empty(img.shape, dtype=torch.float32, device=eng.device)
-        _lib.check(eng.lib.pano_u8_to_f32(eng.ctx(), _ptr(img), img.numel(), _ptr(out)),
-                   "pano_u8_to_f32")
+        eng.call("pano_u8_to_f32", img, img.numel(), out)
         return out
     return img.to(torch.float32)
 
@@ -228,11 +217,8 @@ def poisson_blend_device(src, tgt, mask, eng=None, want_solution=False,
     if bool(sel.any()):
         if want_solution:
             solution = torch.empty((c, h, w), dtype=torch.float64, device=tgt.device)
-        _lib.check(eng.lib.pano_poisson_blend(eng.ctx(), _ptr(src), _ptr(tgt), _ptr(sel), h, w, c,
-                                              POISSON_RTOL, int(max_iters), _ptr(solution),
-                                              iters.ctypes.data_as(C.c_void_p),
-                                              resid.ctypes.data_as(C.c_void_p)),
-                   "pano_poisson_blend")
+        eng.call("pano_poisson_blend", src, tgt, sel, h, w, c, POISSON_RTOL, int(max_iters),
+                 solution, iters, resid)
     elif want_solution:                            # an empty mask: the solution is the target
         solution = tgt.permute(2, 0, 1).to(torch.float64).contiguous()
     return (tgt, solution, iters, resid) if want_solution else tgt
@@ -321,8 +307,7 @@ def seam_levels_device(img1, img2, shrink, eng):
     level = torch.empty((h // shrink, w // shrink), dtype=torch.int16, device=img1.device)
     bad = torch.empty(1, dtype=torch.int32, device=img1.device)
     code = _lib.SEAM_DTYPES[_dtype_name(img1)]
-    _lib.check(eng.lib.pano_seam_levels(eng.ctx(), _ptr(img1), _ptr(img2), code, h, w, c,
-                                        int(shrink), _ptr(level), _ptr(bad)), "pano_seam_levels")
+    eng.call("pano_seam_levels", img1, img2, code, h, w, c, int(shrink), level, bad)
     return level, bad
 
 
@@ -333,8 +318,7 @@ def seam_flood_device(level, border, eng, path=0, want_stats=False):
     rows, cols = level.shape
     labels = torch.empty((rows, cols), dtype=torch.int8, device=level.device)
     stats = torch.zeros(4, dtype=torch.int32, device=level.device) if want_stats else None
-    _lib.check(eng.lib.pano_seam_flood(eng.ctx(), _ptr(level), rows, cols, border, int(path),
-                                       _ptr(labels), _ptr(stats)), "pano_seam_flood")
+    eng.call("pano_seam_flood", level, rows, cols, border, int(path), labels, stats)
     return (labels, stats) if want_stats else labels
 
 
@@ -345,8 +329,7 @@ def seam_mask_device(labels, h, w, eng):
     xtab = eng.to_device(_float_taps(w, cols))
     ytab = eng.to_device(_float_taps(h, rows))
     mask = torch.empty((h, w, 1), dtype=torch.uint8, device=labels.device)
-    _lib.check(eng.lib.pano_seam_mask(eng.ctx(), _ptr(labels), rows, cols, _ptr(xtab), _ptr(ytab),
-                                      _ptr(mask), h, w), "pano_seam_mask")
+    eng.call("pano_seam_mask", labels, rows, cols, xtab, ytab, mask, h, w)
     return mask
 
 
@@ -436,11 +419,8 @@ def alpha_blend_device(img1, img2, mask=None, eng=None):
     mask = mask.contiguous()
     strides = [0 if m == 1 else st for m, st in zip(mask.shape, mask.stride())]
     out = torch.empty((h, w, c), dtype=torch.uint8, device=img1.device)
-    _lib.check(eng.lib.pano_alpha_blend(eng.ctx(), _ptr(img1.contiguous()),
-                                        _ptr(img2.contiguous()), _lib.SEAM_DTYPES[name],
-                                        _ptr(mask), int(mask.dtype == torch.float64), strides[0],
-                                        strides[1], strides[2], h, w, c, _ptr(out)),
-               "pano_alpha_blend")
+    eng.call("pano_alpha_blend", img1.contiguous(), img2.contiguous(), _lib.SEAM_DTYPES[name], mask,
+             int(mask.dtype == torch.float64), *strides, h, w, c, out)
     return out
 
 
@@ -523,8 +503,7 @@ def shrink_device(frame, shrink, eng=None):
     else:
         xtab = eng.to_device(_resize_taps(ow, w, scale))
         ytab = eng.to_device(_resize_taps(oh, h, scale))
-    _lib.check(eng.lib.pano_resize_u8(eng.ctx(), _ptr(frame), h, w, c, _ptr(xtab), _ptr(ytab),
-                                      _ptr(out), oh, ow), "pano_resize_u8")
+    eng.call("pano_resize_u8", frame, h, w, c, xtab, ytab, out, oh, ow)
     return out
 
 

@@ -15,7 +15,6 @@ The class is importable as ``bundle_adj.Image`` through the top-level
 ``bundle_adj.py`` re-export, so ``ba_<name>.pkl`` caches written by the
 reference CLI (stitcher.py:430-439) unpickle into it unchanged.
 """
-import ctypes as C
 import heapq
 import logging
 from dataclasses import dataclass, field
@@ -371,27 +370,20 @@ class _Device:
 
     def pair_ssq(self, pairs_dev, n_pairs, homs):
         """Per-pair sums of squared residuals (pano_ba_residuals), on the device."""
-        from . import engine as _eng
         hom = self.upload(homs.reshape(n_pairs, 9), np.float64)
         ssq = self.torch.empty(n_pairs, dtype=self.torch.float64, device=self.dev)
-        _lib.check(self.eng.lib.pano_ba_residuals(self.eng.ctx(), _eng._ptr(self.rows),
-                                                  _eng._ptr(pairs_dev), n_pairs, _eng._ptr(hom),
-                                                  _eng._ptr(ssq)), "pano_ba_residuals")
+        self.eng.call("pano_ba_residuals", self.rows, pairs_dev, n_pairs, hom, ssq)
         return ssq
 
     def normal(self, pairs_dev, n_pairs, slot_dev, n_active, jtab, hom_r, work):
         """(J^T J + LM_LAMBDA I, J^T r) on the device (pano_ba_normal)."""
-        from . import engine as _eng
         torch = self.torch
         tab = self.upload(np.concatenate([jtab.reshape(-1), hom_r.reshape(-1)]), np.float64)
         n = PARAMS_PER_CAMERA * n_active
         jtj = torch.empty((n, n), dtype=torch.float64, device=self.dev)
         jtr = torch.empty(n, dtype=torch.float64, device=self.dev)
-        _lib.check(self.eng.lib.pano_ba_normal(
-            self.eng.ctx(), _eng._ptr(self.rows), _eng._ptr(pairs_dev), n_pairs,
-            _eng._ptr(slot_dev), n_active, _eng._ptr(tab),
-            C.c_void_p(tab.data_ptr() + 8 * 90 * n_pairs), C.c_double(LM_LAMBDA), _eng._ptr(work),
-            _eng._ptr(jtj), _eng._ptr(jtr)), "pano_ba_normal")
+        self.eng.call("pano_ba_normal", self.rows, pairs_dev, n_pairs, slot_dev, n_active, tab,
+                      tab.data_ptr() + 8 * 90 * n_pairs, LM_LAMBDA, work, jtj, jtr)
         return jtj, jtr
 
 
@@ -659,14 +651,11 @@ class _Refiner:
 
     def sums(self, f, pp, R, k):
         """out [n_pairs][70] at one state."""
-        from . import engine as _eng
         dev = self.dev
         cams = dev.upload(np.concatenate([f[:, None], pp, R.reshape(self.n, 9)], axis=1),
                           np.float64)
-        _lib.check(dev.eng.lib.pano_ba_refine(
-            dev.eng.ctx(), _eng._ptr(dev.rows), dev.n_rows, _eng._ptr(self.pairs), self.n_pairs,
-            _eng._ptr(cams), self.n, C.c_double(k[0]), C.c_double(k[1]), C.c_double(self.huber),
-            _eng._ptr(self.out)), "pano_ba_refine")
+        dev.eng.call("pano_ba_refine", dev.rows, dev.n_rows, self.pairs, self.n_pairs, cams, self.n,
+                     k[0], k[1], self.huber, self.out)
         return dev.download(self.out)[0].copy()
 
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Patch, _ptr
+from ._lib import Patch, _ptr   # noqa: F401  (_ptr: tests and tools make raw calls with engine._ptr)
 
 BORDER_SAMPLES = 100        # stitcher.py:109
 MULTIBAND_PAD = 10          # stitcher.py:296-297
@@ -508,10 +508,6 @@ class PatchTable:
         self.max_vw, self.max_vh, self.max_aw, self.max_ah = (mx("vw"), mx("vh"), mx("aw"),
                                                               mx("ah"))
 
-    @property
-    def ptr(self):
-        return _ptr(self.dev)
-
 
 def patch_table(patches, eng):
     """``pano_patch`` table of stage-level patches."""
@@ -537,7 +533,6 @@ class FusedPatches:
         (``pano_layout_windows``); the arenas are the engine's, grown as needed
         (``Engine.arena``).
         ``have``: uint8 [n], 0 = that camera's frame is not resident."""
-        lib = _lib.lib()
         n = len(rects)
         if rec is None:
             rec = np.zeros(n * max_spans, dtype=PATCH_DTYPE)
@@ -545,11 +540,8 @@ class FusedPatches:
         raw = np.ascontiguousarray(raw, np.int32)
         rects = np.ascontiguousarray(rects, np.int32)
         have = np.ascontiguousarray(have, np.uint8)
-        _lib.check(lib.pano_layout_windows(
-            eng.tile_grid, raw.ctypes.data, n, max_spans, rects.ctypes.data, have.ctypes.data,
-            radius,
-            strip[0], strip[1], n_blur, rec.ctypes.data, len(rec), C.byref(lay)),
-            "pano_layout_windows")
+        _lib.call("pano_layout_windows", eng.tile_grid, raw, n, max_spans, rects, have, radius,
+                  strip[0], strip[1], n_blur, rec, len(rec), C.byref(lay))
         rec = rec[:lay.n_records]
         if lay.missing:
             missing = sorted({int(i) for i in rec["index"] if not have[int(i)]})
@@ -559,9 +551,7 @@ class FusedPatches:
         self.planes = eng.arena("planes", int(lay.planes_floats))
         self.blurred = eng.arena("blurred", int(lay.blurred_floats))
         self.scratch = eng.arena("scratch", int(lay.scratch_floats))
-        _lib.check(lib.pano_layout_place(rec.ctypes.data, len(rec), self.planes.data_ptr(),
-                                         self.blurred.data_ptr(), self.scratch.data_ptr()),
-                   "pano_layout_place")
+        _lib.call("pano_layout_place", rec, len(rec), self.planes, self.blurred, self.scratch)
         self._area = self._window = None
         self.table = PatchTable.from_layout(rec, lay, eng)
         return self
@@ -633,8 +623,7 @@ class Engine:
         self._device_index = index
         handle = C.c_void_p()
         self._ctx_stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self.lib.pano_ctx_create(index, C.c_void_p(self._ctx_stream), C.byref(handle)),
-                   "pano_ctx_create")
+        _lib.call("pano_ctx_create", index, self._ctx_stream, C.byref(handle))
         self._ctx = handle
         if blur not in ("mfma", "valu"):
             raise ValueError(f"blur kernel {blur!r}: 'mfma' or 'valu'")
@@ -689,14 +678,17 @@ class Engine:
         raw = (stream.cuda_stream if stream is not None
                else _torch()._C._cuda_getCurrentRawStream(self._device_index))
         if raw != self._ctx_stream:
-            _lib.check(self.lib.pano_ctx_set_stream(self._ctx, C.c_void_p(raw)),
-                       "pano_ctx_set_stream")
+            _lib.call("pano_ctx_set_stream", self._ctx, raw)
             self._ctx_stream = raw
         return self._ctx
 
+    def call(self, name, *args):
+        """``_lib.call`` of a function whose first argument is the context, targeted at torch's
+        current stream, through ``self.lib``."""
+        _lib.call(name, self.ctx(), *args, via=self.lib)
+
     def set_option(self, option, value):
-        _lib.check(self.lib.pano_ctx_set_option(self._ctx, option, int(value)),
-                   "pano_ctx_set_option")
+        _lib.call("pano_ctx_set_option", self._ctx, option, int(value))
         if option == _lib.OPT_BLUR_KERNEL:
             self.tile_grid = int(self.lib.pano_blur_tile_grid(self._ctx))
         # an option may change how a stitch is laid out: the verified stitch a trusted repeat
@@ -705,28 +697,25 @@ class Engine:
 
     def get_option(self, option):
         value = C.c_int(0)
-        _lib.check(self.lib.pano_ctx_get_option(self._ctx, option, C.byref(value)),
-                   "pano_ctx_get_option")
+        _lib.call("pano_ctx_get_option", self._ctx, option, C.byref(value))
         return value.value
 
     def stitch_counts(self):
         """(stitches that went through on the device-side layout, attempts that fell back to
         the host layout) of this engine's context."""
         ok, back = C.c_int(0), C.c_int(0)
-        _lib.check(self.lib.pano_stitch_counts(self._ctx, C.byref(ok), C.byref(back)),
-                   "pano_stitch_counts")
+        _lib.call("pano_stitch_counts", self._ctx, C.byref(ok), C.byref(back))
         return ok.value, back.value
 
     def timing(self, on):
-        _lib.check(self.lib.pano_timing_enable(self._ctx, 1 if on else 0), "pano_timing_enable")
+        _lib.call("pano_timing_enable", self._ctx, 1 if on else 0)
 
     def kernel_times(self):
         """{kernel name: (summed ms, launches)} since ``timing(True)``; waits for the events."""
         out = {}
         for kid in range(self.lib.pano_kernel_count()):
             ms, n = C.c_double(), C.c_int()
-            _lib.check(self.lib.pano_timing_read(self._ctx, kid, C.byref(ms), C.byref(n)),
-                       "pano_timing_read")
+            _lib.call("pano_timing_read", self._ctx, kid, C.byref(ms), C.byref(n))
             if n.value:
                 out[self.lib.pano_kernel_name(kid).decode()] = (ms.value, n.value)
         return out
@@ -808,9 +797,7 @@ class Engine:
         hx, hy = self.hat_tables((h, w))
         out = torch.empty((h, w, 4), dtype=torch.float32, device=self.device)
         lut = self.lut255 if lut is None else lut
-        _lib.check(self.lib.pano_add_weights(self.ctx(), _ptr(frame), h, w, _ptr(lut), _ptr(hx),
-                                             _ptr(hy), _ptr(out)),
-                   "pano_add_weights")
+        self.call("pano_add_weights", frame, h, w, lut, hx, hy, out)
         return out
 
     def warp(self, frame, plan, index, patch, want_maps=False, lut=None):
@@ -824,11 +811,8 @@ class Engine:
             mx = torch.empty((patch.h, patch.w), dtype=torch.float32, device=self.device)
             my = torch.empty_like(mx)
         proj = plan.projs[index]
-        _lib.check(self.lib.pano_warp_spherical(
-            self.ctx(), _ptr(frame), sh, sw, proj.ctypes.data_as(C.c_void_p), _ptr(plan.dev[0]),
-            _ptr(plan.dev[1]), _ptr(plan.dev[2]), _ptr(lut), _ptr(hx), _ptr(hy),
-            x0, y0, patch.w, patch.h, _ptr(patch.planes), _ptr(patch.mask), _ptr(mx),
-            _ptr(my)), "pano_warp_spherical")
+        self.call("pano_warp_spherical", frame, sh, sw, proj, *plan.dev, lut, hx, hy,
+                  x0, y0, patch.w, patch.h, patch.planes, patch.mask, mx, my)
         return mx, my
 
     def warp_all(self, frames, plan, n_blur=0, want_maps=False, luts=None):
@@ -845,8 +829,7 @@ class Engine:
         H, W = shape
         owner = torch.empty((H, W), dtype=torch.int16, device=self.device)
         valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pano_ownership(self.ctx(), table.ptr, table.n, H, W, _ptr(owner),
-                                           _ptr(valid)), "pano_ownership")
+        self.call("pano_ownership", table.dev, table.n, H, W, owner, valid)
         return owner, valid
 
     def multiband(self, patches, shape, n_levels, want_float=False, table=None):
@@ -869,8 +852,7 @@ class Engine:
         shape8 = ((H + ib - 1) // ib, (W + ib - 1) // ib)
         bown = torch.empty((2,) + shape8, dtype=torch.int16, device=self.device)
         interior = torch.empty(shape8, dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.pano_interior_map(self.ctx(), _ptr(owner), H, W, c0, c1, radius,
-                                              _ptr(bown), _ptr(interior)), "pano_interior_map")
+        self.call("pano_interior_map", owner, H, W, c0, c1, radius, bown, interior)
         return interior
 
     def interior_classes(self, owner, radii, strip=None):
@@ -887,9 +869,8 @@ class Engine:
         interior = torch.empty(shape8, dtype=torch.uint8, device=self.device)
         classes = torch.empty(shape8, dtype=torch.uint8, device=self.device)
         arr = (C.c_int * len(radii))(*[int(r) for r in radii])
-        _lib.check(self.lib.pano_interior_classes(self.ctx(), _ptr(owner), H, W, c0, c1, arr,
-                                                  len(radii), _ptr(bown), _ptr(interior),
-                                                  _ptr(classes)), "pano_interior_classes")
+        self.call("pano_interior_classes", owner, H, W, c0, c1, arr, len(radii), bown, interior,
+                  classes)
         return interior, classes
 
     def level_radii(self, n_levels):
@@ -1010,22 +991,17 @@ class Engine:
         if n_blur:
             if flags is None and interior is not None:
                 flags = torch.empty(max(table.n_tiles, 1), dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.pano_multiband_blur(
-                self.ctx(), table.ptr, table.n, table.max_aw, table.max_vh, table.max_ah,
-                _ptr(owner), W, taps.ctypes.data, ntaps, n_blur, _ptr(interior), _ptr(flags)),
-                "pano_multiband_blur")
+            self.call("pano_multiband_blur", table.dev, table.n, table.max_aw, table.max_vh,
+                      table.max_ah, owner, W, taps, ntaps, n_blur, interior, flags)
             self.last_tiles = (table, flags)        # for active_tile_pixels (reporting)
         mosaic = (mosaic_out if mosaic_out is not None else
                   torch.empty((H, W, 3), dtype=torch.uint8, device=self.device))
         fl = (torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
               if want_float else None)
         tabs = plan.dev if interior is not None else (None, None, None)
-        _lib.check(self.lib.pano_multiband_compose(
-            self.ctx(), table.ptr, table.n, H, W, c0, c1, n_levels, _ptr(owner), _ptr(valid),
-            _ptr(interior), _ptr(classes) if interior is not None else None,
-            _ptr(cams) if interior is not None else None, _ptr(tabs[0]),
-            _ptr(tabs[1]), _ptr(tabs[2]), *self._lut_args(luts), _ptr(mosaic), _ptr(fl)),
-            "pano_multiband_compose")
+        self.call("pano_multiband_compose", table.dev, table.n, H, W, c0, c1, n_levels, owner,
+                  valid, interior, classes if interior is not None else None,
+                  cams if interior is not None else None, *tabs, *self._lut_args(luts), mosaic, fl)
         return mosaic, fl
 
     def _patch_blend(self, name, patches, shape, table, *mode):
@@ -1036,8 +1012,7 @@ class Engine:
         if table is None:
             table = patch_table(patches, self)
         mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-        _lib.check(getattr(self.lib, name)(self.ctx(), table.ptr, table.n, H, W, *mode, _ptr(mosaic)),
-                   name)
+        self.call(name, table.dev, table.n, H, W, *mode, mosaic)
         return mosaic
 
     def simple_blend(self, patches, shape, linear, table=None):
@@ -1053,8 +1028,8 @@ class Engine:
     def _lut_args(self, luts):
         """(lut, lut_stride) of include/pano360.h: one shared table, or one per camera."""
         if luts is None:
-            return _ptr(self.lut255), 0
-        return _ptr(luts), 256
+            return self.lut255, 0
+        return luts, 256
 
     # -- exposure ---------------------------------------------------------------
     def equalize_gains(self, frames, rots, intrs, chunk_bytes=256 << 20):
@@ -1088,10 +1063,8 @@ class Engine:
             for a in range(0, len(pairs), step):
                 part = pairs[a:a + step]
                 dev_pairs = torch.from_numpy(part.view(np.uint8).reshape(-1)).to(self.device)
-                _lib.check(self.lib.pano_overlap_stats(
-                    self.ctx(), _ptr(cams), _ptr(dev_pairs), len(part), h, w, bw0,
-                    _ptr(self.lut255),
-                    _ptr(partials), _ptr(stats[a:])), "pano_overlap_stats")
+                self.call("pano_overlap_stats", cams, dev_pairs, len(part), h, w, bw0,
+                          self.lut255, partials, stats[a:])
             host = stats.cpu().numpy()
             for (_, i, j), (count, sum_i, sum_j) in zip(pairs, host):
                 sizes[i, j] = sizes[j, i] = count                       # stitcher.py:59
@@ -1144,10 +1117,7 @@ class Engine:
         xs0, xs1 = strip if strip is not None else (0, W)
         if cams is None:
             cams = self.camera_table(plan)
-        _lib.check(self.lib.pano_ownership_cameras(
-            self.ctx(), _ptr(cams), plan.n, H, W, xs0, xs1, _ptr(plan.dev[0]), _ptr(plan.dev[1]),
-            _ptr(plan.dev[2]), _ptr(owner), _ptr(valid)),
-            "pano_ownership_cameras")
+        self.call("pano_ownership_cameras", cams, plan.n, H, W, xs0, xs1, *plan.dev, owner, valid)
         return owner, valid
 
     def ownership_regions(self, plan, strip=None, min_gap=0, max_spans=4, cams=None):
@@ -1163,10 +1133,8 @@ class Engine:
         xs0, xs1 = strip if strip is not None else (0, W)
         if cams is None:
             cams = self.camera_table(plan)
-        _lib.check(self.lib.pano_ownership_regions(
-            self.ctx(), _ptr(cams), plan.n, H, W, xs0, xs1, _ptr(plan.dev[0]), _ptr(plan.dev[1]),
-            _ptr(plan.dev[2]), _ptr(owner), _ptr(valid), min_gap, max_spans, _ptr(marks),
-            _ptr(regions)), "pano_ownership_regions")
+        self.call("pano_ownership_regions", cams, plan.n, H, W, xs0, xs1, *plan.dev, owner, valid,
+                  min_gap, max_spans, marks, regions)
         return owner, valid, regions, marks
 
     def owned_regions_async(self, owner, n, strip=None, min_gap=0, max_spans=4):
@@ -1179,10 +1147,7 @@ class Engine:
         c0, c1 = strip if strip is not None else (0, W)
         marks = torch.empty((n, W), dtype=torch.uint8, device=self.device)
         regions = torch.empty((n, 5 + 2 * max_spans), dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.pano_owned_regions(
-            self.ctx(), _ptr(owner), H, W, c0, c1, n, min_gap, max_spans,
-                                               _ptr(marks), _ptr(regions)),
-                   "pano_owned_regions")
+        self.call("pano_owned_regions", owner, H, W, c0, c1, n, min_gap, max_spans, marks, regions)
         key = (n, max_spans)
         host_buf = self._region_bufs.get(key)
         if host_buf is None:
@@ -1271,13 +1236,10 @@ class Engine:
             torch = _torch()
             flags = torch.empty(max(table.n_tiles, 1), dtype=torch.uint8, device=self.device)
             need = torch.empty(max(table.n_tiles, 1), dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.pano_blur_tiles(
-                self.ctx(), table.ptr, table.n, table.max_aw, table.max_ah, plan.shape[1], radius,
-                _ptr(interior), _ptr(flags), _ptr(need)), "pano_blur_tiles")
-        _lib.check(self.lib.pano_warp_windows(
-            self.ctx(), _ptr(cams), table.ptr, table.n, table.max_vw, table.max_vh,
-            _ptr(plan.dev[0]),
-            _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(need)), "pano_warp_windows")
+            self.call("pano_blur_tiles", table.dev, table.n, table.max_aw, table.max_ah,
+                      plan.shape[1], radius, interior, flags, need)
+        self.call("pano_warp_windows", cams, table.dev, table.n, table.max_vw, table.max_vh,
+                  *plan.dev, *self._lut_args(luts), need)
         mosaic, fl = self.blur_and_compose(table, owner, valid, plan.shape, n_levels,
                                            want_float, (c0, c1), interior, cams, plan, luts,
                                            flags=flags, mosaic_out=mosaic_out, classes=classes)
@@ -1334,7 +1296,7 @@ class Engine:
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         a.cams, a.rects, a.have = ptr(cams), rects32.ctypes.data, resident.ctypes.data
         a.sin_t, a.cos_t, a.tan_p = (ptr(t) for t in plan.dev)
-        a.lut, a.lut_stride = lut, lut_stride
+        a.lut, a.lut_stride = ptr(lut), lut_stride
         a.taps, a.ntaps = taps.ctypes.data, C.cast(ntaps, C.c_void_p)
         a.mosaic, a.mosaic_f32 = ptr(mosaic), ptr(fl)
         a.marks, a.regions, a.regions_host = ptr(ws["marks"]), ptr(ws["regions"]), ptr(ws["regions_host"])
@@ -1427,7 +1389,7 @@ class Engine:
         """Compares the layout the device made for the last trusted stitch with the verified one
         it was queued with (``pano_stitch_verify``; waits for that stitch's layout kernel).
         Raises ``PanoError`` if they differ: the cameras were changed under a kept Plan."""
-        _lib.check(self.lib.pano_stitch_verify(self._ctx), "pano_stitch_verify")
+        _lib.call("pano_stitch_verify", self._ctx)
 
     def _fused_blend(self, name, mode, frames, plan, frame_ids, strip, luts):
         """A blender ``name`` of the library that samples the frames itself (``mode``: its argument
@@ -1447,10 +1409,8 @@ class Engine:
         cams = self.camera_table(plan, have)
         mosaic = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
         valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
-        _lib.check(getattr(self.lib, name)(
-            self.ctx(), _ptr(cams), plan.n, H, W, c0, c1, mode, _ptr(plan.dev[0]),
-            _ptr(plan.dev[1]), _ptr(plan.dev[2]), *self._lut_args(luts), _ptr(mosaic),
-            _ptr(valid)), name)
+        self.call(name, cams, plan.n, H, W, c0, c1, mode, *plan.dev, *self._lut_args(luts), mosaic,
+                  valid)
         return mosaic, valid
 
     def blend_fused(self, frames, plan, linear, frame_ids=None, strip=None, luts=None):
@@ -1473,8 +1433,7 @@ class Engine:
         H, W = valid.shape
         heights = torch.empty((H, W), dtype=torch.int32, device=self.device)
         result = torch.zeros(6, dtype=torch.int64, device=self.device)
-        _lib.check(self.lib.pano_crop_rect(
-            self.ctx(), _ptr(valid), H, W, _ptr(heights), _ptr(result)), "pano_crop_rect")
+        self.call("pano_crop_rect", valid, H, W, heights, result)
         res = result.cpu().numpy()
         if not res[0]:
             return None
@@ -1501,9 +1460,8 @@ class Engine:
             src[:, :w] = plane
         dst = out if out is not None and pitch == w else torch.empty_like(src)
         tmp = torch.empty_like(src)
-        _lib.check(self.lib.pano_blur_plane(
-            self.ctx(), _ptr(src), _ptr(dst), _ptr(tmp), h, w, pitch,
-            self.plane_taps(ksize, sigma).ctypes.data, ksize), "pano_blur_plane")
+        self.call("pano_blur_plane", src, dst, tmp, h, w, pitch, self.plane_taps(ksize, sigma),
+                  ksize)
         return dst[:, :w]
 
     def pyr_down(self, plane):
@@ -1512,8 +1470,7 @@ class Engine:
         h, w = plane.shape
         out = torch.empty(((h + 1) // 2, (w + 1) // 2), dtype=torch.float32,
                           device=self.device)
-        _lib.check(self.lib.pano_pyr_down(self.ctx(), _ptr(plane), h, w, _ptr(out)),
-                   "pano_pyr_down")
+        self.call("pano_pyr_down", plane, h, w, out)
         return out
 
     # -- whole stitch -----------------------------------------------------------

@@ -107,7 +107,7 @@ class _Dev:
     """Thin typed wrappers over the pyramid entry points (device tensors)."""
 
     def __init__(self, eng):
-        self.eng, self.lib = eng, eng.lib
+        self.eng = eng
 
     def _new(self, h, w):
         import torch
@@ -116,28 +116,24 @@ class _Dev:
     def gray(self, frame):
         h, w = frame.shape[:2]
         out = self._new(h, w)
-        _lib.check(self.lib.pano_gray_u8(self.eng.ctx(), _eng._ptr(frame), h, w, _eng._ptr(out)),
-                   "pano_gray_u8")
+        self.eng.call("pano_gray_u8", frame, h, w, out)
         return out
 
     def up2(self, plane):
         h, w = plane.shape
         out = self._new(2 * h, 2 * w)
-        _lib.check(self.lib.pano_resize_up2(self.eng.ctx(), _eng._ptr(plane), h, w,
-                                            _eng._ptr(out)), "pano_resize_up2")
+        self.eng.call("pano_resize_up2", plane, h, w, out)
         return out
 
     def half(self, plane):
         h, w = plane.shape
         out = self._new(h // 2, w // 2)
-        _lib.check(self.lib.pano_decimate2(self.eng.ctx(), _eng._ptr(plane), h, w,
-                                           _eng._ptr(out)), "pano_decimate2")
+        self.eng.call("pano_decimate2", plane, h, w, out)
         return out
 
     def sub(self, a, b):
         out = self._new(*a.shape)
-        _lib.check(self.lib.pano_subtract(self.eng.ctx(), _eng._ptr(a), _eng._ptr(b),
-                                          C.c_size_t(a.numel()), _eng._ptr(out)), "pano_subtract")
+        self.eng.call("pano_subtract", a, b, a.numel(), out)
         return out
 
     def blur(self, plane, sigma):
@@ -187,9 +183,7 @@ def sift_pyramid_device(frame, n_octaves=None, sigma=SIFT_SIGMA, layers=SIFT_LAY
     ntaps = (C.c_int * len(kernels))(*[len(k) for k in kernels])
     gptr = (C.c_void_p * len(dims))(*[g.data_ptr() for g in gauss])
     dptr = (C.c_void_p * len(dims))(*[d.data_ptr() for d in dog])
-    _lib.check(eng.lib.pano_scale_space(eng.ctx(), _eng._ptr(frame), h, w, len(dims), layers,
-                                        taps.ctypes.data, ntaps, gptr, dptr, _eng._ptr(work)),
-               "pano_scale_space")
+    eng.call("pano_scale_space", frame, h, w, len(dims), layers, taps, ntaps, gptr, dptr, work)
     return gauss, dog
 
 
@@ -426,7 +420,7 @@ class SiftPipeline:
         ws["gen"] += 1                      # what a detection from this workspace held is gone
         a = ws["args"]
         a.frame, a.detect = frame.data_ptr(), 1 if detect else 0
-        _lib.check(self.eng.lib.pano_sift_detect(self.eng.ctx(), C.byref(a)), "pano_sift_detect")
+        self.eng.call("pano_sift_detect", C.byref(a))
         ws["last_frame"] = frame            # (queued kernels read it)
         return ws
 
@@ -502,28 +496,21 @@ def sift_detect_async(frame, max_keypoints=1 << 18, pyramid=None, eng=None):
     counts = torch.zeros(3, dtype=torch.int32, device=dev)    # candidates, keypoints, kept
     for o, diff in enumerate(dog):
         _, oh, ow = diff.shape
-        _lib.check(lib.pano_sift_extrema(eng.ctx(), _eng._ptr(diff), oh, ow, o, n_layers,
-                                         SIFT_CONTRAST, SIFT_EDGE, SIFT_SIGMA, _eng._ptr(cands),
-                                         _eng._ptr(counts[0:]), max_keypoints),
-                   "pano_sift_extrema")
-    _lib.check(lib.pano_sift_orient(eng.ctx(), _eng._ptr(gptr), _eng._ptr(dims), n_layers,
-                                    _eng._ptr(cands), _eng._ptr(counts[0:]), max_keypoints,
-                                    _eng._ptr(kpts), _eng._ptr(counts[1:]), max_keypoints),
-               "pano_sift_orient")
+        eng.call("pano_sift_extrema", diff, oh, ow, o, n_layers, SIFT_CONTRAST, SIFT_EDGE,
+                 SIFT_SIGMA, cands, counts[0:], max_keypoints)
+    eng.call("pano_sift_orient", gptr, dims, n_layers, cands, counts[0:], max_keypoints, kpts,
+             counts[1:], max_keypoints)
     # OpenCV's order and duplicate removal, and the first-octave adjustment (positions and
     # sizes halved, octave byte shifted: sift.cpp, detectAndCompute), on the device: the
     # six-key lexsort took 54 of a 4K frame's 69 ms on the host.  The capacity is sorted; the
     # slots past the device-side count sort to the end.
     work = torch.empty(int(lib.pano_sift_sort_work_bytes(max_keypoints)), dtype=torch.uint8,
                        device=dev)
-    _lib.check(lib.pano_sift_sort_unique(eng.ctx(), _eng._ptr(kpts), max_keypoints,
-                                         _eng._ptr(counts[1:]), SIFT_FIRST_OCTAVE, _eng._ptr(work),
-                                         _eng._ptr(cands), _eng._ptr(counts[2:])),
-               "pano_sift_sort_unique")                      # cands: free again, reused as output
+    eng.call("pano_sift_sort_unique", kpts, max_keypoints, counts[1:], SIFT_FIRST_OCTAVE, work,
+             cands, counts[2:])                              # cands: free again, reused as output
     desc = torch.empty((max_keypoints, 128), dtype=torch.float32, device=dev)
-    _lib.check(lib.pano_sift_describe(eng.ctx(), _eng._ptr(gptr), _eng._ptr(dims),
-                                      SIFT_FIRST_OCTAVE, _eng._ptr(cands), max_keypoints,
-                                      _eng._ptr(counts[2:]), _eng._ptr(desc)), "pano_sift_describe")
+    eng.call("pano_sift_describe", gptr, dims, SIFT_FIRST_OCTAVE, cands, max_keypoints,
+             counts[2:], desc)
     return SiftDetection(counts, cands, desc, max_keypoints, (gauss, dog, dims, gptr, kpts, work),
                          eng)
 
@@ -648,9 +635,8 @@ def ssc_device(points, im_size, n_points, tol=0.1, eng=None, path="auto"):
         if path == "global" or (path == "auto" and not onchip):
             work = torch.empty(int(eng.lib.pano_ssc_probe_work_bytes(ncr, ncc)), dtype=torch.uint8,
                                device=eng.device)
-        _lib.check(eng.lib.pano_ssc_probe(eng.ctx(), _eng._ptr(points), n, C.c_double(cgr), ncr,
-                                          ncc, reach, SSC_PATHS[path], _eng._ptr(work),
-                                          _eng._ptr(sel), _eng._ptr(count)), "pano_ssc_probe")
+        eng.call("pano_ssc_probe", points, n, cgr, ncr, ncc, reach, SSC_PATHS[path], work, sel,
+                 count)
         taken = int(count.cpu()[0])
         search.report(taken)
     return sel, taken
@@ -688,9 +674,7 @@ def _msop_smooth(eng, plane, sigma, tmp, out):
         ksz += not ksz % 2
         _SMOOTH_TAPS[sigma] = np.ascontiguousarray(_eng.gaussian_taps(ksz, sigma))
     taps = _SMOOTH_TAPS[sigma]
-    _lib.check(eng.lib.pano_msop_smooth(eng.ctx(), _eng._ptr(plane), h, w, taps.ctypes.data,
-                                        len(taps), _eng._ptr(tmp), _eng._ptr(out)),
-               "pano_msop_smooth")
+    eng.call("pano_msop_smooth", plane, h, w, taps, len(taps), tmp, out)
     return out
 
 
@@ -713,30 +697,25 @@ def msop_detect_device(frame, max_feat=MSOP_MAX_FEAT, eng=None, want_stages=Fals
         maxf = int(maxf)
         h, w = (int(v) for v in gray.shape)
         hrs = torch.empty_like(gray)
-        _lib.check(lib.pano_harris(eng.ctx(), _eng._ptr(gray), h, w, C.c_float(HARRIS_K),
-                                   _eng._ptr(hrs)), "pano_harris")
+        eng.call("pano_harris", gray, h, w, HARRIS_K, hrs)
         keys = torch.empty(h * w, dtype=torch.int32, device=dev)
         pos = torch.empty(h * w, dtype=torch.int32, device=dev)
         count = torch.zeros(1, dtype=torch.int32, device=dev)
         work = torch.empty(int(lib.pano_msop_candidates_work_bytes(h, w)), dtype=torch.uint8,
                            device=dev)
-        _lib.check(lib.pano_msop_candidates(eng.ctx(), _eng._ptr(hrs), h, w, _eng._ptr(work),
-                                            _eng._ptr(keys), _eng._ptr(pos), _eng._ptr(count)),
-                   "pano_msop_candidates")
+        eng.call("pano_msop_candidates", hrs, h, w, work, keys, pos, count)
         n_cand = int(count.cpu()[0])
         keep = min(n_cand, 20 * maxf)
         if keep == 0:
             raise ValueError(f"msop_detect: level {lvl} has no candidates")
         cut = torch.empty((keep, 2), dtype=torch.int32, device=dev)
         work = torch.empty(int(lib.pano_msop_cut_work_bytes(n_cand)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.pano_msop_cut(eng.ctx(), _eng._ptr(keys), _eng._ptr(pos), n_cand, keep, w,
-                                     _eng._ptr(work), _eng._ptr(cut)), "pano_msop_cut")
+        eng.call("pano_msop_cut", keys, pos, n_cand, keep, w, work, cut)
         sel, taken = ssc_device(cut, (h, w), maxf, eng=eng)
         if taken == 0:
             raise ValueError(f"msop_detect: ssc left level {lvl} without points")
         d_x, d_y = torch.empty_like(gray), torch.empty_like(gray)
-        _lib.check(lib.pano_sobel(eng.ctx(), _eng._ptr(gray), h, w, _eng._ptr(d_x),
-                                  _eng._ptr(d_y)), "pano_sobel")
+        eng.call("pano_sobel", gray, h, w, d_x, d_y)
         tmp = torch.empty_like(gray)
         g_x = _msop_smooth(eng, d_x, 1.0, tmp, d_x)           # gaussian_filter(.., 1.0): ksize 5
         g_y = _msop_smooth(eng, d_y, 1.0, tmp, d_y)
@@ -746,10 +725,8 @@ def msop_detect_device(frame, max_feat=MSOP_MAX_FEAT, eng=None, want_stages=Fals
         tiles = torch.empty((taken, DSIZE, DSIZE), dtype=torch.float32, device=dev) \
             if want_stages else None
         desc = torch.empty((taken, DSIZE * DSIZE), dtype=torch.float32, device=dev)
-        _lib.check(lib.pano_msop_describe(eng.ctx(), _eng._ptr(g_x), _eng._ptr(g_y),
-                                          _eng._ptr(blurred), h, w, _eng._ptr(cut), _eng._ptr(sel),
-                                          taken, 2 ** lvl, _eng._ptr(pts), _eng._ptr(theta),
-                                          _eng._ptr(tiles), _eng._ptr(desc)), "pano_msop_describe")
+        eng.call("pano_msop_describe", g_x, g_y, blurred, h, w, cut, sel, taken, 2 ** lvl, pts,
+                 theta, tiles, desc)
         points.append(pts)
         descs.append(desc)
         if want_stages:
@@ -842,9 +819,7 @@ def _knn2_raw(des1, des2, eng, scale=None):
     idx = torch.empty((nq, 2), dtype=torch.int32, device=eng.device)
     dist = torch.empty((nq, 2), dtype=torch.float32, device=eng.device)
     rescans = torch.zeros(1, dtype=torch.int32, device=eng.device)
-    _lib.check(eng.lib.pano_knn2(eng.ctx(), _eng._ptr(des1), nq, _eng._ptr(des2), nt, d,
-                                 C.c_float(scale), _eng._ptr(work), _eng._ptr(idx),
-                                 _eng._ptr(dist), _eng._ptr(rescans)), "pano_knn2")
+    eng.call("pano_knn2", des1, nq, des2, nt, d, scale, work, idx, dist, rescans)
     return idx, dist, rescans
 
 
@@ -904,11 +879,8 @@ def find_homographies_device(pts, offsets, counts, max_iters=2000, thresh=3.0, s
     scores = torch.empty((n, max_iters), dtype=torch.int32, device=dev) if want_scores else None
     work = None if want_scores else torch.empty(
         int(eng.lib.pano_hom_ransac_work_bytes(n, max_iters)), dtype=torch.uint8, device=dev)
-    _lib.check(eng.lib.pano_hom_ransac(eng.ctx(), _eng._ptr(pts), _eng._ptr(offsets),
-                                       _eng._ptr(counts), n, max_iters, C.c_float(thresh),
-                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _eng._ptr(work),
-                                       _eng._ptr(hom), _eng._ptr(mask), _eng._ptr(n_inl),
-                                       _eng._ptr(scores)), "pano_hom_ransac")
+    eng.call("pano_hom_ransac", pts, offsets, counts, n, max_iters, thresh,
+             int(seed) & 0xFFFFFFFFFFFFFFFF, work, hom, mask, n_inl, scores)
     out = (hom, mask, n_inl)
     return out + (scores,) if want_scores else out
 
@@ -968,10 +940,8 @@ class _Pairs:
             idx, dist, _ = _knn2_raw(des_dev[i], des_dev[j], eng,
                                      _knn_scale(max(peaks[i], peaks[j])))
             off = int(self.offsets[p])
-            _lib.check(eng.lib.pano_match_pack(
-                eng.ctx(), _eng._ptr(idx), _eng._ptr(dist), nq, C.c_double(LOWE_RATIO),
-                _eng._ptr(kp_dev[i]), _eng._ptr(kp_dev[j]), nt, _eng._ptr(self.pts[off:]),
-                _eng._ptr(self.match[off:]), _eng._ptr(self.counts[p:])), "pano_match_pack")
+            eng.call("pano_match_pack", idx, dist, nq, LOWE_RATIO, kp_dev[i], kp_dev[j], nt,
+                     self.pts[off:], self.match[off:], self.counts[p:])
         # pairs below N_MIN_MATCH survivors take part with no rows: they fail without a wait
         eff = torch.where(self.counts >= N_MIN_MATCH, self.counts, torch.zeros_like(self.counts))
         off_dev = torch.from_numpy(self.offsets[:-1].astype(np.int32)).to(dev)

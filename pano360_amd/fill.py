@@ -14,7 +14,6 @@ The fill works in the equirectangular plane: near a pole it is smooth, not isotr
 closed image whose width is odd at some level the seam is slightly stretched there.  There is no
 CPU fallback.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -100,10 +99,8 @@ def fill_device(image, mask, closed=False, eng=None, out=None):
         out = image
     elif tuple(out.shape) != (h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError("out: the image itself or a dense uint8 tensor of its shape")
-    _lib.check(eng.lib.pano_fill_u8(eng.ctx(), _lib._ptr(image), C.c_int64(image.stride(0)),
-                                    _lib._ptr(mask), C.c_int64(mask.stride(0)), h, w,
-                                    1 if closed else 0, _lib._ptr(out), C.c_int64(out.stride(0))),
-               "pano_fill_u8")
+    eng.call("pano_fill_u8", image, image.stride(0), mask, mask.stride(0), h, w, 1 if closed else 0,
+             out, out.stride(0))
     return out
 
 
@@ -119,8 +116,7 @@ def select_device(a, mask, b, eng=None, out=None):
     for t in (a, mask, b, out):
         if t.dtype != torch.uint8 or not t.is_contiguous():
             raise ValueError("select_device: dense uint8 tensors")
-    _lib.check(eng.lib.pano_select_u8(eng.ctx(), _lib._ptr(a), _lib._ptr(mask), _lib._ptr(b),
-                                      _lib._ptr(out), C.c_int64(mask.numel())), "pano_select_u8")
+    eng.call("pano_select_u8", a, mask, b, out, mask.numel())
     return out
 
 

@@ -122,8 +122,7 @@ def fuse_device(stacks, params=None, eng=None, want_stages=False):
     work = torch.empty(need, dtype=torch.uint8, device=outs[0].device)
     native = _lib.FuseParams(params.contrast, params.saturation, params.exposure,
                              -1 if params.n_levels is None else params.n_levels)
-    _lib.check(eng.lib.pano_fuse_u8(eng.ctx(), records, len(stacks), C.byref(native), work.data_ptr(),
-                                    need), "pano_fuse_u8")
+    eng.call("pano_fuse_u8", records, len(stacks), C.byref(native), work, need)
     # (the kernels are queued on the stream the tensors belong to: the frames and `work` may go)
     return (outs, stages) if want_stages else outs
 

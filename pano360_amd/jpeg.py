@@ -438,7 +438,6 @@ def decode_device(blobs, eng=None, want_coefs=False, _headers=None):
     also returns each image's coefficients (int16 [blocks][64], natural order, DC prediction
     applied, in MCU block order)."""
     import torch
-    from . import engine as _eng
     eng = _lib._engine(eng)
     headers = _headers or [parse(b) for b in blobs]
     for i, h in enumerate(headers):
@@ -459,10 +458,8 @@ def decode_device(blobs, eng=None, want_coefs=False, _headers=None):
     work = torch.empty(int(bt[JB_WORK_BYTES]), dtype=torch.uint8, device=dev)
     out = torch.empty(max(int(bt[JB_OUT_BYTES]), 1), dtype=torch.uint8, device=dev)
     desc_c = np.ascontiguousarray(desc)
-    _lib.check(eng.lib.pano_jpeg_decode(
-        eng.ctx(), desc_c.ctypes.data_as(C.c_void_p), len(headers), _eng._ptr(packed),
-        C.c_int64(packed_bytes), _eng._ptr(work), C.c_int64(work.numel()), _eng._ptr(out),
-        C.c_int64(out.numel())), "pano_jpeg_decode")
+    eng.call("pano_jpeg_decode", desc_c, len(headers), packed, packed_bytes, work, work.numel(),
+             out, out.numel())
     frames = []
     for i, h in enumerate(headers):
         oh, ow = h.out_shape
@@ -627,12 +624,11 @@ def _encode_setup(images, quality, subsampling, order, eng, numbered):
         return None
     eng = _lib._engine(eng)
     qt = np.ascontiguousarray(quant_tables(quality).astype(np.uint8))
-    settings = (_lib.JPEG_BGR if order == "bgr" else 0, 2 if subsampling == -1 else subsampling,
-                qt.ctypes.data_as(C.c_void_p))
+    settings = (_lib.JPEG_BGR if order == "bgr" else 0, 2 if subsampling == -1 else subsampling, qt)
 
     def scratch(nbytes):
         work = torch.empty(int(nbytes), dtype=torch.uint8, device=torch.device(eng.device))
-        return work, (_lib._ptr(work), C.c_int64(int(nbytes)))
+        return work, (work, int(nbytes))
 
     def to_file(h, w, address, nbytes):
         return encode_header(w, h, quality, subsampling) + C.string_at(address, nbytes) + b"\xff\xd9"
@@ -655,9 +651,8 @@ def encode_device(img, quality=75, subsampling=-1, order="bgr", eng=None, want_c
     h, w = int(img.shape[0]), int(img.shape[1])
     work, work_args = scratch(eng.lib.pano_jpeg_encode_work_bytes(h, w, settings[1]))
     stream, nbytes = C.c_void_p(), C.c_int64()
-    _lib.check(eng.lib.pano_jpeg_encode(
-        eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)), *settings,
-        *work_args, C.byref(stream), C.byref(nbytes)), "pano_jpeg_encode")
+    eng.call("pano_jpeg_encode", img, h, w, img.stride(0), *settings, *work_args, C.byref(stream),
+             C.byref(nbytes))
     data = to_file(h, w, stream.value, nbytes.value)
     if not want_coefs:
         return data
@@ -681,7 +676,7 @@ def plan_encode_batches(blocks, max_work=BATCH_WORK, work_bytes=None):
     ``JPEG_BATCH_MAX_BLOCKS`` blocks.  Raises ValueError for an image that fits no call alone."""
     if work_bytes is None:
         native = _lib.lib().pano_jpeg_encode_batch_work_bytes
-        work_bytes = lambda b, n: int(native(C.c_int64(b), n))       # noqa: E731
+        work_bytes = lambda b, n: int(native(b, n))       # noqa: E731
 
     def fits(b, n):
         return n <= _lib.JPEG_BATCH_MAX and b <= _lib.JPEG_BATCH_MAX_BLOCKS \
@@ -725,12 +720,11 @@ def encode_batch_device(images, quality=75, subsampling=-1, order="bgr", eng=Non
             img = _lib.rgb_on_device(images[i], eng)
             held.append(img)
             rec.img, rec.pitch, (rec.h, rec.w) = img.data_ptr(), img.stride(0), shapes[i]
-        total = C.c_int64(sum(blocks[i] for i in batch))
+        total = sum(blocks[i] for i in batch)
         work, work_args = scratch(eng.lib.pano_jpeg_encode_batch_work_bytes(total, len(batch)))
         streams, offsets = C.c_void_p(), C.c_void_p()
-        _lib.check(eng.lib.pano_jpeg_encode_batch(
-            eng.ctx(), table, len(batch), *settings, *work_args, C.byref(streams),
-            C.byref(offsets)), "pano_jpeg_encode_batch")
+        eng.call("pano_jpeg_encode_batch", table, len(batch), *settings, *work_args,
+                 C.byref(streams), C.byref(offsets))
         offs = (C.c_int64 * (len(batch) + 1)).from_address(offsets.value)
         for k, i in enumerate(batch):
             files.append(to_file(*shapes[i], streams.value + offs[k], offs[k + 1] - offs[k]))

@@ -18,7 +18,6 @@ needs a fisheye term in the warp itself, which is a different, later piece of wo
 Vignetting and chromatic aberration are out of scope; ``bundle_adj.refine`` estimates k1 and k2
 from the matches and hands them over as ``LensModel`` records (``Refinement.lens_models``).
 """
-import ctypes as C
 import json
 import logging
 import os
@@ -257,8 +256,7 @@ def undistort_device(frames, models, interp="cubic", focal=None, eng=None):
         rec.w, rec.h, rec.model, rec.interp = w, h, KINDS[model.kind], INTERPS[interp]
         sources.append(frame)
         outs.append(out)
-    _lib.check(eng.lib.pano_lens_undistort_u8(eng.ctx(), records, len(frames)),
-               "pano_lens_undistort_u8")
+    eng.call("pano_lens_undistort_u8", records, len(frames))
     return outs, focals
 
 

@@ -28,7 +28,6 @@ The arithmetic is stated in include/pano360.h and, in NumPy, in tests/photo_mode
 CPU fallback.  Not covered: a falloff per camera (mixed lenses), an optical axis away from the
 image centre, and a response curve other than a power law.
 """
-import ctypes as C
 import logging
 
 import numpy as np
@@ -187,11 +186,8 @@ def stats_device(frames, rots, intrs, lo=LO, hi=HI, step=1, params=None, tau=np.
         rec.H[:] = H.ravel().tolist()
         rec.i, rec.j = i, j
     sums = torch.empty((len(pairs), SUMS), dtype=torch.float64, device=frames[0].device)
-    dptr = C.POINTER(C.c_double)
-    _lib.check(eng.lib.pano_photo_stats(eng.ctx(), frame_recs, n, pair_recs, len(pairs), step, lo,
-                                        hi, log_gains.ctypes.data_as(dptr),
-                                        alpha.ctypes.data_as(dptr), tau, sums.data_ptr()),
-               "pano_photo_stats")
+    eng.call("pano_photo_stats", frame_recs, n, pair_recs, len(pairs), step, lo, hi, log_gains,
+             alpha, tau, sums)
     return pairs, sums.cpu().numpy()
 
 
@@ -323,7 +319,7 @@ def apply_device(frames, model, eng=None):
         rec.src_pitch, rec.dst_pitch = frame.stride(0), out.stride(0)
         rec.w, rec.h = int(frame.shape[1]), int(frame.shape[0])
         outs.append(out)
-    _lib.check(eng.lib.pano_photo_apply_u8(eng.ctx(), records, len(frames)), "pano_photo_apply_u8")
+    eng.call("pano_photo_apply_u8", records, len(frames))
     # (the kernels are queued on the stream the tensors belong to: `frames` and `table` may go)
     return outs
 

@@ -47,7 +47,6 @@ def filter_device(img, order="bgr", eng=None):
     as long as the pixels of a row are contiguous (a crop view of a mosaic needs no copy).
     Queued on the engine's stream.  Raises ValueError for what ``encodable`` rejects."""
     import torch
-    from . import engine as _eng
     if order not in ("bgr", "rgb"):
         raise ValueError(f"order {order!r}: 'bgr' or 'rgb'")
     if not encodable(img):
@@ -56,9 +55,8 @@ def filter_device(img, order="bgr", eng=None):
     img = _lib.rgb_on_device(img, eng)
     h, w = int(img.shape[0]), int(img.shape[1])
     out = torch.empty((h, 1 + 3 * w), dtype=torch.uint8, device=img.device)
-    _lib.check(eng.lib.pano_png_filter(
-        eng.ctx(), C.c_void_p(img.data_ptr()), h, w, C.c_int64(img.stride(0)),
-        _lib.PNG_BGR if order == "bgr" else 0, _eng._ptr(out)), "pano_png_filter")
+    eng.call("pano_png_filter", img, h, w, img.stride(0), _lib.PNG_BGR if order == "bgr" else 0,
+             out)
     return out
 
 
@@ -69,7 +67,6 @@ def deflate_device(data, eng=None):
     the Adler-32 big-endian.  ``zlib.decompress`` returns the buffer.  The call waits on the
     stream twice and downloads the stream; not capturable."""
     import torch
-    from . import engine as _eng
     eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     if isinstance(data, (bytes, bytearray, memoryview)):
@@ -81,13 +78,11 @@ def deflate_device(data, eng=None):
     n = int(data.numel())
     if n > MAX_DEFLATE:
         raise ValueError(f"{n} bytes: pano_deflate takes at most {MAX_DEFLATE}")
-    lib = eng.lib
-    work_bytes = int(lib.pano_deflate_work_bytes(C.c_int64(n)))
+    work_bytes = int(eng.lib.pano_deflate_work_bytes(n))
     work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
     stream, nbytes, adler = C.c_void_p(), C.c_int64(), C.c_uint32()
-    _lib.check(lib.pano_deflate(
-        eng.ctx(), C.c_void_p(data.data_ptr() if n else 0), C.c_int64(n), _eng._ptr(work),
-        C.c_int64(work_bytes), C.byref(stream), C.byref(nbytes), C.byref(adler)), "pano_deflate")
+    eng.call("pano_deflate", data if n else None, n, work, work_bytes, C.byref(stream),
+             C.byref(nbytes), C.byref(adler))
     return b"\x78\x01" + C.string_at(stream.value, nbytes.value) + adler.value.to_bytes(4, "big")
 
 
@@ -95,7 +90,6 @@ def code_lengths_device(freq, max_bits, eng=None):
     """``pano_deflate_lengths``: the optimal code lengths of at most ``max_bits`` bits for the
     symbol frequencies ``freq`` (up to 288 of them, their sum below 2^32), as a uint8 array."""
     import torch
-    from . import engine as _eng
     eng = _lib._engine(eng)
     dev = torch.device(eng.device)
     f = np.ascontiguousarray(freq, dtype=np.int64)
@@ -103,8 +97,7 @@ def code_lengths_device(freq, max_bits, eng=None):
         raise ValueError("frequencies: one row of non-negative counts, their sum below 2^32")
     fd = torch.from_numpy(f.astype(np.uint32).view(np.int32)).to(dev)
     out = torch.zeros(len(f), dtype=torch.uint8, device=dev)
-    _lib.check(eng.lib.pano_deflate_lengths(eng.ctx(), _eng._ptr(fd), len(f), int(max_bits),
-                                            _eng._ptr(out)), "pano_deflate_lengths")
+    eng.call("pano_deflate_lengths", fd, len(f), int(max_bits), out)
     return out.cpu().numpy()
 
 

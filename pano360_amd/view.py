@@ -240,9 +240,7 @@ def mip_device(mosaic, eng=None):
     offs = mip_offsets(h, w)
     buf = torch.empty(offs[-1], dtype=torch.uint8, device=mosaic.device)
     table = (C.c_int64 * len(offs))(*offs)
-    _lib.check(eng.lib.pano_mip_u8(eng.ctx(), C.c_void_p(mosaic.data_ptr()), h, w,
-                                   C.c_int64(mosaic.stride(0)), _lib._ptr(buf), table,
-                                   len(offs) - 1), "pano_mip_u8")
+    eng.call("pano_mip_u8", mosaic, h, w, mosaic.stride(0), buf, table, len(offs) - 1)
     return Mips(buf, offs, (h, w))
 
 
@@ -290,8 +288,8 @@ def render_device(mosaic_or_mips, geom, views, eng=None):
     for rec, img, mask in zip(table, images, masks):
         rec.image, rec.mask = img.data_ptr(), mask.data_ptr()
     offs = (C.c_int64 * len(mips.offsets))(*mips.offsets)
-    _lib.check(eng.lib.pano_view_render(eng.ctx(), _lib._ptr(mips.buffer), offs, mips.n_levels,
-                                        C.byref(record), table, len(views)), "pano_view_render")
+    eng.call("pano_view_render", mips.buffer, offs, mips.n_levels, C.byref(record), table,
+             len(views))
     return images, masks
 
 
