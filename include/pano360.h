@@ -265,8 +265,10 @@ int pano_warp_spherical(pano_ctx *ctx, const uint8_t *frame, int sh, int sw,
  * pano_ownership_cameras.  cams, patches: dev arrays of n records;
  * max_vw / max_vh: the largest window among them (sizes the grid).
  * need (optional): the per-tile flags pano_blur_tiles writes (one byte per 32 x 32
- * tile of every record, at patches[i].tiles_off); 64 x 4 pixel blocks none of whose
- * tiles is needed are left unwritten - nothing reads them. */
+ * tile of every record, at patches[i].tiles_off, the grid being that of rectangle A with
+ * the tiles of V's pixels outside it clamped to its border); every pixel of V whose tile is
+ * needed is written, blocks of pixels none of whose tiles is needed may be left unwritten -
+ * nothing reads them. */
 int pano_warp_windows(pano_ctx *ctx, const pano_camera *cams, const pano_patch *patches,
                       int n, int max_vw, int max_vh, const double *sin_t,
                       const double *cos_t, const double *tan_p, const float *lut,
