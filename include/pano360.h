@@ -1614,6 +1614,13 @@ int pano_align_mtb(pano_ctx *ctx, const pano_align_stack *stacks, int n, const p
  * been queued, and the call is repeated with resume = 1 after the caller has grown them; or a
  * negative error (args->layout.missing > 0: a needed frame is not resident). */
 #define PANO_EGROW 1
+/* pano_stitch_args.trust_layout (described at the field) - in: */
+#define PANO_TRUST_NONE 0
+#define PANO_TRUST_LAYOUT 1
+#define PANO_TRUST_GEOMETRY 3
+/* ... and out (or PANO_TRUST_NONE: the stitch took a waiting path): */
+#define PANO_TRUST_TRUSTED 2
+#define PANO_TRUST_KEPT 4
 typedef struct pano_stitch_args {
     const pano_camera *cams;
     const int32_t *rects;
@@ -1640,7 +1647,8 @@ typedef struct pano_stitch_args {
     int32_t lut_stride, n_levels, radius, shortcut, warp_need, max_spans, min_gap;
     int32_t cap_records, cap_tiles;
     int32_t used_need;         /* out: 1 = the warp ran on the need flags */
-    int32_t trust_layout;      /* in: 1 = the caller vouches that cameras (matrices, rectangles),
+    int32_t trust_layout;      /* PANO_TRUST_* above.
+                                * in: 1 = the caller vouches that cameras (matrices, rectangles),
                                 * strip and resident frames are those of this context's previous
                                 * stitch (with PANO_OPT_STITCH_ASYNC on): the stitch is queued with
                                 * that stitch's verified layout and NOBODY WAITS - the call returns

@@ -85,6 +85,9 @@ class StitchArgs(C.Structure):
 EINVAL = -1     # PANO_EINVAL
 ESOLVE = -4     # PANO_ESOLVE: pano_poisson_blend did not converge (cap or breakdown)
 EGROW = 1       # pano_stitch_multiband: an arena is too small, args.layout says what is needed
+# pano_stitch_args.trust_layout: what the caller asks for, and what the stitch did
+TRUST_NONE, TRUST_LAYOUT, TRUST_GEOMETRY = 0, 1, 3
+TRUST_TRUSTED, TRUST_KEPT = 2, 4
 # pano_seam_levels' dtype codes, the resident flood's capacity in cells (wall included)
 SEAM_U8, SEAM_I16, SEAM_I32, SEAM_F32, SEAM_F64 = 0, 1, 2, 3, 4
 SEAM_DTYPES = {"uint8": SEAM_U8, "int16": SEAM_I16, "int32": SEAM_I32, "float32": SEAM_F32,

@@ -64,7 +64,7 @@ extern "C" int pano_ctx_create(int device, void *stream, pano_ctx **out) {
 
 int pano_ctx_enter(pano_ctx *ctx) {
     // any call but the stitch's own may write the buffers a stitch left its geometry in
-    if (!ctx->in_stitch) ctx->geom_valid = false;
+    if (!ctx->in_stitch) stitch_memo_void_geometry(ctx->memo);
     PANO_HIP(hipSetDevice(ctx->device));
     return PANO_OK;
 }
@@ -162,7 +162,7 @@ extern "C" int pano_ctx_set_stream(pano_ctx *ctx, void *stream) {
     PANO_REQUIRE(ctx, "pano_ctx_set_stream: null context");
     // what the previous stitch left behind was produced in the OTHER stream's order: a kept-geometry
     // repeat (stitch.hip) would read its owner map, table and flags with nothing ordering the two
-    if ((hipStream_t)stream != ctx->stream) ctx->geom_valid = false;
+    if ((hipStream_t)stream != ctx->stream) stitch_memo_void_geometry(ctx->memo);
     ctx->stream = (hipStream_t)stream;
     return PANO_OK;
 }
@@ -189,9 +189,8 @@ extern "C" int pano_ctx_set_option(pano_ctx *ctx, int option, int value) {
     // ... and so is everything a stitch left for a kept-geometry repeat (stitch.hip): the record
     // table, the flags and the work list were laid out for the options as they were.  A changed
     // blur kernel changes the tile grid: the previous layout's bounds are another grid's too.
-    ctx->geom_valid = false;
-    if (changed && option == PANO_OPT_BLUR_KERNEL)
-        ctx->lay_prev_valid = ctx->lay_prev_verified = false;
+    stitch_memo_void_geometry(ctx->memo);
+    if (changed && option == PANO_OPT_BLUR_KERNEL) stitch_memo_void_layout(ctx->memo);
     return PANO_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/pano360.h"
+#include "stitch_mode.h"
 
 // ---- error plumbing --------------------------------------------------------
 void pano_set_error(const char *fmt, ...);
@@ -115,7 +116,6 @@ struct PanoTapSet {                 // one set of Gaussian apertures (pano_multi
     hipStream_t built_on;           // the stream those were queued on
 };
 
-struct LayoutSummary;               // layout.h
 struct PanoSiftGraph {               // detect.hip: one captured launch sequence of pano_sift_detect
     uint64_t key;                   // hash of sizes, switches, buffer addresses, tap values
     hipGraphExec_t exec;            // null: not captured (yet, or the capture failed)
@@ -183,8 +183,6 @@ int pano_buf_reserve_sync(pano_ctx *ctx, int id, size_t need, hipStream_t stream
 // ... and then queues the copy of `bytes` bytes of pageable host memory into it.
 int pano_buf_upload(pano_ctx *ctx, int id, const void *host, size_t bytes, hipStream_t stream);
 
-#define GEOM_BUFS 11
-#define STITCH_SIG 13             // stitch.hip: stitch_signature
 struct pano_ctx {
     int device;
     hipStream_t stream;
@@ -208,21 +206,11 @@ struct pano_ctx {
     hipStream_t side;               // second stream of pano_stitch_multiband
     bool upload_pending;
     // pano_stitch_multiband without its host round trip (stitch.hip): the host values the device
-    // copies of the patch rectangles and resident flags were made from, and what the previous
-    // stitch's layout needed: the next one's launch bounds
+    // copies of the patch rectangles and resident flags were made from
     std::vector<int32_t> lay_rects_host;
     std::vector<uint8_t> lay_have_host;
-    pano_layout lay_prev;
-    int lay_prev_sig[STITCH_SIG];
-    bool lay_prev_valid;
-    bool lay_prev_verified;         // lay_prev was read back (device summary) or made on the host
-    bool trusted_pending;           // a trusted stitch's summary has not been compared yet
-    int lay_prev_used_need;
-    // kept geometry (args->trust_layout = 3): the previous stitch of this context went through whole
-    // with these buffers and no other call has entered the context since (pano_ctx_enter clears it)
-    bool geom_valid, in_stitch;
-    const void *geom_bufs[GEOM_BUFS];
-    int lay_count[2];               // stitches that went through on the device layout / fell back
+    StitchMemo memo;                // what the previous stitch left for the next (stitch_mode.h)
+    bool in_stitch;                 // the stitch's own nested calls do not void the kept geometry
     bool sift_capturing;            // pano_sift_detect is capturing a launch sequence (detect.hip)
     // pano_sift_detect: the captured launch sequences, one per set of buffers (detect.hip)
     std::vector<PanoSiftGraph> sift_graphs;
@@ -250,9 +238,9 @@ int pano_ctx_tap_set_built(pano_ctx *ctx, PanoTapSet *set);
 // An entry point that only READS what a stitch left behind (the crop reads the valid mask): the
 // kept geometry (stitch.hip) survives it.
 #define PANO_ENTER_READONLY(ctx, who)                              \
-    const bool geom_keep_ = (ctx) != nullptr && (ctx)->geom_valid; \
+    const bool geom_keep_ = (ctx) != nullptr && (ctx)->memo.geom_valid; \
     PANO_ENTER(ctx, who);                                          \
-    (ctx)->geom_valid = geom_keep_
+    (ctx)->memo.geom_valid = geom_keep_
 
 void pano_timing_edge(pano_ctx *ctx, int kid, hipStream_t stream, bool begin);
 

@@ -101,12 +101,19 @@ __host__ __device__ static inline bool layout_record_fits(const pano_patch &r) {
 
 // What the device-side layout (layout_windows_kernel) leaves for the host to check.
 struct LayoutSummary {
-    int64_t planes_floats, blurred_floats, scratch_floats;
-    int32_t n_records, n_tiles;
-    int32_t max_vw, max_vh, max_aw, max_ah;
-    int32_t missing;
+    pano_layout lay;
     int32_t ok;                // 1: the table holds the records; 0: it was emptied (see `why`)
     int32_t why;               // bit 0 arenas / tile flags too small, 1 launch bounds exceeded,
                                // 2 more records than slots, 3 a plane beyond 2 GiB, 4 frames missing
-    int32_t pad;
 };
+
+// Did the layout kernel lay out exactly the verified layout `want` (a trusted stitch's promise)?
+__host__ __device__ static inline bool layout_as_verified(const LayoutSummary &got,
+                                                          const pano_layout &want) {
+    const pano_layout &g = got.lay;
+    return got.ok && g.planes_floats == want.planes_floats &&
+           g.blurred_floats == want.blurred_floats && g.scratch_floats == want.scratch_floats &&
+           g.n_records == want.n_records && g.n_tiles == want.n_tiles && g.max_vw == want.max_vw &&
+           g.max_vh == want.max_vh && g.max_aw == want.max_aw && g.max_ah == want.max_ah &&
+           g.missing == 0;
+}

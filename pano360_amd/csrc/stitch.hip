@@ -22,7 +22,7 @@ __global__ __launch_bounds__(LAY_THREADS) void layout_windows_kernel(
     int n_blur, int grid32, float *planes, float *blurred, float *scratch, long cap_planes,
     long cap_blurred, long cap_scratch, int cap_tiles, int want_tiles, int b_nr, int b_vw,
     int b_vh, int b_aw, int b_ah, pano_patch *__restrict__ table,
-    LayoutSummary *__restrict__ summary, LayoutSummary expect, int check_expect,
+    LayoutSummary *__restrict__ summary, pano_layout expect, int check_expect,
     int *__restrict__ sticky) {
     __shared__ long s_planes[LAY_THREADS], s_blurred[LAY_THREADS], s_scratch[LAY_THREADS];
     __shared__ int s_tiles[LAY_THREADS], s_slot[LAY_THREADS];
@@ -129,27 +129,22 @@ __global__ __launch_bounds__(LAY_THREADS) void layout_windows_kernel(
     // records the launches cover beyond the real ones - or all of them - are empty
     for (int k = (why ? 0 : nr) + tid; k < b_nr; k += LAY_THREADS) table[k] = pano_patch{};
     if (tid == 0) {
-        LayoutSummary out;
-        out.planes_floats = need_planes;
-        out.blurred_floats = need_blurred;
-        out.scratch_floats = need_scratch;
-        out.n_records = nr;
-        out.n_tiles = (int)(s_run[3] < (1l << 30) ? s_run[3] : (1l << 30));
-        out.max_vw = s_max[0], out.max_vh = s_max[1], out.max_aw = s_max[2], out.max_ah = s_max[3];
-        out.missing = s_missing;
+        LayoutSummary out = {};
+        out.lay.planes_floats = need_planes;
+        out.lay.blurred_floats = need_blurred;
+        out.lay.scratch_floats = need_scratch;
+        out.lay.n_records = nr;
+        out.lay.n_tiles = (int)(s_run[3] < (1l << 30) ? s_run[3] : (1l << 30));
+        out.lay.max_vw = s_max[0], out.lay.max_vh = s_max[1];
+        out.lay.max_aw = s_max[2], out.lay.max_ah = s_max[3];
+        out.lay.missing = s_missing;
         out.ok = why == 0;
         out.why = why;
-        out.pad = 0;
         *summary = out;
         // a trusted stitch: ITS layout against the verified one it was queued with, kept in a
         // sticky word - the one summary slot is overwritten by the next stitch's kernel, and a
         // broken promise in the middle of a run of trusted stitches must not be lost with it
-        if (check_expect &&
-            !(out.ok && out.planes_floats == expect.planes_floats &&
-              out.blurred_floats == expect.blurred_floats && out.scratch_floats == expect.scratch_floats &&
-              out.n_records == expect.n_records && out.n_tiles == expect.n_tiles &&
-              out.max_vw == expect.max_vw && out.max_vh == expect.max_vh && out.max_aw == expect.max_aw &&
-              out.max_ah == expect.max_ah && out.missing == 0))
+        if (check_expect && !layout_as_verified(out, expect))
             *(volatile int *)sticky = 1;
     }
 }
@@ -174,52 +169,45 @@ static int ensure_layout_buffers(pano_ctx *ctx, int n) {
     return PANO_OK;
 }
 
-// The verified layout as the layout kernel compares it, and the sticky word behind the summary.
+// The summary the layout kernel writes, and the sticky word behind it.
 static LayoutSummary *lay_sum_host(pano_ctx *ctx) {
     return (LayoutSummary *)ctx->buf[BUF_LAY_SUM_HOST].p;
-}
-static LayoutSummary layout_expectation(const pano_layout &v) {
-    LayoutSummary e = {};
-    e.planes_floats = v.planes_floats, e.blurred_floats = v.blurred_floats;
-    e.scratch_floats = v.scratch_floats;
-    e.n_records = v.n_records, e.n_tiles = v.n_tiles;
-    e.max_vw = v.max_vw, e.max_vh = v.max_vh, e.max_aw = v.max_aw, e.max_ah = v.max_ah;
-    return e;
 }
 static int *layout_sticky(pano_ctx *ctx) {
     return (int *)((unsigned char *)lay_sum_host(ctx) + sizeof(LayoutSummary));
 }
 
-static void stitch_signature(const pano_stitch_args *a, int tile_grid, int *sig) {
-    const int v[STITCH_SIG] = {a->n, a->H, a->W, a->xs0, a->xs1, a->own0, a->own1, a->n_levels,
-                               a->radius, a->max_spans, a->shortcut, a->min_gap, tile_grid};
-    for (int k = 0; k < STITCH_SIG; ++k) sig[k] = v[k];
-}
+// One call of pano_stitch_multiband: the context, the arguments, and the facts about the stitch
+// that its routes and the tail behind them share.
+struct Stitch {
+    pano_ctx *ctx;
+    pano_stitch_args *a;
+    int n_blur, tile_grid;
+    bool interior;                  // the interior shortcut, with something to blur
+    bool two_streams;               // the side stream takes one of each pair of small chains
+    bool classes;                   // the interior map fills args->classes, the collapse reads them
+    int sig[STITCH_SIG];            // the stitch's shape (StitchMemo::sig)
+};
 
-// The interior map of a stitch - with the level classes beside it when the caller gave a buffer
-// for them (radii of the levels: half their apertures, ascending as stitcher.py:218 makes them).
-static int stitch_interior_map(pano_ctx *ctx, const pano_stitch_args *a, int n_blur) {
-    if (a->classes && n_blur > 0 && ctx->opt[PANO_OPT_LEVEL_CLASSES]) {
-        int radii[PANO_MAX_LEVELS];
-        bool ascending = true;
-        for (int k = 0; k < n_blur; ++k) {
-            radii[k] = a->ntaps[k] / 2;
-            if (k && radii[k] < radii[k - 1]) ascending = false;
-        }
-        if (ascending && radii[n_blur - 1] == a->radius)
-            return pano_interior_classes(ctx, a->owner, a->H, a->W, a->own0, a->own1, radii, n_blur,
-                                         a->block_owner, a->interior, a->classes);
-    }
-    return pano_interior_map(ctx, a->owner, a->H, a->W, a->own0, a->own1, a->radius, a->block_owner,
-                             a->interior);
-}
-
-// Do this stitch's classes hold (the buffer was given and stitch_interior_map filled it)?
+// Level classes beside the interior map: when the caller gave a buffer for them (radii of the
+// levels: half their apertures, ascending as stitcher.py:218 makes them).
 static bool stitch_has_classes(const pano_ctx *ctx, const pano_stitch_args *a, int n_blur) {
     if (!a->classes || n_blur <= 0 || !ctx->opt[PANO_OPT_LEVEL_CLASSES]) return false;
-    for (int k = 0; k < n_blur; ++k)
-        if (k && a->ntaps[k] / 2 < a->ntaps[k - 1] / 2) return false;
+    for (int k = 1; k < n_blur; ++k)
+        if (a->ntaps[k] / 2 < a->ntaps[k - 1] / 2) return false;
     return a->ntaps[n_blur - 1] / 2 == a->radius;
+}
+
+static int stitch_interior_map(const Stitch &st) {
+    const pano_stitch_args *a = st.a;
+    if (st.classes) {
+        int radii[PANO_MAX_LEVELS];
+        for (int k = 0; k < st.n_blur; ++k) radii[k] = a->ntaps[k] / 2;
+        return pano_interior_classes(st.ctx, a->owner, a->H, a->W, a->own0, a->own1, radii,
+                                     st.n_blur, a->block_owner, a->interior, a->classes);
+    }
+    return pano_interior_map(st.ctx, a->owner, a->H, a->W, a->own0, a->own1, a->radius,
+                             a->block_owner, a->interior);
 }
 
 // Runs `call` with the context targeted at its side stream.
@@ -236,11 +224,14 @@ static bool stitch_has_classes(const pano_ctx *ctx, const pano_stitch_args *a, i
 // the tile flags / warp-need flags, the warp, the blur's work list, the blur, the collapse.
 // `lay`: the layout, or - device layout - the bounds the launches are sized by.
 // `kept`: the tile flags, the warp-need flags and the blur's work list are the previous stitch's
-// (kept geometry): only the warp, the blur and the collapse are queued.
-static int queue_tail(pano_ctx *ctx, pano_stitch_args *a, const pano_layout &lay, bool device_table,
-                      int need_choice, bool two_streams, bool interior, int n_blur, int tile_grid,
+// (kept geometry): only the warp, the blur and the collapse are queued, on one stream.
+static int queue_tail(const Stitch &st, const pano_layout &lay, bool device_table, int need_choice,
                       bool kept = false) {
+    pano_ctx *ctx = st.ctx;
+    pano_stitch_args *a = st.a;
     const hipStream_t s = ctx->stream;
+    const bool interior = st.interior, two_streams = st.two_streams && !kept;
+    const int n_blur = st.n_blur;
     const bool use_blur = n_blur > 0 && lay.n_records > 0;
     const int nr = lay.n_records;
     if (!device_table) {
@@ -263,8 +254,7 @@ static int queue_tail(pano_ctx *ctx, pano_stitch_args *a, const pano_layout &lay
     a->used_need = 0;
     if (kept) {
         a->used_need = need_choice == 1;
-        two_streams = false;
-    } else if (interior && tile_grid == 32 && nr && a->tile_flags && a->need) {
+    } else if (interior && st.tile_grid == 32 && nr && a->tile_flags && a->need) {
         bool on = need_choice == 1;
         if (need_choice < 0) {
             double sum = 0.0;
@@ -283,7 +273,7 @@ static int queue_tail(pano_ctx *ctx, pano_stitch_args *a, const pano_layout &lay
         }
     }
     const bool fork2 = two_streams && interior && n_blur && nr &&
-                       !a->used_need && tile_grid == 32 && a->tile_flags;
+                       !a->used_need && st.tile_grid == 32 && a->tile_flags;
     if (fork2) {            // the blur's tile flags and sorted work list beside the warp
         if (device_table) {                                      // behind the layout kernel
             PANO_HIP(hipEventRecord(ctx->ev_upload, s));
@@ -312,7 +302,7 @@ static int queue_tail(pano_ctx *ctx, pano_stitch_args *a, const pano_layout &lay
             return rc;
     return pano_multiband_compose(ctx, a->table, nr, a->H, a->W, a->xs0, a->xs1, a->n_levels,
                                   a->owner, a->valid, interior ? a->interior : nullptr,
-                                  interior && stitch_has_classes(ctx, a, n_blur) ? a->classes : nullptr,
+                                  st.classes ? a->classes : nullptr,
                                   interior ? a->cams : nullptr, interior ? a->sin_t : nullptr,
                                   interior ? a->cos_t : nullptr, interior ? a->tan_p : nullptr,
                                   a->lut, a->lut_stride, a->mosaic, a->mosaic_f32);
@@ -324,9 +314,202 @@ static void geometry_buffers(const pano_stitch_args *a, const void *out[GEOM_BUF
                                 a->planes, a->blurred, a->scratch, a->sin_t, a->classes};
     for (int k = 0; k < GEOM_BUFS; ++k) out[k] = v[k];
 }
-static void geometry_left(pano_ctx *ctx, const pano_stitch_args *a) {
-    geometry_buffers(a, ctx->geom_bufs);
-    ctx->geom_valid = true;
+static void geometry_left(const Stitch &st) {
+    geometry_buffers(st.a, st.ctx->memo.geom_bufs);
+    st.ctx->memo.geom_valid = true;
+}
+
+// Ownership and, in the same pass, one record per (camera, span of columns it owns): boxes and
+// column marks out of the ownership kernel, then the spans' search.  (Rounds 3 - 4 took the one
+// pass on mosaics of 16 MP and more only; with round 5's ownership kernel it is as fast or faster
+// on every size - config 2 0.449 / 0.451 ms per stitch, a world-8 strip of config 3 0.321 against
+// 0.331: the separate box kernel's 30 us were a quarter of a strip's ownership -
+// profiles/r05/ab_regions_fused_*.txt.)
+// Two small chains depend on the owner map only - the interior map and the region search's tail -
+// and two more on the record table only - the warp and the blur's tile flags and work list: the
+// context's side stream takes one of each pair (the short kernels of a config-3 stitch were
+// 0.15 ms of a 2.0 ms timeline, plus the gaps between them).  With one stream the interior map is
+// left to the route: each queues it where it keeps the GPU busy.
+static int queue_ownership(const Stitch &st) {
+    pano_ctx *ctx = st.ctx;
+    const pano_stitch_args *a = st.a;
+    if (int rc = pano_ownership_regions(ctx, a->cams, a->n, a->H, a->W, a->own0, a->own1, a->sin_t,
+                                        a->cos_t, a->tan_p, a->owner, a->valid, a->min_gap,
+                                        a->max_spans, a->marks, a->regions))
+        return rc;
+    if (st.two_streams && st.interior) {
+        PANO_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
+        PANO_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        ON_SIDE(ctx, stitch_interior_map(st));
+    }
+    return PANO_OK;
+}
+
+// The device routes (both imply the interior shortcut): ownership, the layout kernel with the
+// launch bounds `bound`, and the tail behind it sized by those.  `trusted`: the kernel compares its
+// layout with the verified one, and the records are not copied to the caller.
+static int queue_device_layout(const Stitch &st, const pano_layout &bound, bool trusted) {
+    pano_ctx *ctx = st.ctx;
+    pano_stitch_args *a = st.a;
+    const hipStream_t s = ctx->stream;
+    if (int rc = ensure_layout_buffers(ctx, a->n)) return rc;
+    // rectangles and resident flags for the layout kernel: uploaded when they changed,
+    // in front of the ownership kernel (off the critical path)
+    const size_t nrect = (size_t)a->n * 4;
+    if (ctx->lay_rects_host.size() != nrect ||
+        memcmp(ctx->lay_rects_host.data(), a->rects, nrect * sizeof(int32_t)) != 0) {
+        ctx->lay_rects_host.assign(a->rects, a->rects + nrect);
+        PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_RECTS].p, ctx->lay_rects_host.data(),
+                                nrect * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    std::vector<uint8_t> have(a->n, 1);
+    if (a->have) have.assign(a->have, a->have + a->n);
+    if (ctx->lay_have_host != have) {
+        ctx->lay_have_host = have;
+        PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_HAVE].p, ctx->lay_have_host.data(), (size_t)a->n,
+                                hipMemcpyHostToDevice, s));
+    }
+    if (int rc = queue_ownership(st)) return rc;
+    if (ctx->upload_pending) {                           // records_host may be in use
+        PANO_HIP(hipEventSynchronize(ctx->ev_upload));
+        ctx->upload_pending = false;
+    }
+    uintptr_t bbase = (uintptr_t)a->blurred;             // as pano_layout_place aligns it
+    bbase += (uintptr_t)(-(intptr_t)bbase) % 128;
+    hipLaunchKernelGGL(layout_windows_kernel, dim3(1), dim3(LAY_THREADS), 0, s, a->regions,
+                       (const int32_t *)ctx->buf[BUF_LAY_RECTS].p,
+                       (const uint8_t *)ctx->buf[BUF_LAY_HAVE].p, a->n, a->max_spans, a->radius,
+                       a->xs0, a->xs1, st.n_blur, 1, a->planes, (float *)bbase, a->scratch,
+                       (long)a->planes_floats, (long)a->blurred_floats, (long)a->scratch_floats,
+                       a->cap_tiles, 1, bound.n_records, bound.max_vw, bound.max_vh, bound.max_aw,
+                       bound.max_ah, a->table, lay_sum_host(ctx), ctx->memo.lay, trusted ? 1 : 0,
+                       layout_sticky(ctx));
+    PANO_LAUNCH_CHECK("layout_windows_kernel");
+    // the summary goes straight into pinned host memory; the caller's copy of the records
+    // leaves through the side stream: nothing stands between this kernel and the warp
+    PANO_HIP(hipEventRecord(ctx->ev_regions, s));
+    if (!trusted) {
+        PANO_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_regions, 0));
+        PANO_HIP(hipMemcpyAsync(a->records_host, a->table, (size_t)bound.n_records * sizeof(pano_patch),
+                                hipMemcpyDeviceToHost, ctx->side));
+        PANO_HIP(hipEventRecord(ctx->ev_copy, ctx->side));
+    }
+    if (!st.two_streams)
+        if (int rc = stitch_interior_map(st)) return rc;
+    return queue_tail(st, bound, true, ctx->memo.used_need);
+}
+
+// Kept geometry: the owner map, the valid mask, the interior map, the record table, the tile flags
+// and the blur's work list are functions of the cameras, rectangles, strip and resident frames
+// alone - what the caller vouches for - and lie untouched where this context's previous stitch
+// left them: the frames' pixels go through the warp, the blur and the collapse, nothing else is
+// queued.
+static int stitch_kept(const Stitch &st) {
+    StitchMemo &memo = st.ctx->memo;
+    if (int rc = queue_tail(st, memo.lay, true, memo.used_need, true)) return rc;
+    st.a->layout = memo.lay;
+    st.a->trust_layout = PANO_TRUST_KEPT;                // nobody waited
+    memo.geom_valid = true;
+    ++memo.count[0];
+    return PANO_OK;
+}
+
+// The caller vouches that cameras, rectangles, strip and resident frames are those of this
+// context's previous stitch, whose layout was read and verified: the owner map, the regions and so
+// the layout are functions of exactly those, the kernels are queued with that layout's own bounds,
+// and nobody waits - the summary this stitch's layout kernel writes is compared with the verified
+// one at the next untrusted call or in pano_stitch_verify.
+static int stitch_trusted(const Stitch &st) {
+    StitchMemo &memo = st.ctx->memo;
+    if (int rc = queue_device_layout(st, memo.lay, true)) return rc;
+    st.a->layout = memo.lay;
+    st.a->used_need = memo.used_need;
+    st.a->trust_layout = PANO_TRUST_TRUSTED;             // went through without a wait
+    memo.trusted_pending = true;
+    geometry_left(st);
+    ++memo.count[0];
+    return PANO_OK;
+}
+
+// The layout on the device with launch bounds from what the previous layout needed, with slack for
+// cameras that move; the host reads the summary while the GPU works.  `*fits` = 0: this layout
+// needs more than the launches covered (or an arena is too small): the table was emptied, the
+// queued tail did nothing, and the caller goes on into the host layout.
+static int stitch_device(const Stitch &st, bool *fits) {
+    pano_ctx *ctx = st.ctx;
+    pano_stitch_args *a = st.a;
+    StitchMemo &memo = ctx->memo;
+    pano_layout bound = memo.lay;
+    bound.n_records = bound.n_records + 2 < a->cap_records ? bound.n_records + 2 : a->cap_records;
+    bound.max_vw += 64, bound.max_vh += 64, bound.max_aw += 64, bound.max_ah += 64;
+    if (ctx->opt[PANO_OPT_STITCH_ASYNC] == 2) {          // tests: bounds this layout exceeds
+        bound.n_records = memo.lay.n_records > 1 ? memo.lay.n_records - 1 : 1;
+        bound.max_vw = memo.lay.max_vw - 1;
+    }
+    if (int rc = queue_device_layout(st, bound, false)) return rc;
+    PANO_HIP(hipEventSynchronize(ctx->ev_regions));      // the GPU is in the warp by now
+    PANO_HIP(hipEventSynchronize(ctx->ev_copy));
+    const LayoutSummary sum = *lay_sum_host(ctx);
+    a->layout = sum.lay;
+    *fits = sum.ok != 0;
+    if (sum.ok) {
+        memo.lay = a->layout;
+        memo.used_need = a->used_need;
+        memo.verified = true;
+        geometry_left(st);
+        ++memo.count[0];
+    } else {
+        ++memo.count[1];
+        stitch_memo_void_layout(memo);
+    }
+    return PANO_OK;
+}
+
+// The layout on the host, from the regions (`owner_queued`: behind a device layout that did not
+// fit, whose ownership pass and interior map stand), then - where a call with `resume` enters,
+// its arenas grown after PANO_EGROW - the tail, and what the next stitch is told.
+static int stitch_host(const Stitch &st, bool resume, bool owner_queued) {
+    pano_ctx *ctx = st.ctx;
+    pano_stitch_args *a = st.a;
+    const hipStream_t s = ctx->stream;
+    if (!resume) {
+        if (!owner_queued)
+            if (int rc = queue_ownership(st)) return rc;
+        PANO_HIP(hipMemcpyAsync(a->regions_host, a->regions,
+                                (size_t)a->n * (5 + 2 * a->max_spans) * sizeof(int32_t),
+                                hipMemcpyDeviceToHost, s));
+        PANO_HIP(hipEventRecord(ctx->ev_regions, s));
+        // the interior map needs the owner map only: queued before the wait, it keeps the GPU
+        // busy while the host lays out the windows
+        if (st.interior && !st.two_streams && !owner_queued)
+            if (int rc = stitch_interior_map(st)) return rc;
+        PANO_HIP(hipEventSynchronize(ctx->ev_regions));          // the one wait of a stitch
+        if (ctx->upload_pending) {                               // records_host may be in use
+            PANO_HIP(hipEventSynchronize(ctx->ev_upload));
+            ctx->upload_pending = false;
+        }
+        a->layout = pano_layout{};
+        if (int rc = pano_layout_windows(st.tile_grid, a->regions_host, a->n, a->max_spans, a->rects,
+                                         a->have, a->radius, a->xs0, a->xs1, st.n_blur,
+                                         a->records_host, a->cap_records, &a->layout))
+            return rc;
+        if (a->layout.missing) {
+            pano_set_error("pano_stitch_multiband: %d records of cameras whose frames are not "
+                           "resident reach columns [%d, %d)", a->layout.missing, a->xs0, a->xs1);
+            return PANO_EINVAL;
+        }
+    }
+    const int rc = queue_tail(st, a->layout, false, a->warp_need);
+    if (rc == PANO_OK) {                     // what this layout needed: the next stitch's bounds
+        StitchMemo &memo = ctx->memo;
+        memo.lay = a->layout;
+        memcpy(memo.sig, st.sig, sizeof(memo.sig));
+        memo.used_need = a->used_need;
+        memo.valid = true;
+        memo.verified = true;                // laid out on the host from this stitch's own regions
+        geometry_left(st);
+    }
+    return rc;
 }
 
 namespace {
@@ -338,9 +521,10 @@ struct StitchScope {                 // the stitch's own nested calls do not voi
 }  // namespace
 
 extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int resume) {
-    const bool geom_was_valid = ctx && ctx->geom_valid;  // (PANO_ENTER is a foreign call's entry too)
+    const bool geom_was_valid = ctx && ctx->memo.geom_valid;  // (PANO_ENTER is a foreign call's entry too)
     PANO_ENTER(ctx, "pano_stitch_multiband");
-    ctx->geom_valid = false;
+    StitchMemo &memo = ctx->memo;
+    stitch_memo_void_geometry(memo);
     StitchScope scope(ctx);
     PANO_REQUIRE(a, "pano_stitch_multiband: null arguments");
     PANO_REQUIRE(a->cams && a->rects && a->sin_t && a->cos_t && a->tan_p && a->lut && a->owner &&
@@ -362,220 +546,54 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
     const bool interior = a->shortcut && n_blur > 0;
     PANO_REQUIRE(!interior || (a->block_owner && a->interior),
                  "pano_stitch_multiband: interior map without its buffers");
-    const hipStream_t s = (hipStream_t)stream;
     if (int rc = pano_ctx_side_stream(ctx)) return rc;
     // the second stream pays on large mosaics only (config 3: 1.975 -> 1.945 ms per stitch;
     // config 2, 7.9 MP: 0.527 -> 0.537: the forks and joins cost more than the overlap gives)
     // (round 5, with trusted layouts: still nothing below - a world-8 strip 0.363 against 0.362 ms,
     // config 2 0.50 against 0.444; profiles/r05/visit_p_*.txt)
     const bool big = (long long)a->H * (a->own1 - a->own0) >= (1ll << 24);
-    const bool two_streams = ctx->opt[PANO_OPT_STITCH_STREAMS] != 0 && big;
     const int tile_grid = pano_blur_tile_grid(ctx);
-    const int stride = 5 + 2 * a->max_spans;
-    int sig[STITCH_SIG];
-    stitch_signature(a, tile_grid, sig);
-
+    const Stitch st = {ctx, a, n_blur, tile_grid, interior,
+                       ctx->opt[PANO_OPT_STITCH_STREAMS] != 0 && big,
+                       interior && stitch_has_classes(ctx, a, n_blur),
+                       {a->n, a->H, a->W, a->xs0, a->xs1, a->own0, a->own1, a->n_levels, a->radius,
+                        a->max_spans, a->shortcut, a->min_gap, tile_grid}};
+    bool owner_queued = false;
     if (!resume) {
-        // The layout on the device (option PANO_OPT_STITCH_ASYNC): for the default form of the
-        // stitch - interior shortcut, matrix-core blur - once a stitch of this shape has gone
-        // through and left its layout's needs behind.
-        bool spec = ctx->opt[PANO_OPT_STITCH_ASYNC] != 0 && interior && tile_grid == 32 &&
-                    ctx->lay_prev_valid && memcmp(sig, ctx->lay_prev_sig, sizeof(sig)) == 0 &&
-                    ctx->lay_prev.n_records > 0 && a->planes && a->blurred && a->tile_flags;
-        pano_layout bound = ctx->lay_prev;
-        // a trusted stitch (args->trust_layout = 1, see below) needs the verified layout of the
-        // same shape; its summary is checked first if one is still pending
-        const bool want_keep = a->trust_layout == 3;
-        const bool want_trust = a->trust_layout == 1 || want_keep;
-        a->trust_layout = 0;
-        if (ctx->trusted_pending && !(want_trust && spec))
+        const void *bufs[GEOM_BUFS];
+        geometry_buffers(a, bufs);
+        StitchFacts f;
+        f.async = ctx->opt[PANO_OPT_STITCH_ASYNC];
+        f.interior = interior;
+        f.grid32 = tile_grid == 32;
+        f.memo_valid = memo.valid;
+        f.sig_equal = memcmp(st.sig, memo.sig, sizeof(st.sig)) == 0;
+        f.prev_records = memo.lay.n_records > 0;
+        f.arenas_given = a->planes && a->blurred && a->tile_flags;
+        f.request = a->trust_layout;
+        f.verified = memo.verified;
+        f.pending = memo.trusted_pending;
+        f.geom_was_valid = geom_was_valid;
+        // (while the work list in the context's buffers is the one the previous stitch built for
+        // this very table: an option switch voids it, pano_ctx_set_option)
+        f.list_kept = n_blur == 0 || memo.lay.n_records == 0 ||
+                      (ctx->buf[BUF_ITEM_LIST].p && ctx->list_table == a->table &&
+                       ctx->list_n == memo.lay.n_records);
+        f.bufs_equal = memcmp(bufs, memo.geom_bufs, sizeof(bufs)) == 0;
+        const StitchMode mode = stitch_mode(f);
+        a->trust_layout = PANO_TRUST_NONE;
+        if (mode.verify_first)
             if (int rc = pano_stitch_verify(ctx)) return rc;
-        const bool trusted = want_trust && spec && ctx->lay_prev_verified &&
-                             ctx->opt[PANO_OPT_STITCH_ASYNC] == 1;
-        // (kept: only on the matrix-core grid - `spec` says so - and only while the work list in
-        // the context's buffers is the one the previous stitch built for this very table: an
-        // option switch voids it, pano_ctx_set_option)
-        const bool list_kept = n_blur == 0 || ctx->lay_prev.n_records == 0 ||
-                               (ctx->buf[BUF_ITEM_LIST].p && ctx->list_table == a->table &&
-                                ctx->list_n == ctx->lay_prev.n_records);
-        if (want_keep && trusted && geom_was_valid && tile_grid == 32 && list_kept) {
-            // Kept geometry: the owner map, the valid mask, the interior map, the record table, the
-            // tile flags and the blur's work list are functions of the cameras, rectangles, strip and
-            // resident frames alone - what the caller vouches for - and lie untouched where this
-            // context's previous stitch left them: the frames' pixels go through the warp, the blur
-            // and the collapse, nothing else is queued.
-            const void *bufs[GEOM_BUFS];
-            geometry_buffers(a, bufs);
-            if (memcmp(bufs, ctx->geom_bufs, sizeof(bufs)) == 0) {
-                if (int rc = queue_tail(ctx, a, ctx->lay_prev, true, ctx->lay_prev_used_need, false,
-                                        interior, n_blur, tile_grid, true))
-                    return rc;
-                a->layout = ctx->lay_prev;
-                a->trust_layout = 4;                             // out: geometry kept, nobody waited
-                ctx->geom_valid = true;
-                ++ctx->lay_count[0];
-                return PANO_OK;
-            }
-        }
-        if (spec) {
-            if (int rc = ensure_layout_buffers(ctx, a->n)) return rc;
-            // rectangles and resident flags for the layout kernel: uploaded when they changed,
-            // in front of the ownership kernel (off the critical path)
-            const size_t nrect = (size_t)a->n * 4;
-            if (ctx->lay_rects_host.size() != nrect ||
-                memcmp(ctx->lay_rects_host.data(), a->rects, nrect * sizeof(int32_t)) != 0) {
-                ctx->lay_rects_host.assign(a->rects, a->rects + nrect);
-                PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_RECTS].p, ctx->lay_rects_host.data(),
-                                        nrect * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            }
-            std::vector<uint8_t> have(a->n, 1);
-            if (a->have) have.assign(a->have, a->have + a->n);
-            if (ctx->lay_have_host != have) {
-                ctx->lay_have_host = have;
-                PANO_HIP(hipMemcpyAsync(ctx->buf[BUF_LAY_HAVE].p, ctx->lay_have_host.data(), (size_t)a->n,
-                                        hipMemcpyHostToDevice, s));
-            }
-            // launch bounds: what the previous layout needed, with slack for cameras that move
-            // (a trusted stitch repeats that layout exactly)
-            if (!trusted) {
-                bound.n_records = bound.n_records + 2 < a->cap_records ? bound.n_records + 2 : a->cap_records;
-                bound.max_vw += 64, bound.max_vh += 64, bound.max_aw += 64, bound.max_ah += 64;
-            }
-            if (ctx->opt[PANO_OPT_STITCH_ASYNC] == 2) {          // tests: bounds this layout exceeds
-                bound.n_records = ctx->lay_prev.n_records > 1 ? ctx->lay_prev.n_records - 1 : 1;
-                bound.max_vw = ctx->lay_prev.max_vw - 1;
-            }
-        }
-        // ownership and, in the same pass, one record per (camera, span of columns it owns):
-        // boxes and column marks out of the ownership kernel, then the spans' search.  (Rounds 3 - 4
-        // took the one pass on mosaics of 16 MP and more only; with round 5's ownership kernel it is
-        // as fast or faster on every size - config 2 0.449 / 0.451 ms per stitch, a world-8 strip of
-        // config 3 0.321 against 0.331: the separate box kernel's 30 us were a quarter of a strip's
-        // ownership - profiles/r05/ab_regions_fused_*.txt.)
-        if (int rc = pano_ownership_regions(ctx, a->cams, a->n, a->H, a->W, a->own0, a->own1,
-                                            a->sin_t, a->cos_t, a->tan_p, a->owner, a->valid,
-                                            a->min_gap, a->max_spans, a->marks, a->regions))
-            return rc;
-        // Two small chains depend on the owner map only - the interior map and the region
-        // search's tail - and two more on the record table only - the warp and the blur's tile
-        // flags and work list: the context's side stream takes one of each pair (the short
-        // kernels of a config-3 stitch were 0.15 ms of a 2.0 ms timeline, plus the gaps between
-        // them).
-        const bool forked = two_streams;
-        if (forked && interior) {
-            PANO_HIP(hipEventRecord(ctx->ev_fork, s));
-            PANO_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-            ON_SIDE(ctx, stitch_interior_map(ctx, a, n_blur));
-        }
-        bool interior_queued = forked && interior;
-        if (spec) {
-            if (ctx->upload_pending) {                           // records_host may be in use
-                PANO_HIP(hipEventSynchronize(ctx->ev_upload));
-                ctx->upload_pending = false;
-            }
-            uintptr_t bbase = (uintptr_t)a->blurred;             // as pano_layout_place aligns it
-            bbase += (uintptr_t)(-(intptr_t)bbase) % 128;
-            hipLaunchKernelGGL(layout_windows_kernel, dim3(1), dim3(LAY_THREADS), 0, s, a->regions,
-                               (const int32_t *)ctx->buf[BUF_LAY_RECTS].p,
-                               (const uint8_t *)ctx->buf[BUF_LAY_HAVE].p, a->n, a->max_spans, a->radius,
-                               a->xs0, a->xs1, n_blur, 1, a->planes, (float *)bbase, a->scratch,
-                               (long)a->planes_floats, (long)a->blurred_floats,
-                               (long)a->scratch_floats, a->cap_tiles, 1, bound.n_records,
-                               bound.max_vw, bound.max_vh, bound.max_aw, bound.max_ah, a->table,
-                               lay_sum_host(ctx), layout_expectation(ctx->lay_prev), trusted ? 1 : 0,
-                               layout_sticky(ctx));
-            PANO_LAUNCH_CHECK("layout_windows_kernel");
-            // the summary goes straight into pinned host memory; the caller's copy of the records
-            // leaves through the side stream: nothing stands between this kernel and the warp
-            PANO_HIP(hipEventRecord(ctx->ev_regions, s));
-            if (!trusted) {
-                PANO_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_regions, 0));
-                PANO_HIP(hipMemcpyAsync(a->records_host, a->table,
-                                        (size_t)bound.n_records * sizeof(pano_patch),
-                                        hipMemcpyDeviceToHost, ctx->side));
-                PANO_HIP(hipEventRecord(ctx->ev_copy, ctx->side));
-            }
-            if (interior && !interior_queued) {
-                if (int rc = stitch_interior_map(ctx, a, n_blur)) return rc;
-                interior_queued = true;
-            }
-            if (int rc = queue_tail(ctx, a, bound, true, ctx->lay_prev_used_need, two_streams, interior,
-                                    n_blur, tile_grid))
-                return rc;
-            if (trusted) {
-                // The caller vouches that cameras, rectangles, strip and resident frames are those
-                // of this context's previous stitch, whose layout was read and verified: the owner
-                // map, the regions and so the layout are functions of exactly those, the kernels
-                // were queued with that layout's own bounds, and nobody waits - the summary this
-                // stitch's layout kernel writes is compared with the verified one at the next
-                // untrusted call or in pano_stitch_verify.
-                a->layout = ctx->lay_prev;
-                a->used_need = ctx->lay_prev_used_need;
-                a->trust_layout = 2;                             // out: went through without a wait
-                ctx->trusted_pending = true;
-                geometry_left(ctx, a);
-                ++ctx->lay_count[0];
-                return PANO_OK;
-            }
-            PANO_HIP(hipEventSynchronize(ctx->ev_regions));      // the GPU is in the warp by now
-            PANO_HIP(hipEventSynchronize(ctx->ev_copy));
-            const LayoutSummary sum = *lay_sum_host(ctx);
-            a->layout.planes_floats = sum.planes_floats;
-            a->layout.blurred_floats = sum.blurred_floats;
-            a->layout.scratch_floats = sum.scratch_floats;
-            a->layout.n_records = sum.n_records, a->layout.n_tiles = sum.n_tiles;
-            a->layout.max_vw = sum.max_vw, a->layout.max_vh = sum.max_vh;
-            a->layout.max_aw = sum.max_aw, a->layout.max_ah = sum.max_ah;
-            a->layout.missing = sum.missing;
-            if (sum.ok) {
-                ctx->lay_prev = a->layout;
-                ctx->lay_prev_used_need = a->used_need;
-                ctx->lay_prev_verified = true;
-                geometry_left(ctx, a);
-                ++ctx->lay_count[0];
-                return PANO_OK;
-            }
-            ++ctx->lay_count[1];
-            // this layout needs more than the launches covered (or an arena is too small): the
-            // table was emptied, the queued tail did nothing; lay it out on the host and queue
-            // the tail again
-            ctx->lay_prev_valid = false;
-            ctx->lay_prev_verified = false;
-        }
-        PANO_HIP(hipMemcpyAsync(a->regions_host, a->regions, (size_t)a->n * stride * sizeof(int32_t),
-                                hipMemcpyDeviceToHost, s));
-        PANO_HIP(hipEventRecord(ctx->ev_regions, s));
-        // the interior map needs the owner map only: queued before the wait, it keeps the GPU
-        // busy while the host lays out the windows
-        if (interior && !interior_queued)
-            if (int rc = stitch_interior_map(ctx, a, n_blur)) return rc;
-        PANO_HIP(hipEventSynchronize(ctx->ev_regions));          // the one wait of a stitch
-        if (ctx->upload_pending) {                               // records_host may be in use
-            PANO_HIP(hipEventSynchronize(ctx->ev_upload));
-            ctx->upload_pending = false;
-        }
-        a->layout = pano_layout{};
-        if (int rc = pano_layout_windows(tile_grid, a->regions_host, a->n, a->max_spans, a->rects,
-                                         a->have, a->radius, a->xs0, a->xs1, n_blur,
-                                         a->records_host, a->cap_records, &a->layout))
-            return rc;
-        if (a->layout.missing) {
-            pano_set_error("pano_stitch_multiband: %d records of cameras whose frames are not "
-                           "resident reach columns [%d, %d)", a->layout.missing, a->xs0, a->xs1);
-            return PANO_EINVAL;
+        if (mode.route == ROUTE_KEPT) return stitch_kept(st);
+        if (mode.route == ROUTE_TRUSTED) return stitch_trusted(st);
+        if (mode.route == ROUTE_DEVICE) {
+            bool fits = false;
+            const int rc = stitch_device(st, &fits);
+            if (rc || fits) return rc;
+            owner_queued = true;
         }
     }
-    const int rc = queue_tail(ctx, a, a->layout, false, a->warp_need, two_streams, interior, n_blur,
-                              tile_grid);
-    if (rc == PANO_OK) {                     // what this layout needed: the next stitch's bounds
-        ctx->lay_prev = a->layout;
-        memcpy(ctx->lay_prev_sig, sig, sizeof(sig));
-        ctx->lay_prev_used_need = a->used_need;
-        ctx->lay_prev_valid = true;
-        ctx->lay_prev_verified = true;       // laid out on the host from this stitch's own regions
-        geometry_left(ctx, a);
-    }
-    return rc;
+    return stitch_host(st, resume != 0, owner_queued);
 }
 
 // The summary the LAST trusted stitch's layout kernel wrote against the verified layout those
@@ -585,26 +603,21 @@ extern "C" int pano_stitch_multiband(pano_ctx *ctx, pano_stitch_args *a, int res
 // stitch's layout kernel (an event long past when mosaics are collected a stitch later).
 extern "C" int pano_stitch_verify(pano_ctx *ctx) {
     PANO_REQUIRE(ctx, "pano_stitch_verify: null context");
-    if (!ctx->trusted_pending) return PANO_OK;
+    StitchMemo &memo = ctx->memo;
+    if (!memo.trusted_pending) return PANO_OK;
     PANO_HIP(hipSetDevice(ctx->device));                 // (writes no buffer: kept geometry stays)
     PANO_HIP(hipEventSynchronize(ctx->ev_regions));
-    ctx->trusted_pending = false;
+    memo.trusted_pending = false;
     const LayoutSummary sum = *lay_sum_host(ctx);
-    const pano_layout &v = ctx->lay_prev;
     // (the last trusted stitch's summary, and the sticky word every trusted stitch before it left)
     const int sticky = __atomic_exchange_n(layout_sticky(ctx), 0, __ATOMIC_SEQ_CST);
-    const bool same = !sticky && sum.ok && sum.planes_floats == v.planes_floats &&
-                      sum.blurred_floats == v.blurred_floats && sum.scratch_floats == v.scratch_floats &&
-                      sum.n_records == v.n_records && sum.n_tiles == v.n_tiles &&
-                      sum.max_vw == v.max_vw && sum.max_vh == v.max_vh && sum.max_aw == v.max_aw &&
-                      sum.max_ah == v.max_ah && sum.missing == 0;
-    if (!same) {
-        ctx->lay_prev_valid = ctx->lay_prev_verified = false;
-        ctx->geom_valid = false;
+    if (sticky || !layout_as_verified(sum, memo.lay)) {
+        stitch_memo_void_layout(memo);
+        stitch_memo_void_geometry(memo);
         pano_set_error("pano_stitch_verify: a trusted stitch laid out %d records (ok %d, why %d, an "
                        "earlier one differed: %d) where the verified layout has %d: the cameras were "
                        "not those of the verified stitch",
-                       sum.n_records, sum.ok, sum.why, sticky, v.n_records);
+                       sum.lay.n_records, sum.ok, sum.why, sticky, memo.lay.n_records);
         return PANO_EINVAL;
     }
     return PANO_OK;
@@ -612,7 +625,7 @@ extern "C" int pano_stitch_verify(pano_ctx *ctx) {
 
 extern "C" int pano_stitch_counts(const pano_ctx *ctx, int *device_layouts, int *fallbacks) {
     PANO_REQUIRE(ctx && device_layouts && fallbacks, "pano_stitch_counts: null pointer");
-    *device_layouts = ctx->lay_count[0];
-    *fallbacks = ctx->lay_count[1];
+    *device_layouts = ctx->memo.count[0];
+    *fallbacks = ctx->memo.count[1];
     return PANO_OK;
 }

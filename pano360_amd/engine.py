@@ -8,6 +8,7 @@ Reference lines mirrored by the planning code: stitcher.py:107-157 (ranges,
 resolution), :283-302 (mosaic shape, patch rectangles, angle grids), :218
 (level sigmas); OpenCV's getGaussianKernel for the taps (host, 33..97 floats).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -17,6 +18,8 @@ from ._lib import Patch, _ptr   # noqa: F401  (_ptr: tests and tools make raw ca
 
 BORDER_SAMPLES = 100        # stitcher.py:109
 MULTIBAND_PAD = 10          # stitcher.py:296-297
+# The last verified stitch of an engine (Engine._stitch_native): what a trusted repeat rides on
+VerifiedStitch = collections.namedtuple("VerifiedStitch", "signature plan patches owner valid")
 
 
 # --------------------------------------------------------------- projections
@@ -657,11 +660,11 @@ class Engine:
         # ``keep_geometry`` (with trusted stitches): such a repeat also re-uses what the previous
         # stitch left on the device - owner map, valid mask, interior map, record table, tile
         # flags, the blur's work list, all functions of the same inputs - and queues the warp, the
-        # blur and the collapse alone (trust_layout = 3).  The owner / valid tensors are then the
+        # blur and the collapse alone (TRUST_GEOMETRY).  The owner / valid tensors are then the
         # SAME tensors from stitch to stitch: read-only for the caller.
         self.keep_geometry = False
         self.last_kept_geometry = False
-        self._trusted = None            # (signature, Plan, FusedPatches, owner, valid) of the last verified stitch
+        self._trusted = None            # the last verified stitch (VerifiedStitch)
 
     def __del__(self):
         ctx, self._ctx = getattr(self, "_ctx", None), None
@@ -1274,6 +1277,11 @@ class Engine:
             self._stitch_ws[key] = ws
         return ws
 
+    def _stitch_signature(self, form, ws):
+        """What makes a stitch a repeat of the verified one: its ``form`` and the buffers it runs in."""
+        return form + (tuple(id(self._arenas.get(k)) for k in ("planes", "blurred", "scratch")),
+                       id(ws["tiles"]))
+
     def _stitch_native(self, plan, cams, have, n_levels, want_float, strip, ext, shortcut, luts,
                        mosaic_out):
         """``multiband_fused`` through ``pano_stitch_multiband``: one native call queues the
@@ -1309,14 +1317,15 @@ class Engine:
         a.warp_need = {True: 1, False: 0}.get(self.warp_need, -1)
         a.max_spans, a.min_gap = max_spans, 2 * radius + 2
         # a repeat of the verified stitch (same Plan object and frames set, same strip and form)?
-        sig = (id(plan), strip, ext, n_levels, bool(shortcut), fl is not None, luts is None,
-               tuple(sorted(have)), tuple(id(self._arenas.get(k)) for k in ("planes", "blurred", "scratch")),
-               id(ws["tiles"]))
+        form = (id(plan), strip, ext, n_levels, bool(shortcut), fl is not None, luts is None,
+                tuple(sorted(have)))
         kept = self._trusted
-        repeat = (self.trust_layout and kept is not None and kept[0] == sig and kept[1] is plan)
-        a.trust_layout = (3 if self.keep_geometry else 1) if repeat else 0
+        repeat = (self.trust_layout and kept is not None
+                  and kept.signature == self._stitch_signature(form, ws) and kept.plan is plan)
+        a.trust_layout = ((_lib.TRUST_GEOMETRY if self.keep_geometry else _lib.TRUST_LAYOUT) if repeat
+                          else _lib.TRUST_NONE)
         if repeat and self.keep_geometry:
-            owner, valid = kept[3], kept[4]         # where the verified stitch left them
+            owner, valid = kept.owner, kept.valid   # where the verified stitch left them
         else:
             owner = torch.empty((H, W), dtype=torch.int16, device=self.device)
             valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
@@ -1349,13 +1358,12 @@ class Engine:
                                      f"{strip[1]}) but are not resident on this device")
             _lib.check(status, "pano_stitch_multiband")
         lay = a.layout
-        if a.trust_layout in (2, 4):
+        if a.trust_layout in (_lib.TRUST_TRUSTED, _lib.TRUST_KEPT):
             # queued with the verified layout, nobody waited: the records are the previous stitch's
-            # (4: and so are the owner map, the masks and the work list - nothing was recomputed)
-            patches = kept[2]
-            if self.keep_geometry:
-                self._trusted = kept[:3] + (owner, valid)
-            self.last_kept_geometry = a.trust_layout == 4
+            # (kept: and so are the owner map, the masks and the work list - nothing was recomputed)
+            # (a trusted repeat that keeps the geometry ran in kept.owner and kept.valid, see above)
+            patches = kept.patches
+            self.last_kept_geometry = a.trust_layout == _lib.TRUST_KEPT
         else:
             rec = ws["records_host"].numpy().view(PATCH_DTYPE)[:lay.n_records].copy()
             patches = FusedPatches.from_records(
@@ -1363,9 +1371,9 @@ class Engine:
                 tuple(self._arenas.get(k) for k in ("planes", "blurred", "scratch")))
             # (the signature holds the arenas and tile buffers as they are AFTER this stitch: a
             # stitch that grew one of them is not repeated blindly)
-            sig = sig[:-2] + (tuple(id(self._arenas.get(k)) for k in ("planes", "blurred", "scratch")),
-                              id(ws["tiles"]))
-            self._trusted = ((sig, plan, patches) + ((owner, valid) if self.keep_geometry else (None, None))
+            keep = self.keep_geometry
+            self._trusted = (VerifiedStitch(self._stitch_signature(form, ws), plan, patches,
+                                            owner if keep else None, valid if keep else None)
                              if self.trust_layout else None)
             self.last_kept_geometry = False
         if n_blur:

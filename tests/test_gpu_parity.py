@@ -468,22 +468,24 @@ def test_trusted_stitches_equal_waiting_ones_and_a_broken_promise_is_caught(stri
         trusting.verify_trusted()
     # the first stitch laid out on the host, the second on the device and waited (it verifies the
     # device layout), from the third on nobody waits
-    assert took[0] == 0 and took[-1] == 2 and took.count(2) >= 3, took
+    assert (took[0] == _lib.TRUST_NONE and took[-1] == _lib.TRUST_TRUSTED
+            and took.count(_lib.TRUST_TRUSTED) >= 3), took
     # a broken promise: other cameras under the kept signature
     rots2, _ = synth.make_cameras(n, w, h, sweep_deg=100.0, jitter=0.004, seed=2)
     other = trusting.upload_plan(engine.Plan(shapes, rots2, intrs, True, 10 ** 9))
     if other.shape == plan_t.shape:
-        sig, _, kept = trusting._trusted[:3]
-        trusting._trusted = ((id(other),) + sig[1:], other, kept) + trusting._trusted[3:]
+        sig = trusting._trusted.signature
+        trusting._trusted = trusting._trusted._replace(signature=(id(other),) + sig[1:], plan=other)
         trusting.multiband_fused(frames, other, 5, frame_ids=ids, strip=strip)
         if strip_case:
             # ... and a GOOD trusted stitch behind the bad one, before anybody verifies: the one
             # summary slot now holds the good stitch's layout, the bad one's lives on in the sticky
             # word its layout kernel set (a void mosaic must not pass because a later one is fine)
-            sig, _, kept = trusting._trusted[:3]
-            trusting._trusted = ((id(plan_t),) + sig[1:], plan_t, kept) + trusting._trusted[3:]
+            sig = trusting._trusted.signature
+            trusting._trusted = trusting._trusted._replace(signature=(id(plan_t),) + sig[1:], plan=plan_t)
             trusting.multiband_fused(frames, plan_t, 5, frame_ids=ids, strip=strip)
-            assert trusting._stitch_ws[next(iter(trusting._stitch_ws))]["args"].trust_layout == 2
+            assert (trusting._stitch_ws[next(iter(trusting._stitch_ws))]["args"].trust_layout
+                    == _lib.TRUST_TRUSTED)
         with pytest.raises(_lib.PanoError, match="verified"):
             trusting.verify_trusted()
     # ... after which the engine lays out from scratch and is right again
@@ -502,7 +504,7 @@ def test_kept_geometry_stitches_equal_waiting_ones(strip_case, equalised):
     image included; the ownership kernel does not run in a kept stitch; any other call through the
     context voids the kept geometry (the next stitch recomputes it, then keeps again)."""
     import torch
-    from pano360_amd import engine, synth
+    from pano360_amd import _lib, engine, synth
     n, w, h = 8, 480, 270
     rots, intrs = synth.make_cameras(n, w, h, sweep_deg=140.0, jitter=0.004, seed=1)
     shapes = [(h, w)] * n
@@ -533,7 +535,7 @@ def test_kept_geometry_stitches_equal_waiting_ones(strip_case, equalised):
         ran_ownership.append("ownership_cameras_kernel" in keeping.kernel_times())
         keeping.timing(False)
         took.append(keeping._stitch_ws[next(iter(keeping._stitch_ws))]["args"].trust_layout)
-        assert took[-1] == (4 if keeping.last_kept_geometry else took[-1])
+        assert took[-1] == (_lib.TRUST_KEPT if keeping.last_kept_geometry else took[-1])
         assert torch.equal(got[:, c0:c1], want[:, c0:c1]), (k, took)
         assert torch.equal(got_f[:, c0:c1], want_f[:, c0:c1]), (k, took)
         assert torch.equal(got_valid[:, c0:c1], want_valid[:, c0:c1]), (k, took)
@@ -541,8 +543,10 @@ def test_kept_geometry_stitches_equal_waiting_ones(strip_case, equalised):
         keeping.verify_trusted()
     # the first stitch lays out on the host and leaves its geometry; repeats keep it; the foreign
     # call before stitch 4 voids it once
-    assert took[0] == 0 and took[1] == 4 and took[3] == 4 and took[4] in (0, 2) and took[6] == 4, took
-    assert ran_ownership == [t != 4 for t in took], (ran_ownership, took)
+    none, trusted, kept = _lib.TRUST_NONE, _lib.TRUST_TRUSTED, _lib.TRUST_KEPT
+    assert (took[0] == none and took[1] == kept and took[3] == kept and took[4] in (none, trusted)
+            and took[6] == kept), took
+    assert ran_ownership == [t != kept for t in took], (ran_ownership, took)
 
 
 @pytest.mark.parametrize("seed", range(6))
