@@ -1585,6 +1585,77 @@ size_t pano_align_work_bytes(int h, int w, int k);
 int pano_align_mtb(pano_ctx *ctx, const pano_align_stack *stacks, int n, const pano_align_params *params,
                    void *work, int64_t work_bytes);
 
+/* Deghosting of exposure brackets before they are fused      (the reference takes one image per
+ * position; reference-guided and rank based; csrc/deghost.hip, NumPy statement:
+ * tests/deghost_model.py)
+ * Two exposures of a static scene differ by a monotone map of brightness, so a pixel's RANK within
+ * its own frame's histogram is nearly the same in both.  A pixel of exposure i whose rank disagrees
+ * with the reference exposure's shows other scene content; it is replaced by the reference's pixel,
+ * carried to exposure i's brightness through the histogram-matching map of the two frames.  A
+ * clipped pixel sits in a huge bin: its rank is an interval that agrees with anything in it.
+ * A stack is as for pano_align_mtb: k exposures (2 .. PANO_FUSE_MAX_EXPOSURES), uint8 [h][w][3] BGR
+ * of one size, sides 1 .. PANO_FUSE_MAX_SIDE, rows `pitch` bytes apart; `reference` 0 .. k - 1;
+ * N = h w.  Integers throughout; params: slack 0 .. 15 (the usual 3) grey levels of noise tolerated,
+ * tol 0 .. 255 (8) rank units of 1/255 tolerated, erode 0 .. 3 (1), dilate 0 .. 15 (3).
+ *   A, histograms: g = (29 B + 150 G + 77 R + 128) >> 8 (pano_align_mtb's grey); per frame uint32
+ *       hist[4][256] of g, B, G, R.
+ *   B, tables, per frame: below[v] = #{. < v}, v = 0 .. 256.  The rank interval of grey v:
+ *       lo[v] = below_g[max(v - slack, 0)] 255 / N, hi[v] = below_g[min(v + slack + 1, 256)] 255 / N,
+ *       64-bit products, floor division, both uint8.  The colour map onto frame i from the
+ *       reference r, per channel c: target = below_r,c[v] + (hist_r,c[v] + 1) / 2; map_i,c[v] = the
+ *       smallest u with below_i,c[u + 1] >= target (it exists: target <= N).  map_r is the identity.
+ *   C, raw mask, per frame i != r and pixel: set where lo_i[g_i] > hi_r[g_r] + tol or
+ *       lo_r[g_r] > hi_i[g_i] + tol.  Packed as pano_align_mtb's bitmaps: bit x & 31 of word x >> 5,
+ *       wpr = ceil(w / 32) words per row, the bits from w on 0.
+ *   D, clean-up: eroded by a (2 erode + 1)^2 square, pixels outside the image counting as set, then
+ *       dilated by a (2 dilate + 1)^2 square, pixels outside counting as clear; the bits from w on
+ *       are 0.  count[i] = the set bits; count[r] = 0.
+ *   E, apply, for every frame i != r with a dst and count[i] > 0:
+ *       dst[y][x][c] = mask ? map_i,c[ref[y][x][c]] : src[y][x][c].  The reference and frames with
+ *       a count of 0 are NOT copied: their dst is left as it was, the caller takes their src.  (The
+ *       counts stay on the device: the call waits for nothing, the tiles of such a frame leave.)
+ * pano_deghost_work_bytes(h, w, k): the workspace of one stack, callable without a GPU: with
+ *     p = w rounded up to a multiple of 4, wpr as above and a256 rounding up to a multiple of 256,
+ *       a256(4096 k) + a256(512 k) + a256(768 k) + k (a256(h p) + 2 a256(4 h wpr))
+ *     (histograms, rank tables, colour maps; per frame the grey image, the raw and the final
+ *     mask).  0 for a side or k out of range.
+ * pano_deghost_u8: ONE call takes n stacks of mixed sizes and k: one table of tiles over all their
+ *     frames, 5 launches for up to 256 frames (more: further passes of whole stacks), queued on the
+ *     context's stream, no host wait, no allocation.  `work` (dev, work_bytes long) holds ALL stacks
+ *     of the call: at least the sum of their pano_deghost_work_bytes; it need not be cleared.
+ *     stacks: HOST records; src, dst, counts and the stage outputs: dev.  counts: int32 [k], always
+ *     written.  dst[e] NULL: exposure e is not applied.  Stage outputs, NULL in production: hists
+ *     uint32 [k][4][256]; ranks uint8 [k][2][256] (lo, hi); maps uint8 [k][3][256]; raw and mask
+ *     uint32 [k][h][wpr] (the reference's are 0).  The counts are integer sums: two calls give the
+ *     same bytes, and a stack's result does not depend on what else is in the call.
+ *     PANO_EINVAL, with nothing launched or written: a null pointer (stacks, params, work, a src,
+ *     counts), n < 1, k outside 2 .. 8, a side outside 1 .. 32767, reference outside 0 .. k - 1,
+ *     slack outside 0 .. 15, tol outside 0 .. 255, erode outside 0 .. 3, dilate outside 0 .. 15, a
+ *     pitch below 3 w, work_bytes too small, a dst that overlaps a source frame of its stack or the
+ *     workspace. */
+typedef struct pano_deghost_stack {
+    const uint8_t *src[PANO_FUSE_MAX_EXPOSURES];   /* dev uint8 [h][w][3]; the first k are read   */
+    int64_t src_pitch[PANO_FUSE_MAX_EXPOSURES];    /* bytes between their rows                    */
+    uint8_t *dst[PANO_FUSE_MAX_EXPOSURES];         /* dev uint8 [h][w][3] per exposure, or NULL   */
+    int64_t dst_pitch[PANO_FUSE_MAX_EXPOSURES];
+    int32_t *counts;           /* dev int32 [k]: replaced pixels per exposure       */
+    uint32_t *hists;           /* stage outputs, dev or NULL                        */
+    uint8_t *ranks;
+    uint8_t *maps;
+    uint32_t *raw;
+    uint32_t *mask;
+    int32_t w, h, k, reference;
+} pano_deghost_stack;
+typedef struct pano_deghost_params {
+    int32_t slack;             /* 0 .. 15: grey levels of noise tolerated           */
+    int32_t tol;               /* 0 .. 255: rank units of 1/255 tolerated           */
+    int32_t erode;             /* 0 .. 3: the radius of the erosion                 */
+    int32_t dilate;            /* 0 .. 15: the radius of the dilation               */
+} pano_deghost_params;
+size_t pano_deghost_work_bytes(int h, int w, int k);
+int pano_deghost_u8(pano_ctx *ctx, const pano_deghost_stack *stacks, int n, const pano_deghost_params *params,
+                    void *work, int64_t work_bytes);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -130,7 +130,7 @@ LENS_CUBIC, LENS_LINEAR = 0, 1
 PHOTO_MAX_SIDE = 32767
 PHOTO_SUMS = 25
 PHOTO_TABLE = 1026
-# pano_fuse_u8 / pano_align_mtb
+# pano_fuse_u8 / pano_align_mtb / pano_deghost_u8
 FUSE_MAX_EXPOSURES = 8
 FUSE_MAX_SIDE = 32767
 
@@ -208,6 +208,20 @@ class AlignParams(C.Structure):
     _fields_ = [("max_bits", C.c_int32), ("exclude", C.c_int32)]
 
 
+class DeghostStack(C.Structure):
+    """``pano_deghost_stack`` of include/pano360.h (320 bytes)."""
+    _fields_ = [("src", C.c_void_p * FUSE_MAX_EXPOSURES), ("src_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
+                ("dst", C.c_void_p * FUSE_MAX_EXPOSURES), ("dst_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
+                ("counts", C.c_void_p), ("hists", C.c_void_p), ("ranks", C.c_void_p), ("maps", C.c_void_p),
+                ("raw", C.c_void_p), ("mask", C.c_void_p),
+                ("w", C.c_int32), ("h", C.c_int32), ("k", C.c_int32), ("reference", C.c_int32)]
+
+
+class DeghostParams(C.Structure):
+    """``pano_deghost_params`` of include/pano360.h (16 bytes)."""
+    _fields_ = [("slack", C.c_int32), ("tol", C.c_int32), ("erode", C.c_int32), ("dilate", C.c_int32)]
+
+
 class Pair(C.Structure):
     """``pano_pair`` of include/pano360.h (80 bytes)."""
     _fields_ = [("minv", C.c_double * 9), ("i", C.c_int32), ("j", C.c_int32)]
@@ -234,7 +248,8 @@ RECORDS = {
     "pano_view": View, "pano_view_mosaic": ViewMosaic, "pano_lens_frame": LensFrame,
     "pano_photo_frame": PhotoFrame, "pano_photo_pair": PhotoPair, "pano_photo_apply": PhotoApply,
     "pano_fuse_stack": FuseStack, "pano_fuse_params": FuseParams, "pano_align_stack": AlignStack,
-    "pano_align_params": AlignParams, "pano_stitch_args": StitchArgs,
+    "pano_align_params": AlignParams, "pano_deghost_stack": DeghostStack,
+    "pano_deghost_params": DeghostParams, "pano_stitch_args": StitchArgs,
 }
 
 _vp, _i = C.c_void_p, C.c_int
@@ -356,6 +371,8 @@ _SIGNATURES = {
     "pano_fuse_u8": (_i, [_vp, C.POINTER(FuseStack), _i, C.POINTER(FuseParams), _vp, C.c_int64]),
     "pano_align_work_bytes": (C.c_size_t, [_i, _i, _i]),
     "pano_align_mtb": (_i, [_vp, C.POINTER(AlignStack), _i, C.POINTER(AlignParams), _vp, C.c_int64]),
+    "pano_deghost_work_bytes": (C.c_size_t, [_i, _i, _i]),
+    "pano_deghost_u8": (_i, [_vp, C.POINTER(DeghostStack), _i, C.POINTER(DeghostParams), _vp, C.c_int64]),
     "pano_sift_detect": (_i, [_vp, _vp]),
     "pano_sift_detect_replaying": (_i, [_vp]),
     "pano_stitch_multiband": (_i, [_vp, _vp, _i]),

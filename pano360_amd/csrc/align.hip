@@ -346,50 +346,21 @@ extern "C" size_t pano_align_work_bytes(int h, int w, int k) {
 }
 
 static int align_check(const pano_align_stack &S, int i, const void *work, size_t work_bytes) {
-    PANO_REQUIRE(pano_stack_ok(S.h, S.w, S.k), "pano_align_mtb: stack %d: %d exposures of %d x %d (2 .. %d, sides 1 .. %d)",
-                 i, S.k, S.w, S.h, PANO_FUSE_MAX_EXPOSURES, PANO_FUSE_MAX_SIDE);
-    PANO_REQUIRE(S.reference >= 0 && S.reference < S.k, "pano_align_mtb: stack %d: reference %d of %d exposures", i,
-                 S.reference, S.k);
+    if (int rc = pano_stack_frames_check("pano_align_mtb", i, S.src, S.src_pitch, S.dst, S.dst_pitch, S.w, S.h, S.k,
+                                         S.reference, work, work_bytes))
+        return rc;
     PANO_REQUIRE(S.shifts, "pano_align_mtb: stack %d: null shifts", i);
-    for (int e = 0; e < S.k; ++e) {
-        PANO_REQUIRE(S.src[e], "pano_align_mtb: stack %d: exposure %d: null pointer", i, e);
-        PANO_REQUIRE(S.src_pitch[e] >= 3 * (int64_t)S.w, "pano_align_mtb: stack %d: exposure %d: pitch %lld for %d pixels",
-                     i, e, (long long)S.src_pitch[e], S.w);
-    }
-    for (int e = 0; e < S.k; ++e) {
-        if (!S.dst[e]) continue;
-        PANO_REQUIRE(S.dst_pitch[e] >= 3 * (int64_t)S.w, "pano_align_mtb: stack %d: dst %d: pitch %lld for %d pixels", i,
-                     e, (long long)S.dst_pitch[e], S.w);
-        const size_t dst_bytes = (size_t)(S.h - 1) * S.dst_pitch[e] + 3 * (size_t)S.w;
-        PANO_REQUIRE(!pano_overlap(S.dst[e], dst_bytes, work, work_bytes),
-                     "pano_align_mtb: stack %d: dst %d overlaps the workspace", i, e);
-        for (int f = 0; f < S.k; ++f)
-            PANO_REQUIRE(!pano_overlap(S.dst[e], dst_bytes, S.src[f], (size_t)(S.h - 1) * S.src_pitch[f] + 3 * (size_t)S.w),
-                         "pano_align_mtb: stack %d: dst %d overlaps exposure %d", i, e, f);
-    }
     return PANO_OK;
 }
 
-struct AlignSection {               // the records of one launch
-    std::vector<AlignDev> recs;
-    int blocks = 0;                 // its workgroups
-    int first = 0;                  // where its records start in the uploaded table
-};
+typedef BatchSection<AlignDev> AlignSection;        // the records of one launch
 
 template <int TW, int TH, int CHUNK>
 static void align_add(AlignSection &S, AlignDev D, int w, int h) {
-    batch_assign<PANO_FUSE_MAX_SIDE, TW, TH, CHUNK>(D.slot, &S.blocks, (int)S.recs.size(), w, h);
-    S.recs.push_back(D);
+    batch_section_add<PANO_FUSE_MAX_SIDE, TW, TH, CHUNK>(S, D, w, h);
 }
 
-#define AL_LAUNCH(kernel, S, threads)                                                                      \
-    do {                                                                                                   \
-        if (!(S).recs.empty()) {                                                                           \
-            hipLaunchKernelGGL(kernel, dim3((unsigned)(S).blocks), dim3(threads), 0, s, dev + (S).first,   \
-                               (int)(S).recs.size());                                                      \
-            PANO_LAUNCH_CHECK(#kernel);                                                                    \
-        }                                                                                                  \
-    } while (0)
+#define AL_LAUNCH(kernel, S, threads) BATCH_LAUNCH_SECTION(kernel, S, threads, dev, s)
 
 // The stacks [first, first + count) of a call, at most AL_FRAMES frames: one table, every launch.
 static int align_pass(pano_ctx *ctx, const pano_align_stack *stacks, const size_t *at, int first, int count,

@@ -299,7 +299,8 @@ static const char *const g_kernel_names[] = {
     "jpeg_enc_stuff_kernel", "png_filter_kernel", "deflate_code_kernel", "deflate_scan_kernel",
     "deflate_emit_kernel", "deflate_lengths_kernel", "photo_stats_kernel",
     "ba_refine_kernel",
-    "align_grey_kernel", "align_bitmap_kernel", "align_search_kernel", "align_apply_kernel"};
+    "align_grey_kernel", "align_bitmap_kernel", "align_search_kernel", "align_apply_kernel",
+    "deghost_hist_kernel", "deghost_raw_kernel", "deghost_clean_kernel", "deghost_apply_kernel"};
 static_assert(sizeof(g_kernel_names) / sizeof(g_kernel_names[0]) == PK_COUNT,
               "one name per PanoKernelId, in enum order");
 

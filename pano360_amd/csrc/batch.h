@@ -41,6 +41,33 @@ static inline int batch_assign(TileSlot &slot, int *blocks, int i, int w, int h)
     return tiles;
 }
 
+// A call of several kernels over the same frames (align.hip, deghost.hip) uploads ONE table with a
+// section of records per launch: the records of a launch, its workgroups, and where its records
+// start in the uploaded table.
+template <class Rec>
+struct BatchSection {
+    std::vector<Rec> recs;
+    int blocks = 0;
+    int first = 0;
+};
+
+// Appends D, w x h items in tiles of TW x TH, to a section of at most CHUNK records.
+template <int MAX_SIDE, int TW, int TH, int CHUNK, class Rec>
+static inline void batch_section_add(BatchSection<Rec> &S, Rec D, int w, int h) {
+    batch_assign<MAX_SIDE, TW, TH, CHUNK>(D.slot, &S.blocks, (int)S.recs.size(), w, h);
+    S.recs.push_back(D);
+}
+
+// Queues `kernel` for section S of the table at `dev` on stream `s`; an empty section is no launch.
+#define BATCH_LAUNCH_SECTION(kernel, S, threads, dev, s)                                                   \
+    do {                                                                                                   \
+        if (!(S).recs.empty()) {                                                                           \
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(S).blocks), dim3(threads), 0, s, (dev) + (S).first, \
+                               (int)(S).recs.size());                                                      \
+            PANO_LAUNCH_CHECK(#kernel);                                                                    \
+        }                                                                                                  \
+    } while (0)
+
 // The call: the whole table goes up to the context's buffer `id` at once, then launch(records,
 // count, grid) queues kernel `name` for every `chunk` records of it: a launch's first record on
 // the device, how many it takes and its workgroups.

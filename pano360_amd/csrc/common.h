@@ -97,6 +97,10 @@ enum PanoKernelId {
     PK_ALIGN_BITMAP,
     PK_ALIGN_SEARCH,
     PK_ALIGN_APPLY,
+    PK_DEGHOST_HIST,
+    PK_DEGHOST_RAW,
+    PK_DEGHOST_CLEAN,
+    PK_DEGHOST_APPLY,
     PK_COUNT
 };
 // ---- the context (include/pano360.h: pano_ctx) ------------------------------------
@@ -170,6 +174,8 @@ enum PanoBufId {
     BUF_PHOTO_PARTIALS,
     // pano_align_mtb (align.hip): the records of a pass's launches
     BUF_ALIGN_DEV,
+    // pano_deghost_u8 (deghost.hip): the records of a pass's launches
+    BUF_DEGHOST_DEV,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it
@@ -281,10 +287,37 @@ static inline T align_up(T bytes) { return (bytes + 255) / 256 * 256; }
 static inline bool pano_overlap(const void *a, size_t na, const void *b, size_t nb) {
     return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
 }
-// an exposure stack (fuse.hip, align.hip): k frames of h x w within the limits of the header
+// an exposure stack (fuse.hip, align.hip, deghost.hip): k frames of h x w within the limits of the header
 static inline bool pano_stack_ok(int h, int w, int k) {
     return h >= 1 && w >= 1 && h <= PANO_FUSE_MAX_SIDE && w <= PANO_FUSE_MAX_SIDE && k >= 2 &&
            k <= PANO_FUSE_MAX_EXPOSURES;
+}
+// Stack i of entry point `who` (align.hip, deghost.hip): k exposures src within the limits above,
+// `reference` one of them, none null, pitches of 3 w or more, and every dst that is given misses
+// the source frames of its stack and the workspace.
+static inline int pano_stack_frames_check(const char *who, int i, const uint8_t *const *src, const int64_t *src_pitch,
+                                          uint8_t *const *dst, const int64_t *dst_pitch, int w, int h, int k,
+                                          int reference, const void *work, size_t work_bytes) {
+    PANO_REQUIRE(pano_stack_ok(h, w, k), "%s: stack %d: %d exposures of %d x %d (2 .. %d, sides 1 .. %d)", who, i, k, w,
+                 h, PANO_FUSE_MAX_EXPOSURES, PANO_FUSE_MAX_SIDE);
+    PANO_REQUIRE(reference >= 0 && reference < k, "%s: stack %d: reference %d of %d exposures", who, i, reference, k);
+    for (int e = 0; e < k; ++e) {
+        PANO_REQUIRE(src[e], "%s: stack %d: exposure %d: null pointer", who, i, e);
+        PANO_REQUIRE(src_pitch[e] >= 3 * (int64_t)w, "%s: stack %d: exposure %d: pitch %lld for %d pixels", who, i, e,
+                     (long long)src_pitch[e], w);
+    }
+    for (int e = 0; e < k; ++e) {
+        if (!dst[e]) continue;
+        PANO_REQUIRE(dst_pitch[e] >= 3 * (int64_t)w, "%s: stack %d: dst %d: pitch %lld for %d pixels", who, i, e,
+                     (long long)dst_pitch[e], w);
+        const size_t dst_bytes = (size_t)(h - 1) * dst_pitch[e] + 3 * (size_t)w;
+        PANO_REQUIRE(!pano_overlap(dst[e], dst_bytes, work, work_bytes), "%s: stack %d: dst %d overlaps the workspace",
+                     who, i, e);
+        for (int f = 0; f < k; ++f)
+            PANO_REQUIRE(!pano_overlap(dst[e], dst_bytes, src[f], (size_t)(h - 1) * src_pitch[f] + 3 * (size_t)w),
+                         "%s: stack %d: dst %d overlaps exposure %d", who, i, e, f);
+    }
+    return PANO_OK;
 }
 // the grid of a kernel that loops beyond `cap` workgroups
 static inline dim3 capped_grid(int64_t groups, int64_t cap) {

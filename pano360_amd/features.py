@@ -1051,7 +1051,8 @@ def parse_args(argv=None):
 
 def cache_name(args):
     """``<name>`` of ``matches_<name>.npz``: the directory, ``_msop`` for that detector, ``_b<K>``
-    with ``--bracket K`` (``_b<K>a`` with ``--bracket-align``), ``_lens`` with ``--lens``."""
+    with ``--bracket K`` (``_b<K>a`` with ``--bracket-align``, ``_b<K>g`` with ``--bracket-deghost``,
+    ``_b<K>ag`` with both), ``_lens`` with ``--lens``."""
     from . import fuse as _fuse
     name = os.path.basename(args.path)
     if args.detector == "msop":

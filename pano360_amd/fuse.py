@@ -19,9 +19,10 @@ defined.  The arithmetic is stated in include/pano360.h and, in NumPy, in tests/
 There is no CPU fallback.
 
 The brackets are taken as aligned (a tripod) unless ``Bracket(k, align=AlignParams())`` /
-``--bracket-align`` asks for the integer alignment of ``pano360_amd.align`` first.  Not covered:
-rotation and parallax between the exposures, removing what moved in the scene between them, a
-radiance (HDR) output and tone mapping.
+``--bracket-align`` asks for the integer alignment of ``pano360_amd.align`` first, and what moved
+in the scene between the exposures ghosts unless ``Bracket(k, deghost=DeghostParams())`` /
+``--bracket-deghost`` asks for ``pano360_amd.deghost`` before the fusion.  Not covered: rotation
+and parallax between the exposures, a radiance (HDR) output and tone mapping.
 """
 import argparse
 import ctypes as C
@@ -146,23 +147,28 @@ def group_files(files, k):
 
 
 class Bracket:
-    """What ``--bracket`` asked for: ``k`` exposures per position, the ``FuseParams`` and ``align``:
+    """What ``--bracket`` asked for: ``k`` exposures per position, the ``FuseParams``, ``align``:
     None for brackets that are aligned as they are, or the ``align.AlignParams`` of
-    ``--bracket-align``."""
-    __slots__ = ("k", "params", "align")
+    ``--bracket-align``, and ``deghost``: None for a scene in which nothing moves, or the
+    ``deghost.DeghostParams`` of ``--bracket-deghost``."""
+    __slots__ = ("k", "params", "align", "deghost")
 
-    def __init__(self, k, params=None, align=None):
+    def __init__(self, k, params=None, align=None, deghost=None):
         self.k = int(k)
         if not 2 <= self.k <= MAX_EXPOSURES:
             raise ValueError(f"brackets of {self.k} (2 .. {MAX_EXPOSURES})")
         self.params = params or FuseParams()
         self.align = align
+        self.deghost = deghost
 
     def fuse_groups(self, frames, groups, eng=None):
         """``frames``: the decoded device tensors in the order of the groups' files.  Every group
         fused by ONE ``fuse_device`` call - with ``align``, after ONE ``align.align_device`` call
         has moved the exposures of every group onto its reference; each bracket's shifts are
-        logged under its first file name, with a warning for a shift at the search's limit.  A
+        logged under its first file name, with a warning for a shift at the search's limit; with
+        ``deghost``, ONE ``deghost.deghost_device`` call then makes the exposures of every group
+        show the scene of its reference (the one ``align`` used), and the share of pixels replaced
+        in each exposure is logged, with a warning above a quarter of the frame.  A
         group whose frames differ in size is a ``ValueError`` that names its files."""
         stacks, at = [], 0
         for group in groups:
@@ -184,6 +190,21 @@ class Bracket:
                 if np.abs(found).max() >= reach:
                     logging.warning(f"Bracket alignment of {name}: a shift at the limit of {reach} pixels - "
                                     f"the exposures moved further than the search reaches")
+        if self.deghost is not None and stacks:
+            from . import deghost as _deghost
+            how = self.deghost
+            if self.align is not None:                  # (the exposure the others were moved onto)
+                how = _deghost.DeghostParams(how.slack, how.tol, how.erode, how.dilate,
+                                             self.align.reference_of(self.k))
+            stacks, counts = _deghost.deghost_device(stacks, how, eng)
+            for group, stack, found in zip(groups, stacks, counts):
+                shares = [int(c) / (stack[0].shape[0] * stack[0].shape[1]) for c in found]
+                name = os.path.basename(group[0])
+                logging.info(f"Bracket deghosting of {name}: replaced {[round(v, 4) for v in shares]} of the pixels")
+                if max(shares) > _deghost.WARN_SHARE:
+                    logging.warning(f"Bracket deghosting of {name}: {max(shares):.2f} of an exposure differs from "
+                                    f"the reference - misaligned exposures (--bracket-align) or a changed scene; "
+                                    f"the result is mostly the reference exposure")
         return fuse_device(stacks, self.params, eng)
 
 
@@ -208,6 +229,16 @@ def _bits(text):
     return bits
 
 
+def _tol(text):
+    try:
+        tol = int(text)
+    except ValueError:
+        tol = -1
+    if not 0 <= tol <= 255:
+        raise argparse.ArgumentTypeError(f"{text!r}: 0 .. 255 rank units of 1/255")
+    return tol
+
+
 def _count(text):
     try:
         k = int(text)
@@ -219,9 +250,10 @@ def _count(text):
 
 
 def add_arguments(parser):
-    """``--bracket``, ``--bracket-weights``, ``--bracket-align`` and ``--bracket-align-bits`` of
-    stitcher.py and features.py.  Without the flags the parsed namespace is what it was (no
-    attribute: ``bracket_of`` and ``align_of`` read them)."""
+    """``--bracket``, ``--bracket-weights``, ``--bracket-align``, ``--bracket-align-bits``,
+    ``--bracket-deghost`` and ``--bracket-deghost-tol`` of stitcher.py and features.py.  Without
+    the flags the parsed namespace is what it was (no attribute: ``bracket_of``, ``align_of`` and
+    ``deghost_of`` read them)."""
     parser.add_argument("--bracket", type=_count, metavar="K", default=argparse.SUPPRESS,
                         help="the directory holds exposure brackets, K (2 .. 8) consecutive files "
                              "(in sorted order) per position: each bracket is fused into one frame "
@@ -237,6 +269,14 @@ def add_arguments(parser):
     parser.add_argument("--bracket-align-bits", type=_bits, metavar="N", default=argparse.SUPPRESS,
                         help="--bracket-align: at most N (0 .. 7, default 6) pyramid levels: shifts "
                              "up to 2^(N+1) - 1 pixels are found.")
+    parser.add_argument("--bracket-deghost", action="store_true", default=argparse.SUPPRESS,
+                        help="--bracket: something moved in the scene between the exposures: where an "
+                             "exposure's brightness ranks disagree with the middle exposure's, it takes "
+                             "that exposure's pixels, carried to its own brightness, before the fusion "
+                             "(after --bracket-align, if given); the caches get _b<K>g or _b<K>ag.")
+    parser.add_argument("--bracket-deghost-tol", type=_tol, metavar="N", default=argparse.SUPPRESS,
+                        help="--bracket-deghost: ranks may differ by N / 255 (0 .. 255, default 8) of "
+                             "the frame's pixels before a pixel counts as moved.")
 
 
 def bracket_of(args):
@@ -249,11 +289,17 @@ def align_of(args):
     return bool(getattr(args, "bracket_align", False))
 
 
+def deghost_of(args):
+    """True with ``--bracket-deghost``."""
+    return bool(getattr(args, "bracket_deghost", False))
+
+
 def cache_suffix(args):
-    """What the flags add to a cache name: nothing, ``_b<K>`` or, aligned, ``_b<K>a``."""
+    """What the flags add to a cache name: nothing, or ``_b<K>`` and then ``a`` when aligned and
+    ``g`` when deghosted: ``_b<K>``, ``_b<K>a``, ``_b<K>g``, ``_b<K>ag``."""
     if bracket_of(args) is None:
         return ""
-    return f"_b{bracket_of(args)}" + ("a" if align_of(args) else "")
+    return f"_b{bracket_of(args)}" + ("a" if align_of(args) else "") + ("g" if deghost_of(args) else "")
 
 
 def check_arguments(parser, args):
@@ -263,6 +309,10 @@ def check_arguments(parser, args):
         parser.error("--bracket-align needs --bracket")
     if not align_of(args) and getattr(args, "bracket_align_bits", None) is not None:
         parser.error("--bracket-align-bits needs --bracket-align")
+    if bracket_of(args) is None and deghost_of(args):
+        parser.error("--bracket-deghost needs --bracket")
+    if not deghost_of(args) and getattr(args, "bracket_deghost_tol", None) is not None:
+        parser.error("--bracket-deghost-tol needs --bracket-deghost")
 
 
 def from_args(args):
@@ -274,4 +324,8 @@ def from_args(args):
     if align_of(args):
         from . import align as _align
         how = _align.AlignParams(max_bits=getattr(args, "bracket_align_bits", 6))
-    return Bracket(bracket_of(args), FuseParams(*weights), how)
+    ghosts = None
+    if deghost_of(args):
+        from . import deghost as _deghost
+        ghosts = _deghost.DeghostParams(tol=getattr(args, "bracket_deghost_tol", 8))
+    return Bracket(bracket_of(args), FuseParams(*weights), how, ghosts)

@@ -344,7 +344,9 @@ def ingest(path, shrink, decode="device", lens=None, bracket=None):
     taken in sorted file-name order instead, K consecutive files are one position's exposures
     (``fuse.group_files``), and after the one decode every group is fused into one frame by one
     ``fuse.fuse_device`` call - after one ``align.align_device`` call when the bracket has an
-    ``align`` (hand-held brackets: decode, align, fuse, lens, shrink); the fused frames take the images' place, in group order, the lens
+    ``align`` (hand-held brackets) and one ``deghost.deghost_device`` call when it has a
+    ``deghost`` (something moved between the exposures): decode, align, deghost, fuse, lens,
+    shrink; the fused frames take the images' place, in group order, the lens
     correction then runs under each group's first file name: decode, fuse, lens, shrink.
     Returns uint8 [h][w][3] device tensors."""
     from . import blend as _blend
@@ -593,8 +595,9 @@ def parse_args(argv=None):
 def cache_name(args):
     """``<name>`` of ``matches_<name>.npz`` and ``ba_<name>.pkl``: the directory and the shrink
     as in the reference, ``_msop`` for that detector, ``_b<K>`` with ``--bracket K`` (``_b<K>a``
-    with ``--bracket-align``), ``_lens`` with ``--lens``: matches and cameras of corrected and
-    uncorrected, fused and plain, aligned and unaligned frames never mix."""
+    with ``--bracket-align``, ``_b<K>g`` with ``--bracket-deghost``, ``_b<K>ag`` with both),
+    ``_lens`` with ``--lens``: matches and cameras of corrected and uncorrected, fused and plain,
+    aligned and unaligned, deghosted and ghosted frames never mix."""
     name = f"{os.path.basename(os.path.normpath(args.path))}_s{args.shrink}"
     if args.detector == "msop":
         name += "_msop"
