@@ -670,6 +670,64 @@ int pano_alpha_blend(pano_ctx *ctx, const void *img1, const void *img2, int dtyp
                      const void *mask, int mask_f64, int64_t mask_sy, int64_t mask_sx,
                      int64_t mask_sc, int h, int w, int c, uint8_t *out);
 
+/* Seam routing in front of the multiband blend (csrc/seam_route.hip; no reference counterpart;
+ * DESIGN.md section 5t; tests/seam_route_model.py restates all of it in NumPy, heap loop included).
+ * The stage-level multiband path takes any owner map; these calls rewrite pano_ownership's inside
+ * the zones two cameras contest, so that the seam runs where the two agree.
+ *
+ * Per mosaic pixel, from the patch table pano_ownership takes (n <= PANO_SEAM_ROUTE_MAX_CAMERAS):
+ *   a      owner0 at the pixel (first-index argmax of alpha, -1 where every alpha is 0)
+ *   b      the camera other than a with the largest alpha > 0 there, lowest index on ties, else -1
+ *   D      where b >= 0: max over the 3 colour channels of |qa - qb|, q = uint8(255.0f * c), the
+ *          truncation of pano_no_blend; 0 elsewhere
+ *   open   the pixel is valid (some patch's mask is 0 there), a >= 0, b >= 0 and
+ *          alpha_b >= ratio * alpha_a (one float32 product).  Every other valid pixel with
+ *          a >= 0 is a SEED, labelled a for good; the rest are WALLS.
+ * Two cameras COMPETE when some open pixel has them as {a, b}; group[c] is the smallest
+ * non-negative integer no lower-indexed competitor of c uses (greedy colouring in index order, on
+ * the host), so the two cameras an open pixel admits - a and b, no others - are of different
+ * groups, and cameras of one group admit no common pixel.
+ * Flood: pop the smallest (-D, group[c], c, y, x) from a heap; label the pixel c if it is still
+ * unlabelled; push its unlabelled open 4-neighbours that admit c.  As for pano_seam_flood the
+ * labels depend only on the order of the CLASSES (D descending, group ascending): for d = 255 .. 0
+ * and g = 0 .. n_groups - 1, and every camera c of group g, each 4-connected component of
+ * unlabelled open pixels with D >= d that admit c and that touches a pixel labelled c becomes c.
+ * Result: the label, a where an open pixel was never reached, -1 on walls: every owner is a camera
+ * with alpha > 0 at its pixel.
+ *
+ * pano_seam_route_prepare   one thread per mosaic pixel over the patch table.  owner0: dev int16
+ *     [H][W], pano_ownership's.  Writes second (b) dev int16 [H][W], diff (D) dev uint8 [H][W],
+ *     label dev int16 [H][W] (a on seeds, -1 on open pixels, -2 on walls), pairs dev uint8 [n][n]
+ *     (pairs[a][b] = 1 for the open pixels' (a, b); zeroed by the call) and present dev uint8 [256]
+ *     (present[D] = 1 for the open pixels' D; zeroed by the call).  0 < ratio <= 1.  present is
+ *     for the caller's information (how many classes the flood will walk): the flood takes plain
+ *     planes, which may be forged, and reads the levels that occur off them itself.
+ * pano_seam_route_flood     the class sweep on plain planes (a, second, diff as above; label is
+ *     the flood's state and is updated in place: what is still -1 afterwards was never reached).
+ *     group: HOST int32 [n], 0 <= group[c] < n_groups; the two cameras of an open pixel must be of
+ *     different groups (an index outside [0, n) admits nothing).  64 x 64 tiles with a one-cell halo
+ *     flood to their own fixed point of the running class in LDS and write back, one launch per
+ *     round, a one-thread kernel between the rounds keeps the class while the round's "changed"
+ *     word was set and else takes the next class whose level occurs; the host reads one word per
+ *     PANO_SEAM_BATCH queued rounds.  A cell only ever goes from -1 to the one label its class
+ *     admits, so stale reads between waves and tiles only delay a label: no atomics, the same
+ *     bytes on every run.  owner_out dev int16 [H][W] (may be a).  stats (optional, dev int32 [4]):
+ *     classes that labelled a cell, rounds that labelled one, the most of them in one class,
+ *     pixels whose owner is not a.  Waits for the stream (the reads of "done").
+ * pano_seam_route           pano_ownership, the prepare, the download of pairs, the colouring,
+ *     the flood: owner dev int16 [H][W], valid dev uint8 [H][W] (pano_ownership's); stats
+ *     (optional, dev int32 [6]): the flood's four, the open pixels, the groups.  The planes in
+ *     between are the context's. */
+#define PANO_SEAM_ROUTE_MAX_CAMERAS 4096
+int pano_seam_route_prepare(pano_ctx *ctx, const pano_patch *patches, int n, int H, int W,
+                            const int16_t *owner0, float ratio, int16_t *second, uint8_t *diff,
+                            int16_t *label, uint8_t *pairs, uint8_t *present);
+int pano_seam_route_flood(pano_ctx *ctx, const int16_t *a, const int16_t *second,
+                          const uint8_t *diff, int16_t *label, const int32_t *group, int n,
+                          int n_groups, int H, int W, int16_t *owner_out, int32_t *stats);
+int pano_seam_route(pano_ctx *ctx, const pano_patch *patches, int n, int H, int W, float ratio,
+                    int16_t *owner, uint8_t *valid, int32_t *stats);
+
 /* cv2.resize(im, None, fx=1/shrink, fy=1/shrink) on a uint8 image   stitcher.py:419-420
  * (INTER_LINEAR, OpenCV's 8-bit fixed-point path restated; parity unpinned).
  * xtab / ytab: dev int32 [ow][4] / [oh][4] = (first tap, second tap, coefficient of

@@ -93,6 +93,8 @@ SEAM_U8, SEAM_I16, SEAM_I32, SEAM_F32, SEAM_F64 = 0, 1, 2, 3, 4
 SEAM_DTYPES = {"uint8": SEAM_U8, "int16": SEAM_I16, "int32": SEAM_I32, "float32": SEAM_F32,
                "float64": SEAM_F64}
 SEAM_RESIDENT_CELLS = 81408
+# pano_seam_route_prepare / pano_seam_route: the cameras the pair matrix holds
+SEAM_ROUTE_MAX_CAMERAS = 4096
 # pano_ssc_probe's paths, the on-chip bitmap's capacity in cells
 SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
 SSC_ONCHIP_CELLS = 524288
@@ -317,6 +319,9 @@ _SIGNATURES = {
     "pano_seam_mask": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i]),
     "pano_alpha_blend": (_i, [_vp, _vp, _vp, _i, _vp, _i, C.c_int64, C.c_int64, C.c_int64, _i, _i,
                               _i, _vp]),
+    "pano_seam_route_prepare": (_i, [_vp, _vp, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "pano_seam_route_flood": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "pano_seam_route": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp]),
     "pano_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "pano_sift_extrema": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _vp,
                                _vp, _i]),

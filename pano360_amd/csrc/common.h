@@ -176,6 +176,13 @@ enum PanoBufId {
     BUF_ALIGN_DEV,
     // pano_deghost_u8 (deghost.hip): the records of a pass's launches
     BUF_DEGHOST_DEV,
+    // pano_seam_route_flood (seam_route.hip): the class being flooded, its "changed" word and the
+    // group table (device), and the pinned host words "done" is read into; pano_seam_route: the
+    // planes between its stages (device) and the pinned host copy of the pair matrix
+    BUF_ROUTE_STATE,
+    BUF_ROUTE_HOST,
+    BUF_ROUTE_PLANES,
+    BUF_ROUTE_PAIRS_HOST,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it

@@ -665,6 +665,7 @@ class Engine:
         self.keep_geometry = False
         self.last_kept_geometry = False
         self._trusted = None            # the last verified stitch (VerifiedStitch)
+        self.last_seam_stats = None     # seam_multiband's route statistics (int32 [6], device)
 
     def __del__(self):
         ctx, self._ctx = getattr(self, "_ctx", None), None
@@ -841,6 +842,30 @@ class Engine:
         if table is None:
             table = patch_table(patches, self)
         owner, valid = self.ownership(table, shape)
+        mosaic, fl = self.blur_and_compose(table, owner, valid, shape, n_levels, want_float)
+        return mosaic, fl, owner, valid
+
+    def seam_route(self, table, shape, ratio):
+        """The ownership of ``ownership`` with its seams routed around what the frames disagree
+        on: inside the zones where the runner-up's alpha is at least
+        ``ratio`` of the owner's, a priority flood over the two frames' colour difference decides
+        the owner.  Returns (owner, valid, stats); stats: int32 [6] on the device - classes and
+        rounds that labelled a pixel, the most rounds in one class, pixels whose owner changed,
+        open pixels, groups.  Waits for the stream (the flood reads its "done" word)."""
+        torch = _torch()
+        H, W = shape
+        owner = torch.empty((H, W), dtype=torch.int16, device=self.device)
+        valid = torch.empty((H, W), dtype=torch.uint8, device=self.device)
+        stats = torch.zeros(6, dtype=torch.int32, device=self.device)
+        self.call("pano_seam_route", table.dev, table.n, H, W, float(ratio), owner, valid, stats)
+        return owner, valid, stats
+
+    def seam_multiband(self, patches, shape, n_levels, ratio, table=None, want_float=False):
+        """Stage-level multiband on the routed ownership: ``seam_route`` -> blurs -> collapse.
+        Returns what ``multiband`` returns; the route's statistics stay in ``last_seam_stats``."""
+        if table is None:
+            table = patch_table(patches, self)
+        owner, valid, self.last_seam_stats = self.seam_route(table, shape, ratio)
         mosaic, fl = self.blur_and_compose(table, owner, valid, shape, n_levels, want_float)
         return mosaic, fl, owner, valid
 

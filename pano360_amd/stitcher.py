@@ -2,8 +2,8 @@
 
 Same names, argument order, defaults, return types and side effects as the
 reference: ``stitch``, ``no_blend`` / ``linear_blend`` /
-``multiband_blend`` (the ``blender(patches, shape)`` protocol; ``median_blend`` is this port's
-ghost-rejecting addition to them), ``SphProj``,
+``multiband_blend`` (the ``blender(patches, shape)`` protocol; ``median_blend`` and ``seam_blend``
+are this port's ghost-rejecting additions to them), ``SphProj``,
 ``CylProj``, ``_proj_img_range_border``, ``_proj_img_range_corners``,
 ``estimate_resolution``, ``_hat``, ``_add_weights``, ``_valid``,
 ``crop_mosaic``, ``find_gains``, ``equalize_gains``, ``BLENDERS``,
@@ -48,6 +48,12 @@ _exact_engine = None
 # scene, below the contrast of something that moved; chosen by that reasoning, not tuned on
 # photographs.
 GHOST_TOL = 0.1
+# Zone of ``seam_blend`` (read at call time; ``--seam-ratio``): the seam may move wherever the
+# runner-up's weight is at least this share of the owner's.  0.5 - the two weights within a factor
+# of two - keeps the seam in the middle half of an overlap of two hat weights, where both frames
+# are sampled away from their borders; chosen by that reasoning, not tuned on photographs
+# (DESIGN.md section 5t).
+SEAM_RATIO = 0.5
 
 
 def _engine_for_stitch():
@@ -185,6 +191,29 @@ def median_blend(patches, shape, tol=None):
     return eng.median_blend(dev, tuple(shape), _ghost_tol(tol)).cpu().numpy()
 
 
+def seam_blend(patches, shape, n_levels=5, ratio=None):
+    """``multiband_blend`` behind a seam finder: inside the zones two frames contest (the
+    runner-up's weight at least ``ratio`` of the owner's) the ownership map is rewritten by a
+    priority flood over the frames' colour difference, so that the seam runs where the two agree
+    and something that only one of them shows is taken from one frame whole (no reference
+    counterpart).  ``ratio``: None = ``SEAM_RATIO``.  Like
+    ``multiband_blend`` it overwrites each patch's alpha with its sharp ownership mask."""
+    eng = _eng.engine()
+    dev = _upload_patches(eng, patches, n_levels - 1)
+    mosaic, _, owner, _ = eng.seam_multiband(dev, tuple(shape), n_levels, _seam_ratio(ratio))
+    owner = owner.cpu().numpy()
+    for idx, (warped, _, irange) in enumerate(patches):
+        warped[..., 3] = owner[irange] == idx
+    return mosaic.cpu().numpy()
+
+
+def _seam_ratio(ratio=None):
+    ratio = SEAM_RATIO if ratio is None else ratio
+    if not 0 < ratio <= 1:
+        raise ValueError(f"seam_blend: ratio {ratio!r} (0 < ratio <= 1)")
+    return float(ratio)
+
+
 def _ghost_tol(tol=None):
     tol = GHOST_TOL if tol is None else tol
     if not tol >= 0:
@@ -197,6 +226,7 @@ BLENDERS = {
     "linear": linear_blend,
     "multiband": multiband_blend,
     "median": median_blend,
+    "seam": seam_blend,
 }
 _FUSED = {no_blend: "none", linear_blend: "linear", multiband_blend: "multiband",
           median_blend: "median"}
@@ -262,23 +292,26 @@ def _stitch_device(regions, blender, equalize, crop):
     return _stitch_device_geometry(regions, blender, equalize, crop)[:2]
 
 
-def _stitch_device_geometry(regions, blender, equalize, crop, tol=None):
+def _stitch_device_geometry(regions, blender, equalize, crop, tol=None, ratio=None):
     """``_stitch_device`` and, third, the ``view.MosaicGeometry`` of the whole mosaic (where its
     pixels lie on the sphere: the plan's ``low``, ``resolution`` and ``shape``); the cropped
     mosaic's is ``geometry.cropped(rect)``."""
-    return _stitch_device_valid(regions, blender, equalize, crop, False, tol)[:3]
+    return _stitch_device_valid(regions, blender, equalize, crop, False, tol, ratio)[:3]
 
 
-def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=None):
+def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=None, ratio=None):
     """``_stitch_device_geometry`` and, fourth, the valid mask the stitch computes (uint8 [H][W] on
     the device, 1 = some frame covers the pixel): ``eng.stitch``'s third result, or
     ``eng.ownership`` of the warped patches for a custom blender, as under ``crop``.  Without
     ``want_valid`` a custom blender's mask is only computed for the crop (else None).  ``tol``:
-    ``median_blend``'s tolerance for this stitch (None = ``GHOST_TOL``); no other blender reads it."""
+    ``median_blend``'s tolerance for this stitch (None = ``GHOST_TOL``), ``ratio``: ``seam_blend``'s
+    zone (None = ``SEAM_RATIO``); no other blender reads them.  ``seam_blend`` stays on the device
+    too, on the stage path: the warped patches go to ``eng.seam_multiband`` as they are."""
     from . import view as _view
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
     padded = blender == multiband_blend                     # stitcher.py:295
+    padded = padded or blender == seam_blend
     plan = _eng.Plan([im.shape[:2] for im in frames_host], [r.rot for r in regions],
                      [r.intr for r in regions], padded, MAX_RESOLUTION)
     frames = eng.upload_frames(frames_host)
@@ -302,6 +335,13 @@ def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=
         extra = {"tol": _ghost_tol(tol)} if kind == "median" else {}
         mosaic, _, valid, patches = eng.stitch(frames, plan, kind, n_levels, luts=luts,
                                                shortcut=not EXACT, **extra)
+    elif blender == seam_blend:
+        n_levels = seam_blend.__defaults__[0]
+        patches, _ = eng.warp_all(frames, plan, n_blur=n_levels - 1, luts=luts)
+        mosaic, _, _, valid = eng.seam_multiband(patches, plan.shape, n_levels, _seam_ratio(ratio))
+        moved, n_open, n_groups = (int(v) for v in eng.last_seam_stats[3:6].tolist())
+        logging.info(f"Seam routing: {n_groups} groups, {n_open} contested pixels, owner changed "
+                     f"on {moved / max(int(valid.sum()), 1):.4f} of the valid pixels")
     else:
         patches, _ = eng.warp_all(frames, plan, luts=luts)
         valid = None
@@ -504,6 +544,13 @@ def _tolerance(text):
     return value
 
 
+def _zone_ratio(text):
+    value = float(text)
+    if not 0 < value <= 1:
+        raise argparse.ArgumentTypeError(f"{text}: in (0, 1]")
+    return value
+
+
 def refine_of(args):
     """(whether to refine, the radial terms to fit or None): what ``--refine`` and
     ``--refine-lens`` asked for."""
@@ -528,6 +575,10 @@ def parse_args(argv=None):
                         help="-b median: a frame's sample counts where every channel is within "
                              f"this of the pixel's median sample (colours in [0, 1]; default "
                              f"{GHOST_TOL}).")
+    # (an absent flag leaves no attribute: the parsed namespace without it is what it was)
+    parser.add_argument("--seam-ratio", type=_zone_ratio, metavar="FLOAT", default=argparse.SUPPRESS,
+                        help="-b seam: the seam may move wherever the runner-up frame's weight is "
+                             f"at least this share of the owner's (in (0, 1]; default {SEAM_RATIO}).")
     parser.add_argument("-o", "--out", type=str, help="save result to this file")
     parser.add_argument("--register", action="store_true",
                         help="without a camera cache, match the images and run bundle "
@@ -579,6 +630,8 @@ def parse_args(argv=None):
     _fuse.check_arguments(parser, args)
     if args.ghost_tol is not None and args.blend != "median":
         parser.error("--ghost-tol needs -b median")
+    if hasattr(args, "seam_ratio") and args.blend != "seam":
+        parser.error("--seam-ratio needs -b seam")
     if args.fill and args.crop:
         parser.error("--fill and --crop exclude each other: a cropped mosaic has nothing to fill")
     if (args.view or args.equirect or args.cube) and not args.out:
@@ -665,12 +718,14 @@ def main(argv=None):
     if args.fill:
         dev_mosaic, rect, geom, valid = _stitch_device_valid(regions, BLENDERS[args.blend],
                                                              args.equalize, False,
-                                                             tol=args.ghost_tol)
+                                                             tol=args.ghost_tol,
+                                                             ratio=getattr(args, "seam_ratio", None))
         dev_mosaic, background = _filled(args, dev_mosaic, geom, valid)
     else:
         dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend],
                                                          args.equalize, args.crop,
-                                                         tol=args.ghost_tol)
+                                                         tol=args.ghost_tol,
+                                                         ratio=getattr(args, "seam_ratio", None))
     mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
