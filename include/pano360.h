@@ -1714,6 +1714,91 @@ size_t pano_deghost_work_bytes(int h, int w, int k);
 int pano_deghost_u8(pano_ctx *ctx, const pano_deghost_stack *stacks, int n, const pano_deghost_params *params,
                     void *work, int64_t work_bytes);
 
+/* Local alignment of the warped patches between the warp and the blend (--local-align; DESIGN.md
+ * section 5u; tests/flow_model.py restates all of this in NumPy).  Two overlapping frames that
+ * disagree by a small, smooth, locally varying displacement (parallax of a hand-held sweep) are
+ * each moved part of the way towards the other, in proportion to the other's blend weight.
+ * Everything up to the block vectors is integer arithmetic; the two float32 stages do one
+ * rounding per operation in the order stated (-ffp-contract=off): the same input, the same bytes.
+ *
+ * Input: n stage-level patches (planes [4][h][vpitch] float32 over the whole patch, mask uint8
+ *     [h][w] with 1 = invalid, the rect in the H x W mosaic), levels 0 .. PANO_FLOW_MAX_LEVELS
+ *     (reach 2^(levels + 1) - 1 pixels), gain 1 .. PANO_FLOW_MAX_GAIN in 1/16 grey levels per
+ *     sample, min_overlap >= 16.
+ * Grey and validity, per camera: q_k = uint8(float32(255) * c_k) per colour plane,
+ *     g = (q_0 + 2 q_1 + q_2 + 2) >> 2; valid where the mask is 0, invalid outside the rect; an
+ *     invalid pixel has g = 0.
+ * Levels 1 .. L are anchored at the MOSAIC's origin: sample (Y, X) of level l covers the mosaic
+ *     pixels [Y 2^l, (Y + 1) 2^l) of each axis, is (a + b + c + d + 2) >> 2 of its four children
+ *     and valid only if all four are.
+ * Pairs (host): every i < j whose rects meet in at least min_overlap x min_overlap pixels, oh x
+ *     ow; L_ij = min(levels, max(0, bit_length(min(oh, ow)) - 6)).
+ * Blocks: block (by, bx) of level l is the 16 x 16 samples of level l from (16 by, 16 bx); a
+ *     pair's blocks at a level are those that meet its intersection.
+ * Search, l = L_ij .. 0: a block inherits v = 2 * the vector of block (by >> 1, bx >> 1) of level
+ *     l + 1, (0, 0) at the top.  Candidates u = v + (dx, dy): (0, 0) first, then dy, dx = -1 .. 1
+ *     in raster order.  n(u) counts the block's samples s with i valid at s and j valid at s + u,
+ *     S(u) sums |g_i(s) - g_j(s + u)| over them; u is eligible when n(u) >= PANO_FLOW_MIN_COUNT.
+ *     The winner w is the first eligible candidate that minimises S / n, compared exactly:
+ *     S(u) n(w) < S(w) n(u) in int64.  If the centre c is eligible it stays unless
+ *     16 S(w) n(c) + gain n(w) n(c) <= 16 S(c) n(w).  With no eligible candidate the block keeps v
+ *     and is unknown.  Result: int16 (dx, dy, known, 0) per block, g_i(s) ~ g_j(s + F_ij).
+ * Smoothing, per pair on its level-0 blocks: each component becomes the lower median (element
+ *     (m - 1) >> 1 of the m sorted values) of the known vectors of the block's 3 x 3 neighbourhood
+ *     inside the pair's block range; an unknown block takes it when m >= 3 and is (0, 0) otherwise.
+ * Field per pixel: the smoothed vectors as float32, bilinear between the block centres 16 b + 7.5:
+ *     t = float32(2 x - 15) / 32, b0 = floor(t), f = t - b0, the indices b0 and b0 + 1 clamped into
+ *     the pair's block range; x first, then y; every lerp is a + f * (b - a).  F_ji = -F_ij.
+ * Apply, per camera c and pixel p of its patch: a masked pixel is copied.  W = the float32 sum, in
+ *     camera order, of alpha_k(p) over every camera k that covers p (inside its rect, mask 0; c is
+ *     one).  d = sum over c's pair partners j that cover p with alpha_j(p) > 0, in camera order,
+ *     of (alpha_j(p) / W) * F_cj(p), one division and one product per component, from d = 0.  If
+ *     d == (0, 0) the pixel is copied; else the four planes are sampled bilinearly (same lerps) at
+ *     patch position (x - d_x, y - d_y): x0 = floor, fx = sx - x0, taps x0, x0 + 1, likewise in y;
+ *     if a tap is outside the patch or masked the pixel is copied.  The mask never changes.
+ *
+ * patches_host: a HOST array of the n records; their pointers are device pointers.
+ * pano_flow_work_bytes: the workspace (dev) of a call, 0 for arguments a call would refuse.  It
+ *     holds, each from a multiple of 256 bytes: the pyramids (uint16 g | valid << 8; per camera
+ *     that has a pair, in order, the levels 0 .. max L_ij of its box - the rect grown to multiples
+ *     of 16 mosaic pixels - dense, back to back), the block vectors (int16 [4]; per pair the
+ *     levels 0 .. L_ij, [nby][nbx] each), the smoothed vectors (int16 [2]; per pair [nby][nbx] of
+ *     level 0) and int32 statistics (pixels moved, unmasked pixels of the cameras with a pair).
+ * pano_flow_pyramid / _search / _smooth / _apply: one stage each, reading what the stage before
+ *     left in (or a test wrote into) the workspace.  out: HOST array of n device pointers, planes
+ *     [4][h][vpitch] of their own for every camera that has a pair (the others are not read; the
+ *     columns from w on are not written); stats (dev int32 [4] or NULL).
+ * pano_flow_align: the whole stage, 3 + (max L_ij + 1) launches from one record table, no host
+ *     wait; pyramid, vectors, fields, stats: dev or NULL, the workspace's regions copied out
+ *     behind the kernels.  With no pair nothing is launched.
+ * PANO_EINVAL with nothing written: a null table or workspace, n < 2, levels, gain or min_overlap
+ *     out of range, a rect that leaves the mosaic, a patch whose window is not the whole patch or
+ *     without a mask, work_bytes too small, a camera with a pair and no output planes of its own. */
+#define PANO_FLOW_MAX_LEVELS 4
+#define PANO_FLOW_MIN_COUNT 128
+#define PANO_FLOW_MAX_GAIN 4080
+typedef struct pano_flow_params {
+    int32_t levels;            /* 0 .. 4; default 3: a reach of 15 pixels            */
+    int32_t gain;              /* 1/16 grey levels per sample a move must gain; 16   */
+    int32_t min_overlap;       /* side of the smallest intersection that is a pair; 64 */
+    int32_t reserved;
+} pano_flow_params;
+size_t pano_flow_work_bytes(const pano_patch *patches_host, int n, int H, int W,
+                            const pano_flow_params *params);
+int pano_flow_pyramid(pano_ctx *ctx, const pano_patch *patches_host, int n, int H, int W,
+                      const pano_flow_params *params, void *work, int64_t work_bytes);
+int pano_flow_search(pano_ctx *ctx, const pano_patch *patches_host, int n, int H, int W,
+                     const pano_flow_params *params, void *work, int64_t work_bytes);
+int pano_flow_smooth(pano_ctx *ctx, const pano_patch *patches_host, int n, int H, int W,
+                     const pano_flow_params *params, void *work, int64_t work_bytes);
+int pano_flow_apply(pano_ctx *ctx, const pano_patch *patches_host, int n, int H, int W,
+                    const pano_flow_params *params, void *work, int64_t work_bytes,
+                    float *const *out, int32_t *stats);
+int pano_flow_align(pano_ctx *ctx, const pano_patch *patches_host, int n, int H, int W,
+                    const pano_flow_params *params, void *work, int64_t work_bytes,
+                    float *const *out, uint16_t *pyramid, int16_t *vectors, int16_t *fields,
+                    int32_t *stats);
+
 /* One multiband stitch of the mosaic columns [xs0, xs1), queued by ONE call
  *                                                  stitcher.py:283-327 (equalize and crop aside)
  * = pano_ownership_cameras, pano_owned_regions (+ its copy to the host), pano_interior_map,

@@ -95,6 +95,8 @@ SEAM_DTYPES = {"uint8": SEAM_U8, "int16": SEAM_I16, "int32": SEAM_I32, "float32"
 SEAM_RESIDENT_CELLS = 81408
 # pano_seam_route_prepare / pano_seam_route: the cameras the pair matrix holds
 SEAM_ROUTE_MAX_CAMERAS = 4096
+# pano_flow_*: levels, the pairs a candidate needs, gain
+FLOW_MAX_LEVELS, FLOW_MIN_COUNT, FLOW_MAX_GAIN = 4, 128, 4080
 # pano_ssc_probe's paths, the on-chip bitmap's capacity in cells
 SSC_AUTO, SSC_ONCHIP, SSC_GLOBAL = 0, 1, 2
 SSC_ONCHIP_CELLS = 524288
@@ -210,6 +212,12 @@ class AlignParams(C.Structure):
     _fields_ = [("max_bits", C.c_int32), ("exclude", C.c_int32)]
 
 
+class FlowParams(C.Structure):
+    """``pano_flow_params`` of include/pano360.h (16 bytes)."""
+    _fields_ = [("levels", C.c_int32), ("gain", C.c_int32), ("min_overlap", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class DeghostStack(C.Structure):
     """``pano_deghost_stack`` of include/pano360.h (320 bytes)."""
     _fields_ = [("src", C.c_void_p * FUSE_MAX_EXPOSURES), ("src_pitch", C.c_int64 * FUSE_MAX_EXPOSURES),
@@ -251,7 +259,7 @@ RECORDS = {
     "pano_photo_frame": PhotoFrame, "pano_photo_pair": PhotoPair, "pano_photo_apply": PhotoApply,
     "pano_fuse_stack": FuseStack, "pano_fuse_params": FuseParams, "pano_align_stack": AlignStack,
     "pano_align_params": AlignParams, "pano_deghost_stack": DeghostStack,
-    "pano_deghost_params": DeghostParams, "pano_stitch_args": StitchArgs,
+    "pano_deghost_params": DeghostParams, "pano_flow_params": FlowParams, "pano_stitch_args": StitchArgs,
 }
 
 _vp, _i = C.c_void_p, C.c_int
@@ -322,6 +330,12 @@ _SIGNATURES = {
     "pano_seam_route_prepare": (_i, [_vp, _vp, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "pano_seam_route_flood": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "pano_seam_route": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp]),
+    "pano_flow_work_bytes": (C.c_size_t, [C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams)]),
+    "pano_flow_pyramid": (_i, [_vp, C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams), _vp, C.c_int64]),
+    "pano_flow_search": (_i, [_vp, C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams), _vp, C.c_int64]),
+    "pano_flow_smooth": (_i, [_vp, C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams), _vp, C.c_int64]),
+    "pano_flow_apply": (_i, [_vp, C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams), _vp, C.c_int64, _vp, _vp]),
+    "pano_flow_align": (_i, [_vp, C.POINTER(Patch), _i, _i, _i, C.POINTER(FlowParams), _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "pano_resize_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
     "pano_sift_extrema": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _vp,
                                _vp, _i]),

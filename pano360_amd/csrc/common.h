@@ -183,6 +183,8 @@ enum PanoBufId {
     BUF_ROUTE_HOST,
     BUF_ROUTE_PLANES,
     BUF_ROUTE_PAIRS_HOST,
+    // pano_flow_* (flow.hip): the records of a call's launches
+    BUF_FLOW_DEV,
     PANO_BUF_COUNT
 };
 // Makes `b` hold at least `need` bytes.  A buffer that is large enough is left alone; otherwise it

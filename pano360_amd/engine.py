@@ -869,6 +869,13 @@ class Engine:
         mosaic, fl = self.blur_and_compose(table, owner, valid, shape, n_levels, want_float)
         return mosaic, fl, owner, valid
 
+    def flow_align(self, patches, shape, params=None):
+        """The stage-level patches aligned locally (``flow.align_device``):
+        (patches, statistics).  The masks are shared, patches without a partner come back as
+        they are."""
+        from . import flow
+        return flow.align_device(patches, tuple(shape), params, self)
+
     def interior_map(self, owner, radius, strip=None):
         """uint8 [ceil(H/B)][ceil(W/B)], B = the library's interior block: B x B blocks whose
         pixels all have a single owner within ``radius`` - there the multiband mosaic is the

@@ -25,6 +25,7 @@ import time
 
 import numpy as np
 
+from . import _lib
 from . import bundle_adj as _ba
 from . import engine as _eng
 from . import fuse as _fuse
@@ -269,7 +270,7 @@ def _download_patches(dev_patches):
     return out
 
 
-def stitch(regions, blender=no_blend, equalize=False, crop=False):
+def stitch(regions, blender=no_blend, equalize=False, crop=False, local_align=None):
     """Stitch the images together (stitcher.py:274-327).
 
     ``regions``: list of ``bundle_adj.Image``.  Side effects kept from the
@@ -281,8 +282,15 @@ def stitch(regions, blender=no_blend, equalize=False, crop=False):
     Accuracy: none / linear and every integer result (valid mask, crop rectangle) equal
     the reference's bit for bit; multiband is within one uint8 level and 1e-4 relative L2
     (see ``EXACT`` above for the two modes).
+
+    ``local_align`` (a ``flow.FlowParams``): the warped patches are aligned locally before the
+    blend (``flow.align_device``), and every blender takes the stage path:
+    warp, align, blend.  The valid mask and the crop rectangle are those without it.
     """
-    return _download_cropped(*_stitch_device(regions, blender, equalize, crop))
+    if local_align is None:
+        return _download_cropped(*_stitch_device(regions, blender, equalize, crop))
+    return _download_cropped(*_stitch_device_valid(regions, blender, equalize, crop, False,
+                                                   local_align=local_align)[:2])
 
 
 def _stitch_device(regions, blender, equalize, crop):
@@ -292,21 +300,26 @@ def _stitch_device(regions, blender, equalize, crop):
     return _stitch_device_geometry(regions, blender, equalize, crop)[:2]
 
 
-def _stitch_device_geometry(regions, blender, equalize, crop, tol=None, ratio=None):
+def _stitch_device_geometry(regions, blender, equalize, crop, tol=None, ratio=None,
+                            local_align=None):
     """``_stitch_device`` and, third, the ``view.MosaicGeometry`` of the whole mosaic (where its
     pixels lie on the sphere: the plan's ``low``, ``resolution`` and ``shape``); the cropped
     mosaic's is ``geometry.cropped(rect)``."""
-    return _stitch_device_valid(regions, blender, equalize, crop, False, tol, ratio)[:3]
+    return _stitch_device_valid(regions, blender, equalize, crop, False, tol, ratio,
+                                local_align)[:3]
 
 
-def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=None, ratio=None):
+def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=None, ratio=None,
+                         local_align=None):
     """``_stitch_device_geometry`` and, fourth, the valid mask the stitch computes (uint8 [H][W] on
     the device, 1 = some frame covers the pixel): ``eng.stitch``'s third result, or
     ``eng.ownership`` of the warped patches for a custom blender, as under ``crop``.  Without
     ``want_valid`` a custom blender's mask is only computed for the crop (else None).  ``tol``:
     ``median_blend``'s tolerance for this stitch (None = ``GHOST_TOL``), ``ratio``: ``seam_blend``'s
     zone (None = ``SEAM_RATIO``); no other blender reads them.  ``seam_blend`` stays on the device
-    too, on the stage path: the warped patches go to ``eng.seam_multiband`` as they are."""
+    too, on the stage path: the warped patches go to ``eng.seam_multiband`` as they are.
+    ``local_align`` (a ``flow.FlowParams``): every blender takes the stage path, with
+    ``eng.flow_align`` between the warp and the blend."""
     from . import view as _view
     eng = _engine_for_stitch()
     frames_host = [reg.img for reg in regions]
@@ -330,7 +343,10 @@ def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=
     eng.upload_plan(plan)
 
     kind = _FUSED.get(blender)
-    if kind is not None:
+    if local_align is not None:
+        mosaic, valid, patches = _blend_aligned(eng, frames, plan, luts, blender, kind, local_align,
+                                                tol, ratio)
+    elif kind is not None:
         n_levels = multiband_blend.__defaults__[0]
         extra = {"tol": _ghost_tol(tol)} if kind == "median" else {}
         mosaic, _, valid, patches = eng.stitch(frames, plan, kind, n_levels, luts=luts,
@@ -356,6 +372,30 @@ def _stitch_device_valid(regions, blender, equalize, crop, want_valid=True, tol=
         if rect is None:
             raise UnboundLocalError("local variable 'last' referenced before assignment")
     return mosaic, rect, _view.MosaicGeometry.of_plan(plan), valid
+
+
+def _blend_aligned(eng, frames, plan, luts, blender, kind, params, tol, ratio):
+    """The stage path behind ``local_align``: ``warp_all`` (with the blur planes for multiband and
+    seam), ``flow_align``, then the blender's stage call on the aligned patches.  Returns (mosaic,
+    valid or None, patches); a custom blender gets the aligned patches downloaded."""
+    from . import flow as _flow
+    banded = blender in (multiband_blend, seam_blend)
+    n_levels = multiband_blend.__defaults__[0]
+    patches, _ = eng.warp_all(frames, plan, n_blur=n_levels - 1 if banded else 0, luts=luts)
+    patches, stats = eng.flow_align(patches, plan.shape, params)
+    _flow.log_statistics(stats)
+    valid = None
+    if blender == seam_blend:
+        mosaic, _, _, valid = eng.seam_multiband(patches, plan.shape, n_levels, _seam_ratio(ratio))
+    elif kind == "multiband":
+        mosaic, _, _, valid = eng.multiband(patches, plan.shape, n_levels)
+    elif kind == "median":
+        mosaic = eng.median_blend(patches, plan.shape, _ghost_tol(tol))
+    elif kind is not None:
+        mosaic = eng.simple_blend(patches, plan.shape, linear=kind == "linear")
+    else:
+        mosaic = blender(_download_patches(patches), plan.shape)
+    return mosaic, valid, patches
 
 
 def _download_cropped(mosaic, rect):
@@ -551,6 +591,15 @@ def _zone_ratio(text):
     return value
 
 
+def local_align_of(args):
+    """The ``flow.FlowParams`` that ``--local-align`` and ``--local-align-levels`` ask for, or
+    None."""
+    if not getattr(args, "local_align", False):
+        return None
+    from . import flow as _flow
+    return _flow.FlowParams(levels=getattr(args, "local_align_levels", 3))
+
+
 def refine_of(args):
     """(whether to refine, the radial terms to fit or None): what ``--refine`` and
     ``--refine-lens`` asked for."""
@@ -579,6 +628,14 @@ def parse_args(argv=None):
     parser.add_argument("--seam-ratio", type=_zone_ratio, metavar="FLOAT", default=argparse.SUPPRESS,
                         help="-b seam: the seam may move wherever the runner-up frame's weight is "
                              f"at least this share of the owner's (in (0, 1]; default {SEAM_RATIO}).")
+    parser.add_argument("--local-align", action="store_true", default=argparse.SUPPRESS,
+                        help="align overlapping frames locally before the blend: what a hand-held "
+                             "sweep's parallax doubles is moved to where the frames meet (every "
+                             "blender; DESIGN.md section 5u).")
+    parser.add_argument("--local-align-levels", type=int, choices=range(_lib.FLOW_MAX_LEVELS + 1),
+                        default=argparse.SUPPRESS, metavar="N",
+                        help="--local-align: pyramid levels of the search, a reach of "
+                             "2^(N+1) - 1 pixels (0 .. 4; default 3).")
     parser.add_argument("-o", "--out", type=str, help="save result to this file")
     parser.add_argument("--register", action="store_true",
                         help="without a camera cache, match the images and run bundle "
@@ -632,6 +689,8 @@ def parse_args(argv=None):
         parser.error("--ghost-tol needs -b median")
     if hasattr(args, "seam_ratio") and args.blend != "seam":
         parser.error("--seam-ratio needs -b seam")
+    if hasattr(args, "local_align_levels") and not hasattr(args, "local_align"):
+        parser.error("--local-align-levels needs --local-align")
     if args.fill and args.crop:
         parser.error("--fill and --crop exclude each other: a cropped mosaic has nothing to fill")
     if (args.view or args.equirect or args.cube) and not args.out:
@@ -719,13 +778,15 @@ def main(argv=None):
         dev_mosaic, rect, geom, valid = _stitch_device_valid(regions, BLENDERS[args.blend],
                                                              args.equalize, False,
                                                              tol=args.ghost_tol,
-                                                             ratio=getattr(args, "seam_ratio", None))
+                                                             ratio=getattr(args, "seam_ratio", None),
+                                                             local_align=local_align_of(args))
         dev_mosaic, background = _filled(args, dev_mosaic, geom, valid)
     else:
         dev_mosaic, rect, geom = _stitch_device_geometry(regions, BLENDERS[args.blend],
                                                          args.equalize, args.crop,
                                                          tol=args.ghost_tol,
-                                                         ratio=getattr(args, "seam_ratio", None))
+                                                         ratio=getattr(args, "seam_ratio", None),
+                                                         local_align=local_align_of(args))
     mosaic = _download_cropped(dev_mosaic, rect)
     logging.info(f"Built mosaic, time: {time.time() - start}")
     if args.out:
